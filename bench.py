@@ -23,11 +23,20 @@ would be measured on almost-empty rings: nearly all-pad output).  If the timed s
 reach the end of the stream the state is reset and the stream restarts (an epoch
 boundary); the default step count stops before that.
 
-Rank 0 prints ONE JSON line (contract in the task statement) with two extra
-objects: "roofline" (dominant kernel = the hop-1 lookup/gather launch, timed with
-HIP events on its launch stream inside the timed region) and "cpu_baseline" (the
-reference algorithm restated for torch-CPU, oracle/ring_port.py, timed on this
-box's host cores on a bounded sample of the same stream; N=1 only).
+Rank 0 prints ONE JSON line (metric, value, unit, higher_is_better, dtype,
+ms_per_step, ...) with an extra object "roofline" (dominant kernel = the hop-1 lookup/gather launch, timed with
+HIP events on its launch stream inside the timed region).
+
+``--full`` adds everything that takes work of its own beyond the timed steps:
+"cpu_baseline" (the reference algorithm restated for torch-CPU, oracle/ring_port.py,
+timed on this box's host cores on a bounded sample of the same stream; N=1 only),
+"default_path" (the same steps through the library's default arguments), the
+extras blocks (--extras) and, at N > 1, "rccl", "scale_comment" and
+"tgn_memory_allgather".  A plain run sets up, warms up, times the steps and prints.
+
+``--dump-outputs DIR`` writes the batch the timed path returned in its last step
+as DIR/<field>.npy (float32 features, float64 ids / times / masks; a fixed, seeded
+row sample of any array too large for the 64 MB budget).
 """
 from __future__ import annotations
 
@@ -55,7 +64,10 @@ def parse_args():
     p.add_argument('--batch-size', type=int, default=None, help='edges per rank per step (default: 200 wiki, 512 review, 4096 comment)')
     p.add_argument('--num-nbrs', type=int, nargs='+', default=None)
     p.add_argument('--mode', default='ring', choices=['ring', 'csr'])
-    p.add_argument('--cpu-batches', type=int, default=30, help='batches of the CPU-baseline sample PER thread setting (0 = skip); ~0.1 s each: 30 x 4 settings = ~12 s of CPU work')
+    p.add_argument('--full', action='store_true', help='also measure what the headline does not need: CPU baseline, default-path region, extras, '
+                   'and at N > 1 the RCCL / scale_comment / tgn_memory_allgather blocks')
+    p.add_argument('--dump-outputs', metavar='DIR', default=None, help="write the timed path's last batch as DIR/<field>.npy (at most 64 MB)")
+    p.add_argument('--cpu-batches', type=int, default=30, help='--full: batches of the CPU-baseline sample PER thread setting (0 = skip); ~0.1 s each: 30 x 4 settings = ~12 s of CPU work')
     p.add_argument('--scaling', default='weak', choices=['weak', 'strong', 'batch'],
                    help="N > 1: 'weak' = global batch N x bs, rank r seeds from its slice; 'strong' = global batch bs, split N ways; 'batch' = "
                    "the single-GPU schedule of bs-edge batches dealt round-robin to the ranks (DGDataLoader(batch_shard=), static index only: "
@@ -70,12 +82,12 @@ def parse_args():
     p.add_argument('--emulate-rank', type=int, default=0)
     p.add_argument('--extras', default='auto', choices=['auto', 'on', 'off'],
                    help="the blocks next to the contract's fields -- the same launch with full feature writes / an output pool of two, the "
-                   "HBM-bound comment-shaped lookup (roofline_hbm_bound), the TGAT aggregation block: 'auto' = at N = 1 on the wiki workload")
+                   "HBM-bound comment-shaped lookup (roofline_hbm_bound), the TGAT aggregation block: 'auto' = under --full, at N = 1 on the wiki workload")
     p.add_argument('--scale-comment', default='on', choices=['on', 'off'],
-                   help='N > 1: also measure the comment-shaped stream over the static index, batch-sharded and weak, in the same job (scale_comment)')
+                   help='--full, N > 1: also measure the comment-shaped stream over the static index, batch-sharded and weak, in the same job (scale_comment)')
     p.add_argument('--tgn-allgather', default='on', choices=['on', 'off'],
-                   help='N > 1: also time the TGN memory module with the commit sharded across the ranks and all-gathered (tgn_memory_allgather)')
-    p.add_argument('--no-default-path', action='store_true', help="skip the second timed region (the same steps through DGDataLoader / RecencyNeighborHook with their DEFAULT arguments)")
+                   help='--full, N > 1: also time the TGN memory module with the commit sharded across the ranks and all-gathered (tgn_memory_allgather)')
+    p.add_argument('--no-default-path', action='store_true', help="--full: skip the second timed region (the same steps through DGDataLoader / RecencyNeighborHook with their DEFAULT arguments)")
     return p.parse_args()
 
 
@@ -271,6 +283,42 @@ def slots_of_shape(edges, num_nbrs):
         total += S * k
         S *= k
     return total
+
+
+DUMP_BUDGET_BYTES = 64 * 2**20
+
+
+def dump_outputs(batch, out_dir, seed=0):
+    """What a caller of the timed path receives from one step: every public tensor of the batch (per-hop lists as <name>_<hop>),
+    floats as float32, ids / times / masks as float64 (exact below 2^53).  The 64 MB budget is shared out smallest array first
+    (what a small array leaves goes to the larger ones); an array above its share keeps a fixed, seeded sample of its rows (the
+    same rows for the same shape, so two builds compare row for row)."""
+    import numpy as np
+
+    arrays = {}
+    for name, v in sorted(vars(batch).items()):
+        if name.startswith('_'):
+            continue
+        if isinstance(v, torch.Tensor):
+            arrays[name] = v
+        elif isinstance(v, (list, tuple)):
+            items = list(v)
+            if items and all(isinstance(t, torch.Tensor) for t in items):
+                arrays.update((f'{name}_{h}', t) for h, t in enumerate(items))
+    dtypes = {n: torch.float32 if t.is_floating_point() and t.element_size() <= 4 else torch.float64 for n, t in arrays.items()}
+    nbytes = {n: t.numel() * (4 if dtypes[n] == torch.float32 else 8) for n, t in arrays.items()}
+    budget, left = DUMP_BUDGET_BYTES, len(arrays)
+    os.makedirs(out_dir, exist_ok=True)
+    for name in sorted(arrays, key=lambda n: (nbytes[n], n)):
+        t, share = arrays[name], budget // left
+        if t.dim() and t.shape[0] and nbytes[name] > share:
+            keep = max(1, share // (nbytes[name] // t.shape[0]))
+            rows = np.sort(np.random.default_rng(seed).choice(t.shape[0], keep, replace=False))
+            t = t.index_select(0, torch.from_numpy(rows).to(t.device))
+        a = t.detach().to(dtypes[name]).cpu().numpy()
+        np.save(os.path.join(out_dir, f'{name}.npy'), a)
+        budget, left = budget - a.nbytes, left - 1
+    return sorted(arrays)
 
 
 def launch_stats(log, D):
@@ -615,6 +663,9 @@ def main():
     # host-side tensor work of this process (stream generation, DGData's checks) on 16 threads: torch's default is every core, and on a SHARED
     # 256-core host the OpenMP barriers of small ops under oversubscription made single runs take a minute longer than others
     torch.set_num_threads(min(16, torch.get_num_threads()))
+    # the negative sampler's device generator starts from torch.initial_seed(), which differs per process unless seeded: the same
+    # arguments must give the same negatives (and so the same sampled neighbours) from run to run
+    torch.manual_seed(args.seed)
     rank, world, local = init_process_group()
     assert world == args.gpus, f'--gpus {args.gpus} but WORLD_SIZE={world}'
     real_world = world
@@ -665,11 +716,15 @@ def main():
         """n_steps consecutive batches, wrapping around the stream (epoch boundary = reset_state)."""
         it = state['it']
         edges = 0
-        for _ in range(n_steps):
+        state['last'] = None
+        for i in range(n_steps):
             if it == n_batches:
                 hm.reset_state()
                 it = 0
-            loader(starts[it])
+            if i == n_steps - 1:
+                state['last'] = loader(starts[it])  # only the last batch is held (--dump-outputs)
+            else:
+                loader(starts[it])
             if count:
                 e_lo = starts[it]
                 edges += min(global_bs, stream.num_edges - e_lo)
@@ -702,12 +757,15 @@ def main():
             torch.distributed.barrier()
         elapsed = time.perf_counter() - t0
         hook.check()
+        if args.dump_outputs and (rank == 0 or args.emulate_world):
+            dump_outputs(state['last'], args.dump_outputs)
+        state['last'] = None
 
     # ---- the same steps through the library's DEFAULT arguments (what an unmodified TGM script gets): DGDataLoader(dg, bs,
     # hook_manager=hm) + RecencyNeighborHook(...) with validate='sync'; the consumer holds batch i while batch i + 1 is produced,
     # like `for batch in loader` does ----
     default_elapsed = None
-    if not args.no_default_path and args.mode == 'ring':
+    if args.full and not args.no_default_path and args.mode == 'ring':
         dg2, hm2, hook2, loader2 = build_pipeline(stream, rank, world, global_bs, num_nbrs, args.mode, device, pool=None, validate=None)
         with hm2.activate('bench'):
             it, held = 0, None
@@ -783,7 +841,7 @@ def main():
     # ---- N > 1: proof that N ranks met over RCCL (the data path itself has no collective): ranks counted by an all-reduce,
     # and what a small all-reduce costs on this node's xGMI links ----
     rccl = None
-    if real_world > 1:
+    if real_world > 1 and args.full:
         import torch.distributed as dist
 
         ones = torch.ones(1, dtype=torch.float32, device=device)
@@ -890,7 +948,7 @@ def main():
         },
     }
     # ---- what the headline fraction does NOT say, measured in this process on the same timed batches (N = 1, wiki) --------------
-    extras = args.extras == 'on' or (args.extras == 'auto' and real_world == 1 and not args.emulate_world and args.workload == 'wiki' and args.mode == 'ring'
+    extras = args.extras == 'on' or (args.extras == 'auto' and args.full and real_world == 1 and not args.emulate_world and args.workload == 'wiki' and args.mode == 'ring'
                                      and args.pool == 1)
     rl = out['roofline']
     rl['traffic'] = pmc_traffic(pkey, rl)
@@ -993,13 +1051,13 @@ def main():
             "that does not shrink with N), only the lookups are sharded.  The multi-GPU mode of this library is the static index "
             "(RecencyNeighborHook(mode='csr'): no per-batch state, no replicated update, no data-path collective): scale_comment below measures it on "
             "north_star's scaling shape in this same job, batch-sharded (DGDataLoader(batch_shard=)) and weak (EdgeShardHook).")
-    if real_world > 1 and args.scale_comment != 'off':
+    if real_world > 1 and args.full and args.scale_comment != 'off':
         try:
             out['scale_comment'] = scale_comment_block(args, rank, world, device)
             out['scale_comment']['rccl_ranks_seen'] = rccl['ranks_seen']
         except Exception as exc:  # noqa: BLE001 -- every rank takes the same path (the block's collectives are symmetric)
             out['scale_comment'] = {'error': f'{type(exc).__name__}: {exc}'[:300]}
-    if real_world > 1 and args.tgn_allgather != 'off':
+    if real_world > 1 and args.full and args.tgn_allgather != 'off':
         try:
             out['tgn_memory_allgather'] = tgn_memory_allgather_block(args, rank, world, device)
         except Exception as exc:  # noqa: BLE001 -- symmetric across ranks, like scale_comment
@@ -1021,7 +1079,7 @@ def main():
             'host_busy_us_per_step': 1e6 * host_busy,
         }
     if rank == 0 or args.emulate_world:
-        if world == 1 and real_world == 1 and args.cpu_batches > 0:
+        if args.full and world == 1 and real_world == 1 and args.cpu_batches > 0:
             out['cpu_baseline'] = cpu_baseline(stream, bs, num_nbrs, args.cpu_batches, args.seed, first_timed)
         else:
             out['cpu_baseline'] = None

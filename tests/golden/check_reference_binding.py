@@ -18,8 +18,11 @@ code, the claims a maintainer relies on when dropping our hooks into the referen
      (``replay_reference_tests.py``, its own process: this one has the real ``tgm`` imported).
 
 Prints one line per check and exits non-zero on the first failure.  No kernel runs (no GPU here).
+With ``--write`` it also records what checks 1-5 read from the reference (protocol members, requires / produces / has_state,
+resolved hook orders, DGBatch fields, the TGAT state_dict layout) as the fixture ``g14_reference_binding.json``, which
+``tests/test_host_cpu.py::test_reference_side_binding_script`` checks our classes against.
 
-    python tests/golden/check_reference_binding.py
+    python tests/golden/check_reference_binding.py [--write]
 """
 from __future__ import annotations
 
@@ -115,6 +118,39 @@ def main() -> None:
     tail = [ln for ln in r.stdout.splitlines() if ln.startswith('[replay]')]
     assert r.returncode == 0, '\n'.join(tail) or r.stdout[-2000:] + r.stderr[-2000:]
     ok(tail[0][len('[replay] '):])
+    if '--write' in sys.argv[1:]:
+        record(theirs, N, ks, keys, tkeys, kw, a)
+
+
+def record(theirs, N, ks, keys, tkeys, tgat_kw, tgat_state) -> None:
+    """Checks 1-5's reference side as data: tests/golden/g14_reference_binding.json."""
+    import json
+    import typing
+
+    orders = [('nbr', 'neg', 'dedup'), ('dedup', 'nbr', 'neg'), ('dedup', 'neg', 'nbr'), ('neg', 'nbr', 'dedup')]
+    resolved = {}
+    for order in orders:
+        hm = ref_hooks.HookManager(keys=['k'])
+        for name in order:
+            hm.register('k', theirs[name])
+        hm.resolve_hooks('k')
+        resolved[','.join(order)] = [type(h).__name__ for h in hm._key_to_hooks['k']]
+    fixture = {
+        'what': 'the reference side of tests/golden/check_reference_binding.py checks 1-5, recorded by its --write mode',
+        'hook_args': {'num_nodes': N, 'num_nbrs': ks, 'seed_nodes_keys': keys, 'seed_times_keys': tkeys},
+        'dghook_protocol': sorted(typing._get_protocol_attrs(RefDGHook)),
+        'hooks': {name: {'class': type(h).__name__, 'requires': sorted(h.requires), 'produces': sorted(h.produces),
+                         'has_state': bool(type(h).has_state)} for name, h in theirs.items()},
+        'resolved_order': resolved,
+        'dgbatch_fields': [[f.name, f.default is not dataclasses.MISSING, None if f.default is dataclasses.MISSING else f.default]
+                           for f in dataclasses.fields(tgm.DGBatch)],
+        'tgat_kwargs': tgat_kw,
+        'tgat_state_dict': [[k, list(v.shape), str(v.dtype)] for k, v in tgat_state.items()],
+    }
+    with open(os.path.join(HERE, 'g14_reference_binding.json'), 'w') as f:
+        json.dump(fixture, f, indent=1)
+        f.write('\n')
+    ok('wrote g14_reference_binding.json')
 
 
 if __name__ == '__main__':
