@@ -914,6 +914,66 @@ int tgmx_tconv_attend_backward(const float* q, const float* k, const float* v, c
                                int32_t C, float scale, const float* dout, float* dq, float* dk, float* dv, float* de,
                                const tgmx_dropout_t* drop /* the forward's, NULL = off */, tgmx_stream_t stream);
 
+/* ---- GraphMixer (the reference's examples/linkproppred/graphmixer.py: MLPMixer link encoder + time-gap node encoder), inference ---- */
+
+/* C = act(A B^T + bias) + res: tgmx_sgemm_nt's kernels and its M-band summation contract (one problem, no batch) with a wider epilogue:
+ * act 0 = none, 1 = ReLU, 2 = exact-erf GELU (torch.nn.GELU()); res [M, N] (leading dimension ldr, may be NULL) is added after the
+ * activation -- the MLPMixer's "x + FFN(x)" in the second Linear's store. */
+int tgmx_sgemm_nt_ep(const float* A, int64_t lda, const float* B, int64_t ldb, float* C, int64_t ldc, int64_t M, int32_t N, int32_t K,
+                     const float* bias, int32_t act, const float* res, int64_t ldr, tgmx_stream_t stream);
+
+/* Time-gap neighbours of a batch: the window's W edges (src / dst + e_lo, stream order) as 2 W incidences (u_j -> v_j), (v_j -> u_j),
+ * stably grouped by node id: out_nbr [2 W] holds every node's neighbours in stream order (a self loop twice), and for each seed i of
+ * the concatenation seeds0[:n0] | seeds1[:n1] | seeds2[:n2] its run out_nbr[out_lo[i] : out_lo[i] + out_cnt[i]].  Sizes are host
+ * integers: no device -> host read.  workspace: 256-byte aligned, tgmx_time_gap_workspace_bytes(W) bytes. */
+size_t tgmx_time_gap_workspace_bytes(int64_t W);
+int tgmx_time_gap_group(const int32_t* src, const int32_t* dst, int64_t e_lo, int64_t W, const int32_t* seeds0, int64_t n0,
+                        const int32_t* seeds1, int64_t n1, const int32_t* seeds2, int64_t n2, void* workspace, size_t workspace_bytes,
+                        int32_t* out_nbr, int32_t* out_lo, int32_t* out_cnt, tgmx_stream_t stream);
+
+/* Link-encoder prologue: out[r, :] = [edge_x[r, :D] | cos(fma(float(seed_t[r / K] - nbr_t[r]), tw, tb)) | 0 pad], r < S K, ldo >= D + T. */
+int tgmx_mixer_prologue(const float* edge_x, const int64_t* seed_t, const int64_t* nbr_t, int64_t S, int32_t K, int32_t D,
+                        const float* tw, const float* tb, int32_t T, float* out, int64_t ldo, tgmx_stream_t stream);
+
+/* One MLPMixer token-mixing block on x [S, K, C] (row (s, k) at x + (s K + k) ldx): per seed and channel, LayerNorm over the K tokens
+ * (tok_g / tok_b [K], biased variance), Linear K -> Ht, exact-erf GELU, Linear Ht -> K, plus the residual: z1 = x + that.  Also writes
+ * y = LayerNorm over the C channels of every token of z1 (ch_g / ch_b [C]) -- the channel FFN's input.  z1 / y share the leading
+ * dimension ldo.  Needs K C + (K + Ht) 128 floats of LDS per workgroup (at most 64 KiB), otherwise TGMX_E_UNSUPPORTED. */
+int tgmx_mixer_token(const float* x, int64_t ldx, int64_t S, int32_t K, int32_t C, const float* tok_g, const float* tok_b,
+                     const float* w1, const float* b1, int32_t Ht, const float* w2, const float* b2, const float* ch_g,
+                     const float* ch_b, float eps, float* z1, float* y, int64_t ldo, tgmx_stream_t stream);
+
+/* GraphMixer tail, one row per seed i < S (seed id: the concatenation seeds0 | seeds1 | seeds2):
+ * out[i, :C] = sum_k z[i, k, :] [nbr_nids[i, k] != -1] / max(1, count), out[i, C : C + F] = mean of node_x over the seed's time-gap run
+ * (0 when empty) + node_x[seed], columns [C + F, ldo) zeroed. */
+int tgmx_mixer_tail(const float* z, int64_t ldz, int64_t S, int32_t K, int32_t C, const int32_t* nbr_nids, const float* node_x,
+                    int64_t num_nodes, int32_t F, const int32_t* tg_nbr, const int32_t* tg_lo, const int32_t* tg_cnt,
+                    const int32_t* seeds0, int64_t n0, const int32_t* seeds1, int64_t n1, const int32_t* seeds2, float* out,
+                    int64_t ldo, tgmx_stream_t stream);
+
+/* The GraphMixerEncoder inference forward as ONE call: tgmx_mixer_prologue, the projection GEMM, per layer tgmx_mixer_token and the
+ * channel FFN's two GEMMs (GELU epilogue; residual epilogue), tgmx_mixer_tail and the output GEMM -- the same launches in the same order
+ * as the entry points above called one by one (identical results).  Weights row-major as nn.Linear keeps them.  Scratch: x0 [S K, ldx0],
+ * z / z1 / y [S K, ldz], h [S K, ldh], cat [S, ldcat]; every leading dimension a multiple of 4 (16-byte aligned GEMM operands). */
+#define TGMX_MIXER_MAX_LAYERS 8
+typedef struct tgmx_mixer_layer {
+  const float *tok_g, *tok_b, *tok_w1, *tok_b1, *tok_w2, *tok_b2;  /* token_norm, token_feedforward.ffn.{0,3} */
+  const float *ch_g, *ch_b, *ch_w1, *ch_b1, *ch_w2, *ch_b2;        /* channel_norm, channel_feedforward.ffn.{0,3} */
+  int32_t tok_hidden, ch_hidden;
+} tgmx_mixer_layer_t;
+typedef struct tgmx_graphmixer_fwd {
+  const float* nbr_edge_x; const int64_t* seed_t; const int64_t* nbr_t; const int32_t* nbr_nids;  /* hop 0: [S, K, D], [S], [S, K], [S, K] */
+  const int32_t* seeds[3]; int64_t n_seeds[3];                                                     /* edge_src | edge_dst | neg */
+  const int32_t* tg_nbr; const int32_t* tg_lo; const int32_t* tg_cnt;                              /* TimeGapNeighborHook */
+  const float* node_x; int64_t num_nodes; int32_t F;                                               /* static node features [num_nodes, F] */
+  int64_t S; int32_t K, D, T, E, num_layers; float eps;
+  const float *tw, *tb, *proj_w, *proj_b, *out_w, *out_b;
+  tgmx_mixer_layer_t layers[TGMX_MIXER_MAX_LAYERS];
+  float *x0, *z, *z1, *y, *h, *cat; int64_t ldx0, ldz, ldh, ldcat;
+  float* out;                                                                                      /* [S, E] */
+} tgmx_graphmixer_fwd_t;
+int tgmx_graphmixer_forward(const tgmx_graphmixer_fwd_t* args, tgmx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -232,6 +232,33 @@ class TgcnFwd(ctypes.Structure):
     ]  # fmt: skip
 
 
+MIXER_MAX_LAYERS = 8  # TGMX_MIXER_MAX_LAYERS
+
+
+class MixerLayer(ctypes.Structure):
+    """tgmx_mixer_layer_t (include/tgm_amd.h)."""
+
+    _fields_ = [(n, c_void_p) for n in ('tok_g', 'tok_b', 'tok_w1', 'tok_b1', 'tok_w2', 'tok_b2', 'ch_g', 'ch_b', 'ch_w1', 'ch_b1', 'ch_w2',
+                                        'ch_b2')] + [('tok_hidden', c_int32), ('ch_hidden', c_int32)]  # fmt: skip
+
+
+class GraphMixerFwd(ctypes.Structure):
+    """tgmx_graphmixer_fwd_t (include/tgm_amd.h)."""
+
+    _fields_ = [
+        ('nbr_edge_x', c_void_p), ('seed_t', c_void_p), ('nbr_t', c_void_p), ('nbr_nids', c_void_p),
+        ('seeds', c_void_p * 3), ('n_seeds', c_int64 * 3),
+        ('tg_nbr', c_void_p), ('tg_lo', c_void_p), ('tg_cnt', c_void_p),
+        ('node_x', c_void_p), ('num_nodes', c_int64), ('F', c_int32),
+        ('S', c_int64), ('K', c_int32), ('D', c_int32), ('T', c_int32), ('E', c_int32), ('num_layers', c_int32), ('eps', ctypes.c_float),
+        ('tw', c_void_p), ('tb', c_void_p), ('proj_w', c_void_p), ('proj_b', c_void_p), ('out_w', c_void_p), ('out_b', c_void_p),
+        ('layers', MixerLayer * MIXER_MAX_LAYERS),
+        ('x0', c_void_p), ('z', c_void_p), ('z1', c_void_p), ('y', c_void_p), ('h', c_void_p), ('cat', c_void_p),
+        ('ldx0', c_int64), ('ldz', c_int64), ('ldh', c_int64), ('ldcat', c_int64),
+        ('out', c_void_p),
+    ]  # fmt: skip
+
+
 class TconvFwd(ctypes.Structure):
     """tgmx_tconv_fwd_t (include/tgm_amd.h)."""
 
@@ -324,6 +351,20 @@ SIGNATURES['tgmx_tgat_forward'] = (
     c_int32,
     [ctypes.POINTER(TgatModel), _P, c_int64, _P, c_int64, ctypes.POINTER(TgatHop), _P, c_size_t, c_int32, _P, _P],
 )
+
+SIGNATURES['tgmx_sgemm_nt_ep'] = (c_int32, [_P, c_int64, _P, c_int64, _P, c_int64, c_int64, c_int32, c_int32, _P, c_int32, _P, c_int64, _P])
+SIGNATURES['tgmx_time_gap_workspace_bytes'] = (c_size_t, [c_int64])
+SIGNATURES['tgmx_time_gap_group'] = (c_int32, [_P, _P, c_int64, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, _P, c_size_t, _P, _P, _P, _P])
+SIGNATURES['tgmx_mixer_prologue'] = (c_int32, [_P, _P, _P, c_int64, c_int32, c_int32, _P, _P, c_int32, _P, c_int64, _P])
+SIGNATURES['tgmx_mixer_token'] = (
+    c_int32,
+    [_P, c_int64, c_int64, c_int32, c_int32, _P, _P, _P, _P, c_int32, _P, _P, _P, _P, ctypes.c_float, _P, _P, c_int64, _P],
+)
+SIGNATURES['tgmx_mixer_tail'] = (
+    c_int32,
+    [_P, c_int64, c_int64, c_int32, c_int32, _P, _P, c_int64, c_int32, _P, _P, _P, _P, c_int64, _P, c_int64, _P, _P, c_int64, _P],
+)
+SIGNATURES['tgmx_graphmixer_forward'] = (c_int32, [ctypes.POINTER(GraphMixerFwd), _P])
 
 _lib: Optional[ctypes.CDLL] = None
 

@@ -32,6 +32,8 @@ extern "C" size_t tgmx_abi_sizeof(int32_t which) {
     case 10: return sizeof(tgmx_tconv_fwd_t);
     case 11: return sizeof(tgmx_pipeline_post_t);
     case 12: return sizeof(tgmx_tgn_step_t);
+    case 13: return sizeof(tgmx_mixer_layer_t);
+    case 14: return sizeof(tgmx_graphmixer_fwd_t);
     default: return 0;
   }
 }

@@ -38,8 +38,18 @@ struct GemmArgs {
   const float* bias;
   long long lda, ldb, ldc, sA, sB, sC;
   long long M;
-  int N, K, relu;
+  int N, K, relu;  // epilogue activation: 0 none, 1 ReLU, 2 exact-erf GELU (tgmx_sgemm_nt_ep)
+  const float* res = nullptr;  // tgmx_sgemm_nt_ep: [M, N] (leading dimension ldr) added after the activation
+  long long ldr = 0;
 };
+
+// bias, activation, residual of one output element (the ReLU path is the arithmetic tgmx_sgemm_nt always had)
+__device__ __forceinline__ float gemm_act_res(const GemmArgs& g, float v, long long row, int col, unsigned bz) {
+  if (g.relu == 1) v = v > 0.f ? v : 0.f;
+  else if (g.relu == 2) v = 0.5f * v * (1.f + erff(v * 0.70710678118654752f));  // torch.nn.GELU(approximate='none')
+  if (g.res) v += g.res[(long long)bz * g.sC + row * g.ldr + col];
+  return v;
+}
 
 // One k-step covers 2 * kGemmK columns of K: lanes 0-31 hold the first kGemmK of their row, lanes 32-63 the next
 // kGemmK (any pairing of k with the two k-slots of the 32x32x2 MFMA is valid as long as A and B agree).
@@ -138,8 +148,7 @@ __device__ __forceinline__ void sgemm_nt_body(const GemmArgs& g, const unsigned 
       const int col = n0 + t * 32 + i;
       if (row < g.M && col < g.N) {
         if (g.bias) v += g.bias[(long long)bz * g.N + col];  // batch b adds row b of a [batch, N] bias
-        if (g.relu) v = v > 0.f ? v : 0.f;
-        C[row * g.ldc + col] = v;
+        C[row * g.ldc + col] = gemm_act_res(g, v, row, col, bz);
       }
     }
     return;
@@ -154,8 +163,7 @@ __device__ __forceinline__ void sgemm_nt_body(const GemmArgs& g, const unsigned 
       if (col < g.N) {
         float v = t ? acc1[r] : acc0[r];
         if (g.bias) v += g.bias[(long long)bz * g.N + col];  // batch b adds row b of a [batch, N] bias
-        if (g.relu) v = v > 0.f ? v : 0.f;
-        C[row * g.ldc + col] = v;
+        C[row * g.ldc + col] = gemm_act_res(g, v, row, col, bz);
       }
     }
   }
@@ -276,8 +284,7 @@ __device__ __forceinline__ void sgemm_nt_lds_body(const GemmArgs& g, const unsig
       if (row < g.M) {
         float v = acc[r];
         if (g.bias) v += bias;
-        if (g.relu) v = v > 0.f ? v : 0.f;
-        C[row * g.ldc + col] = v;
+        C[row * g.ldc + col] = gemm_act_res(g, v, row, col, bz);
       }
     }
   }
@@ -362,8 +369,7 @@ __global__ __launch_bounds__(512) void sgemm_nt_small_kernel(const GemmArgs g) {
     const int col = n0 + i;
     if (row < g.M && col < g.N) {
       if (g.bias) v += g.bias[(long long)blockIdx.z * g.N + col];
-      if (g.relu) v = v > 0.f ? v : 0.f;
-      C[row * g.ldc + col] = v;
+      C[row * g.ldc + col] = gemm_act_res(g, v, row, col, blockIdx.z);
     }
   }
 }
@@ -2382,6 +2388,7 @@ using namespace tgmx;
 // blocks per CU and the K-split kernel's four short chains per 32 x 64 tile finish sooner (4 100 x 172 x 172: 8.3 / 10.4 us).
 constexpr long long kGemmLdsMinRows = 6144;
 static bool gemm_takes_lds(long long M, int /*N*/, int /*batch*/) { return M >= kGemmLdsMinRows; }
+static int sgemm_nt_run(const GemmArgs& g, int32_t batch, tgmx_stream_t stream);
 
 extern "C" int tgmx_sgemm_nt(const float* A, int64_t lda, const float* B, int64_t ldb, float* C, int64_t ldc, int64_t M,
                              int32_t N, int32_t K, const float* bias, int32_t relu, int32_t batch, int64_t strideA,
@@ -2390,7 +2397,26 @@ extern "C" int tgmx_sgemm_nt(const float* A, int64_t lda, const float* B, int64_
   if (M == 0) return TGMX_OK;
   TGMX_REQUIRE(A && B && C, "sgemm_nt: null pointer");
   TGMX_REQUIRE(lda >= K && ldb >= K && ldc >= N, "sgemm_nt: leading dimension smaller than the row length");
-  GemmArgs g{A, B, C, bias, lda, ldb, ldc, strideA, strideB, strideC, M, N, K, relu};
+  return sgemm_nt_run(GemmArgs{A, B, C, bias, lda, ldb, ldc, strideA, strideB, strideC, M, N, K, relu ? 1 : 0}, batch, stream);
+}
+
+extern "C" int tgmx_sgemm_nt_ep(const float* A, int64_t lda, const float* B, int64_t ldb, float* C, int64_t ldc, int64_t M, int32_t N,
+                                int32_t K, const float* bias, int32_t act, const float* res, int64_t ldr, tgmx_stream_t stream) {
+  TGMX_REQUIRE(M >= 0 && N > 0 && K > 0 && act >= 0 && act <= 2, "sgemm_nt_ep: bad sizes M=%lld N=%d K=%d act=%d", (long long)M, N, K, act);
+  if (M == 0) return TGMX_OK;
+  TGMX_REQUIRE(A && B && C, "sgemm_nt_ep: null pointer");
+  TGMX_REQUIRE(lda >= K && ldb >= K && ldc >= N && (!res || ldr >= N), "sgemm_nt_ep: leading dimension smaller than the row length");
+  GemmArgs g{A, B, C, bias, lda, ldb, ldc, 0, 0, 0, M, N, K, act};
+  g.res = res;
+  g.ldr = ldr;
+  return sgemm_nt_run(g, 1, stream);
+}
+
+// the kernel choice of tgmx_sgemm_nt / tgmx_sgemm_nt_ep (arguments checked by the caller)
+static int sgemm_nt_run(const GemmArgs& g, int32_t batch, tgmx_stream_t stream) {
+  const float *A = g.A, *B = g.B;
+  const long long lda = g.lda, ldb = g.ldb, strideA = g.sA, strideB = g.sB, M = g.M;
+  const int N = g.N, K = g.K;
   auto vec_ok = [](const float* p, long long ld, long long stride) { return ((uintptr_t)p & 15) == 0 && ld % 4 == 0 && stride % 4 == 0; };
   const bool av = vec_ok(A, lda, strideA), bv = vec_ok(B, ldb, strideB);
   hipStream_t st = (hipStream_t)stream;
@@ -2465,7 +2491,7 @@ int tgmx_internal_sgemm_nt_pair(const GemmCall& c0, const GemmCall& c1, tgmx_str
   for (int q = 0; q < 2; ++q) {
     const GemmCall& c = *cs[q];
     TGMX_REQUIRE(c.A && c.B && c.C && c.N > 0 && c.lda >= c.K && c.ldb >= c.K && c.ldc >= c.N, "sgemm_nt_pair: bad problem %d", q);
-    p.g[q] = GemmArgs{c.A, c.B, c.C, c.bias, c.lda, c.ldb, c.ldc, c.sA, c.sB, c.sC, c.M, c.N, c.K, c.relu};
+    p.g[q] = GemmArgs{c.A, c.B, c.C, c.bias, c.lda, c.ldb, c.ldc, c.sA, c.sB, c.sC, c.M, c.N, c.K, c.relu ? 1 : 0};
     p.ny[q] = (unsigned)((c.N + 63) / 64);
     p.nz[q] = (unsigned)c.batch;
     p.lds[q] = 0;

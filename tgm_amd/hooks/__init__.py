@@ -5,6 +5,7 @@ from .hook_manager import HookManager
 from .negatives import RandomNegativeEdgeSamplerHook
 from .recency import RecencyNeighborHook
 from .uniform import NeighborSamplerHook
+from .time_gap import TimeGapNeighborHook
 from .registry import hook, list_hooks
 from . import neighbors  # noqa: E402,F401  (the reference's import path: tgm.hooks.neighbors.recency)
 
@@ -20,6 +21,7 @@ __all__ = [
     'SeedableHook',
     'StatefulHook',
     'StatelessHook',
+    'TimeGapNeighborHook',
     'hook',
     'list_hooks',
 ]

@@ -1,0 +1,132 @@
+"""``FeedForwardNet`` / ``MLPMixer`` (tgm/nn/modules/mlp_mixer.py; same constructors and parameter names: ``token_norm``,
+``token_feedforward.ffn.{0,3}``, ``channel_norm``, ``channel_feedforward.ffn.{0,3}``) on HIP kernels.
+
+Inference (no gradient needed, and no active dropout) runs natively: ``tgmx_mixer_token`` does the whole token-mixing block of a seed --
+LayerNorm over the K tokens, Linear K -> int(f_t K), exact-erf GELU, Linear -> K, residual -- and also writes the channel LayerNorm of
+its result; the channel FFN is two exact-fp32 MFMA GEMMs with a GELU and a residual epilogue (``tgmx_sgemm_nt_ep``).
+
+Training (gradients enabled, or train mode with dropout > 0) is NOT native: it composes the reference arithmetic from torch ops on the
+device under autograd, with the same parameters.  A native backward is future work.  CPU tensors raise ``NativeLibraryError``.
+"""
+from __future__ import annotations
+
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+from torch import Tensor
+
+from .. import _native
+from . import _ops
+
+
+def _needs_torch(module: nn.Module, x: Tensor, dropout: float) -> bool:
+    """The composed torch path: autograd has something to track, or dropout is active."""
+    if module.training and dropout > 0:
+        return True
+    return torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in module.parameters()))
+
+
+class FeedForwardNet(nn.Module):
+    r"""Two-layered MLP with GELU activation (Linear -> GELU -> Dropout -> Linear -> Dropout)."""
+
+    def __init__(self, input_dim: int, dim_expansion_factor: float, dropout: float = 0.0) -> None:
+        super().__init__()
+        self.input_dim, self.dim_expansion_factor, self.dropout = input_dim, dim_expansion_factor, dropout
+        hidden = int(dim_expansion_factor * input_dim)
+        self.ffn = nn.Sequential(nn.Linear(input_dim, hidden), nn.GELU(), nn.Dropout(dropout), nn.Linear(hidden, input_dim), nn.Dropout(dropout))
+
+    def forward(self, X: Tensor) -> Tensor:
+        _native.require_device(X, 'FeedForwardNet input')
+        if _needs_torch(self, X, self.dropout):
+            return self.ffn(X)  # training: torch ops under autograd (not native)
+        x = _ops._f32c(X, 'FeedForwardNet input')
+        lin0, lin1 = self.ffn[0], self.ffn[3]
+        M, C, H = x.numel() // self.input_dim, self.input_dim, lin0.out_features
+        h = torch.empty((M, H), dtype=torch.float32, device=x.device)
+        out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+        sgemm_ep(x.view(M, C), lin0.weight.detach(), h, lin0.bias.detach(), act=2)
+        sgemm_ep(h, lin1.weight.detach(), out.view(M, C), lin1.bias.detach())
+        return out
+
+
+def sgemm_ep(A: Tensor, B: Tensor, out: Tensor, bias=None, act: int = 0, res=None) -> Tensor:
+    """out[M, N] = act(A[M, K] @ B[N, K].T + bias) + res; act 0 none, 1 ReLU, 2 exact-erf GELU (row-major 2-D views)."""
+    lib = _native.load()
+    M, K, N = A.shape[0], A.shape[1], B.shape[0]
+    _native.check(
+        lib.tgmx_sgemm_nt_ep(A.data_ptr(), A.stride(0), B.data_ptr(), B.stride(0), out.data_ptr(), out.stride(0), M, N, K, _native.ptr(bias), act,
+                             _native.ptr(res), 0 if res is None else res.stride(0), _native.stream_ptr()),
+        'tgmx_sgemm_nt_ep',
+    )  # fmt: skip
+    return out
+
+
+def token_block(mixer: 'MLPMixer', x: Tensor, ldx: int, S: int, z1: Tensor, y: Tensor, ldo: int) -> None:
+    """``tgmx_mixer_token`` with ``mixer``'s token FFN and channel LayerNorm (x, z1, y: device pointers' owners, rows of ldx / ldo floats)."""
+    lib = _native.load()
+    tn, cn, tf = mixer.token_norm, mixer.channel_norm, mixer.token_feedforward.ffn
+    K, C = mixer.num_tokens, mixer.num_channels
+    _native.check(
+        lib.tgmx_mixer_token(x.data_ptr(), ldx, S, K, C, tn.weight.data_ptr(), tn.bias.data_ptr(), tf[0].weight.data_ptr(), tf[0].bias.data_ptr(),
+                             tf[0].out_features, tf[3].weight.data_ptr(), tf[3].bias.data_ptr(), cn.weight.data_ptr(), cn.bias.data_ptr(),
+                             float(tn.eps), z1.data_ptr(), y.data_ptr(), ldo, _native.stream_ptr()),
+        'tgmx_mixer_token',
+    )  # fmt: skip
+
+
+class MLPMixer(nn.Module):
+    r"""MLP-Mixer block (https://openreview.net/forum?id=ayPPc0SyLv1, Eq. 6): token mixing over the K tokens of each channel, then
+    channel mixing over the C channels of each token, each as ``x + FFN(LayerNorm(x))``.
+
+    Input / output: [B, K, C] = [batch, num_tokens, num_channels].  Inference is native (see the module docstring); with gradients
+    enabled, or in train mode with dropout > 0, the forward is the reference arithmetic composed from torch ops on the device (NOT native).
+    """
+
+    def __init__(self, num_tokens: int, num_channels: int, token_dim_expansion_factor: float = 0.5, channel_dim_expansion_factor: float = 4.0,
+                 dropout: float = 0.0) -> None:  # fmt: skip
+        super().__init__()
+        self.num_tokens, self.num_channels, self.dropout = num_tokens, num_channels, dropout
+        self.token_norm = nn.LayerNorm(num_tokens)
+        self.token_feedforward = FeedForwardNet(input_dim=num_tokens, dim_expansion_factor=token_dim_expansion_factor, dropout=dropout)
+        self.channel_norm = nn.LayerNorm(num_channels)
+        self.channel_feedforward = FeedForwardNet(input_dim=num_channels, dim_expansion_factor=channel_dim_expansion_factor, dropout=dropout)
+
+    def forward(self, node_x: Tensor) -> Tensor:
+        _native.require_device(node_x, 'MLPMixer input')
+        if node_x.dim() != 3 or node_x.shape[1] != self.num_tokens or node_x.shape[2] != self.num_channels:
+            raise ValueError(f'MLPMixer expects [B, {self.num_tokens}, {self.num_channels}], got {list(node_x.shape)}')
+        if _needs_torch(self, node_x, self.dropout):
+            return self._torch_forward(node_x)
+        return self._native_forward(node_x)
+
+    def _torch_forward(self, x: Tensor) -> Tensor:
+        """The reference arithmetic from torch ops (autograd-capable; not native)."""
+        h = F.layer_norm(x.permute(0, 2, 1), (self.num_tokens,), self.token_norm.weight, self.token_norm.bias, self.token_norm.eps)
+        z = x + self.token_feedforward.ffn(h).permute(0, 2, 1)
+        h = F.layer_norm(z, (self.num_channels,), self.channel_norm.weight, self.channel_norm.bias, self.channel_norm.eps)
+        return z + self.channel_feedforward.ffn(h)
+
+    def _check_native(self) -> None:
+        if self.token_norm.eps != self.channel_norm.eps:
+            raise NotImplementedError('tgm_amd MLPMixer: the native token block takes one LayerNorm eps for both norms')
+        if not (self.token_norm.elementwise_affine and self.channel_norm.elementwise_affine and self.token_norm.bias is not None
+                and self.channel_norm.bias is not None):
+            raise NotImplementedError('tgm_amd MLPMixer: the native token block needs affine LayerNorms with bias')  # fmt: skip
+        for p in self.parameters():
+            if p.dtype != torch.float32 or not p.is_contiguous():
+                raise NotImplementedError('tgm_amd MLPMixer: parameters must be contiguous float32')
+
+    def _native_forward(self, node_x: Tensor) -> Tensor:
+        self._check_native()
+        x = _ops._f32c(node_x, 'MLPMixer input')
+        B, K, C = x.shape
+        R = B * K
+        f32 = dict(dtype=torch.float32, device=x.device)
+        z1, y = torch.empty((R, C), **f32), torch.empty((R, C), **f32)
+        token_block(self, x, C, B, z1, y, C)
+        cf = self.channel_feedforward.ffn
+        h = torch.empty((R, cf[0].out_features), **f32)
+        sgemm_ep(y, cf[0].weight.detach(), h, cf[0].bias.detach(), act=2)
+        out = torch.empty((B, K, C), **f32)
+        sgemm_ep(h, cf[3].weight.detach(), out.view(R, C), cf[3].bias.detach(), res=z1)
+        return out
