@@ -168,11 +168,9 @@ int tgmx_ring_update(tgmx_adj_t* ring, int32_t* write_pos, float* ring_x, int32_
  * FIRST workgroups (blockIdx 0 .. riders - 1), and the library relies on the hardware dispatching the workgroups of a launch in
  * ascending blockIdx order: the first 16 workgroups of any launch fit the chip together (one per CU is enough), so they are
  * all dispatched before any lookup workgroup behind them can occupy a slot, whatever the grid size (tests/test_sampler_gpu.py
- * runs them in a launch 7 x larger than what the chip holds at once).  Nothing else waits across workgroups by default: the
- * opt-in tail commit (environment TGMX_TAIL=1: the LAST workgroups of a launch wait for every earlier one, counted at scratch
- * words 2.., then write the rings) relies on the same order -- the workgroups a tail waits for all precede it in dispatch order,
- * so they are running or finished by the time it is resident.  If either wait ever fails to complete -- a scratch head that was
- * not zero at first use, or a device that dispatched out of order -- it gives up after about a second of polling, sets
+ * runs them in a launch 7 x larger than what the chip holds at once).  Nothing else waits across workgroups: the workgroups
+ * that carry a deferred commit (tgmx_recency_step_t.defer) wait for nothing.  If the riders' barrier ever fails to complete -- a
+ * scratch head that was not zero at first use, or a device that dispatched out of order -- it gives up after about a second of polling, sets
  * TGMX_ST_SCRATCH in `status` and the call's update is skipped or incomplete (the rings of that batch are then unspecified;
  * the lookups' outputs are unaffected): a reported error, never a hang (test_dirty_scratch_head_is_reported_not_hung).
  * TGMX_NO_RIDE=1 runs the same update as launches of its own (no in-kernel wait at all).
@@ -259,6 +257,16 @@ typedef struct tgmx_recency_step {
    * -- a consumer that holds the resident store (tgmx_tgat_forward: tgmx_tgat_hop_t.nbr_eid) gathers them by id where it uses them,
    * which removes the copy's writes and the consumer's re-read of them (177 of the 244 MB of a wiki-shaped batch). */
   int32_t* out_eid[TGMX_MAX_HOPS];
+  /* Optional (NULL: off): DEFERRED COMMIT state of a ring (tgmx_defer_create).  With it, a call that takes the fused plan with the
+   * riding placement (hops 0 + 1 as one launch, m <= 1024 entries, n_hops == 2, guard_seed_errors == 0, defer_ok != 0) does not
+   * write its batch into the rings: the commit runs as extra workgroups of the NEXT such call's lookup launch, whose lookups read the
+   * rings as they will be after it (an overlay: per-node headers, per-slot records, the pending batch's rows of the edge store).
+   * Every other call first commits what is pending (tgmx_defer_flush).  Results are identical either way; a reader of the ring
+   * state (ring, write_pos, ring_x) must flush first. */
+  struct tgmx_defer* defer;
+  /* != 0: this call's batch is a slice of the resident edge store -- its edge_x rows (and eid0 >= 0 ids) stay valid and unchanged
+   * until the next call -- so its commit may be deferred */
+  int32_t defer_ok;
 } tgmx_recency_step_t;
 
 int tgmx_recency_step(const tgmx_recency_step_t* step, tgmx_stream_t stream);
@@ -266,6 +274,17 @@ int tgmx_recency_step(const tgmx_recency_step_t* step, tgmx_stream_t stream);
  * not served by the narrow-row kernel; static index: wide rows only).  Informational (bench.py
  * attributes the timed launch's bytes with it); results never depend on it. */
 int tgmx_recency_step_plan(const tgmx_recency_step_t* step);
+
+/* Deferred ring commit (tgmx_recency_step_t.defer): the state of one ring -- the pending batch's update arguments, the stamp
+ * counter, and device buffers for both batch parities (per-node headers, per-slot records and stamps, the plan scratch: about
+ * 40 bytes per ring slot, allocated on the device current at the first call that defers, freed by tgmx_defer_destroy) -- shared
+ * by every argument block that carries the pointer.  TGMX_DEFER_COMMIT=0 in the environment: never defer (A/B). */
+typedef struct tgmx_defer tgmx_defer_t;
+tgmx_defer_t* tgmx_defer_create(int32_t num_nodes, int32_t B);
+void tgmx_defer_destroy(tgmx_defer_t* d);
+int tgmx_defer_pending(const tgmx_defer_t* d);
+int64_t tgmx_defer_count(const tgmx_defer_t* d);       /* batches whose commit was deferred so far */         /* 1: a commit waits */
+int tgmx_defer_flush(tgmx_defer_t* d, tgmx_stream_t stream); /* enqueue the pending commit (one launch) on `stream` */
 
 /* ------------------------------------------------------------------------
  * The loader's per-batch call as ONE entry point: DGDataLoader.__call__ (tgm/data/loader.py:158-170: slice,

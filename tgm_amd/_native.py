@@ -179,6 +179,7 @@ class RecencyStep(ctypes.Structure):
         ('guard_seed_errors', c_int32), ('sorted_ts', c_int32),
         ('out_valid', c_void_p * MAX_HOPS), ('out_valid_prev', c_void_p * MAX_HOPS),
         ('neg_index0', c_int64), ('csr_cursor', c_void_p), ('csr_x_by_pos', c_int32), ('out_eid', c_void_p * MAX_HOPS),
+        ('defer', c_void_p), ('defer_ok', c_int32),
     ]  # fmt: skip
 
 
@@ -302,6 +303,11 @@ SIGNATURES['tgmx_lookup_accounting'] = (c_int32, [_P, c_int64, _P, _P, c_int64, 
 SIGNATURES['tgmx_uniform_lookup_csr'] = (c_int32, [_P, _P, _P, c_int32, _P, c_int64, c_int32, c_int64, c_int32, c_int32, ctypes.c_uint64, ctypes.c_uint64,
                                                    _P, _P, _P, _P, _P])
 SIGNATURES['tgmx_ring_update_scratch_bytes'] = (c_size_t, [c_int64, c_int32])
+SIGNATURES['tgmx_defer_create'] = (c_void_p, [c_int32, c_int32])
+SIGNATURES['tgmx_defer_destroy'] = (None, [_P])
+SIGNATURES['tgmx_defer_pending'] = (c_int32, [_P])
+SIGNATURES['tgmx_defer_count'] = (c_int64, [_P])
+SIGNATURES['tgmx_defer_flush'] = (c_int32, [_P, _P])
 SIGNATURES['tgmx_tgn_gru_gate_backward'] = (c_int32, [_P, _P, _P, _P, c_int32, c_int64, _P, _P, _P])
 SIGNATURES['tgmx_tgn_aggregate_backward'] = (c_int32, [c_int64, _P, _P, _P, _P, _P, _P, c_int32, c_int32, _P, _P, c_int32, c_int32, _P, _P, _P])
 SIGNATURES['tgmx_tconv_edge_attr_backward'] = (c_int32, [_P, _P, _P, _P, _P, _P, c_int32, c_int32, c_int64, _P, _P])

@@ -130,6 +130,7 @@ extern "C" int tgmx_pipeline_step(const tgmx_pipeline_t* p, int64_t edge_lo, int
     s.edge_x = (p->edge_x && s.D > 0) ? p->edge_x + edge_lo * (long long)s.D : nullptr;
     s.n = n_edges;
     s.eid0 = edge_lo;
+    s.defer_ok = 1;  // the batch is a slice of the resident store: its rows stay put until the next call (deferred commit)
   } else {
     s.n = 0;
   }

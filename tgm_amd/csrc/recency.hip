@@ -91,10 +91,19 @@ struct LookupArgs {
   // launch's second argument instead of looking anything up
   unsigned side_blocks;
   int side_stage;
-  // tail commit (tgmx_recency_step, placement decided by the rider): the LAST tail_blocks workgroups wait until every
-  // lookup workgroup and the rider have finished, then write the batch into the rings -- the update's write-back as the
-  // tail of the lookup launch instead of a launch of its own
-  unsigned tail_blocks;
+  // deferred commit (tgmx_defer_t, fused launch only): the commit_blocks workgroups behind the riders write the PREVIOUS batch
+  // into the rings (the launch's third argument).  Nothing waits for them: the lookups read the rings as they will be after
+  // that commit, through the overlay below
+  unsigned commit_blocks;
+  // the overlay (phdr == NULL: nothing pending).  phdr[n] = (stamp << 32) | write_pos after the pending commit, for every node the
+  // pending batch touched (stamp == pstamp); pslot[row] == pstamp: ring row `row` is written by that commit, with record prec[row]
+  // and the feature row pstore[prec[row].eid - peid0] of the pending batch (a lookup encodes it as source N * B + eid - peid0)
+  const unsigned long long* phdr;
+  const Rec* prec;
+  const int32_t* pslot;
+  const float* pstore;
+  unsigned pstamp;
+  int peid0;
   // fused hop 0 + hop 1 launch: hop 1's k and outputs (rows of hop 1 = S * k)
   int k1;
   int32_t* out_nid1;
@@ -212,6 +221,15 @@ struct UpdateArgs {
                      // the lookups of the same call): the reference validates before it changes anything (recency.py:173-237)
   long long n, m, eid0;
   int B, N, D, key_wrap32;
+  // deferred commit (tgmx_defer_t): the riding placement also publishes this batch's effect for the next launch's lookups --
+  // dhdr[n] = (dstamp << 32) | write_pos after the commit (every touched node), drec[row] / dslot[row] = dstamp: the record
+  // every written ring row will hold -- and the commit writes write_pos as dhdr says instead of adding to it.  phdr / pstamp:
+  // the batch before, whose commit runs in this very launch (its write_pos where stamped, write_pos otherwise).
+  unsigned long long* dhdr;
+  Rec* drec;
+  int32_t* dslot;
+  const unsigned long long* phdr;
+  unsigned dstamp, pstamp;
 };
 
 __device__ __forceinline__ long long update_key(int node, long long t, long long span, int wrap32) {
@@ -295,10 +313,36 @@ __device__ __forceinline__ bool update_blocked(const UpdateArgs& a) {
   return a.guard_mask != 0 && (__hip_atomic_load(a.status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & a.guard_mask) != 0;
 }
 
+constexpr int kFold = 1 << 30;
 __device__ __forceinline__ void commit_write_pos(int32_t* wp, int kept, int B) {
   const int old = atomicAdd(wp, kept);
-  constexpr int kFold = 1 << 30;
   if (old < kFold && old + kept >= kFold) atomicSub(wp, kFold / B * B);  // stay far from int32 overflow
+}
+// the same fold as one step on a known value (runs of one node fold in any order to the same sum)
+__device__ __forceinline__ int fold_add(int old, int kept, int B) {
+  return (old < kFold && old + kept >= kFold) ? old + kept - kFold / B * B : old + kept;
+}
+
+// write_pos of node n as the lookups of this launch see it: the pending commit's value where the node is stamped (that commit
+// runs in this launch; nobody here waits for it).  Both words are loaded side by side.
+__device__ __forceinline__ int logical_wp(const int32_t* write_pos, const unsigned long long* phdr, unsigned pstamp, int n) {
+  const int wp = write_pos[n];
+  const unsigned long long h = phdr ? phdr[n] : 0ull;
+  return (phdr && (unsigned)(h >> 32) == pstamp) ? (int)(unsigned)h : wp;
+}
+
+// the run-last entry of node n (kept entries, absolute write_pos w0 before the batch) folds its run into dhdr[n]; runs of one
+// node (the int32 key wrap splits them) meet in the CAS loop, so the word ends as write_pos would after every commit_write_pos
+__device__ __forceinline__ void publish_wp(const UpdateArgs& a, int n, int w0, int kept) {
+  unsigned long long* hp = &a.dhdr[n];
+  unsigned long long cur = __hip_atomic_load(hp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  for (;;) {
+    const int base = (unsigned)(cur >> 32) == a.dstamp ? (int)(unsigned)cur : w0;
+    const unsigned long long nv = ((unsigned long long)a.dstamp << 32) | (unsigned)fold_add(base, kept, a.B);
+    const unsigned long long prev = atomicCAS(hp, cur, nv);
+    if (prev == cur) break;
+    cur = prev;
+  }
 }
 
 // LDS of the placement (and, stand-alone, of the sort); the riders of the lookup launches carve theirs from a union
@@ -495,7 +539,14 @@ __device__ __forceinline__ void update_block_body(const UpdateArgs& a, PlaceLds<
       if (h_maxp[hs[r]] == p) {
         Rec rec;
         if constexpr (DEFER) {
-          // the commit kernel reads sorted_rec[p] itself
+          // the commit kernel reads sorted_rec[p] itself; a deferred commit also publishes the record for the next launch's lookups
+          if (a.drec) {
+            const long long* src = reinterpret_cast<const long long*>(&a.sorted_rec[p]);
+            long long* dst = reinterpret_cast<long long*>(&a.drec[tgt[r]]);
+            dst[0] = COH ? ld_agent(&src[0]) : src[0];
+            dst[1] = COH ? ld_agent(&src[1]) : src[1];
+            a.dslot[tgt[r]] = (int32_t)a.dstamp;
+          }
         } else if constexpr (PRESORTED) {
           rec = a.sorted_rec[p];
         } else {
@@ -515,6 +566,8 @@ __device__ __forceinline__ void update_block_body(const UpdateArgs& a, PlaceLds<
         kept = cnt[r] > a.B ? a.B : cnt[r];
         if constexpr (!DEFER) {
           if (!blocked) commit_write_pos(&a.write_pos[node[r]], kept, a.B);
+        } else {
+          if (a.dhdr) publish_wp(a, node[r], w[r], kept);  // (w: the absolute write_pos the riding merge read)
         }
       }
     }
@@ -755,7 +808,8 @@ __device__ __forceinline__ void update_merge_riding(const UpdateArgs& a, int c0,
 #pragma unroll
   for (int q = 0; q < NE; ++q) {
     valid[q] = act[q] && node[q] >= 0 && node[q] < a.N && nbr[q] >= 0 && nbr[q] < a.N;
-    w[q] = valid[q] ? a.write_pos[node[q]] : 0;  // write_pos only moves after the lookups
+    // write_pos only moves after the lookups -- or, with a deferred commit in this launch, as its header says
+    w[q] = valid[q] ? logical_wp(a.write_pos, a.phdr, a.pstamp, node[q]) : 0;
   }
 #pragma unroll
   for (int q = 0; q < NE; ++q) {
@@ -768,16 +822,20 @@ __device__ __forceinline__ void update_merge_riding(const UpdateArgs& a, int c0,
     rec.nbr = nbr[q];
     rec.eid = a.eid0 >= 0 ? (int)(a.eid0 + i[q]) : -1;
     rec.ts = t[q];
+    // target: the ABSOLUTE write_pos (the placement takes it modulo B; a deferred commit's header needs all of it)
     if constexpr (COH) {
       st_agent(&a.sorted_j[rank], pay[q]);
       st_agent(&a.sorted_node[rank], valid[q] ? node[q] : -1);
-      st_agent(&a.target[rank], w[q] % a.B);
+      st_agent(&a.target[rank], w[q]);
+      long long* rd = reinterpret_cast<long long*>(&a.sorted_rec[rank]);  // (the placing rider copies it for a deferred commit)
+      st_agent(&rd[0], *reinterpret_cast<const long long*>(&rec));
+      st_agent(&rd[1], rec.ts);
     } else {
       a.sorted_j[rank] = pay[q];
       a.sorted_node[rank] = valid[q] ? node[q] : -1;
-      a.target[rank] = w[q] % a.B;
+      a.target[rank] = w[q];
+      a.sorted_rec[rank] = rec;
     }
-    a.sorted_rec[rank] = rec;  // (read by the commit launch only)
   }
 }
 
@@ -829,122 +887,43 @@ __device__ __forceinline__ bool rider_barrier(int32_t* bar, int parts) {
 }
 constexpr int kRidePlaceMaxM = 1024;
 
-// ---- tail commit -----------------------------------------------------------------------------------------------------
-// bar[2] counts finished workgroups (lookups + rider), bar[3] finished tail workgroups; the last tail workgroup zeroes
-// both, so the words only have to be zero when the scratch is first used (like the riders' barrier).
-// Counting is two-level: 3000 same-address device-scope atomics serialise at the memory side (measured: the launch took
-// 117 instead of 39 us with one counter), so workgroup b adds to group counter b % kTailGroups (own 64-byte lines:
-// bar[16 + 16 g]) and only the workgroup that completes a group (it knows the group's size) moves the global word.
-constexpr int kTailGroups = 32;
-__device__ __forceinline__ void tail_signal(int32_t* bar, bool publish, unsigned bid, unsigned nblk) {
-  __syncthreads();  // every thread's loads have returned and its stores have been issued and counted
-  if (threadIdx.x == 0) {
-    if (publish) {
-      // the rider's placement decisions must be visible to tail workgroups on other XCDs (their L2s are not coherent
-      // with this one): one write-back of this L2, once per launch; lookup workgroups publish nothing (relaxed)
-      __threadfence();
-      __hip_atomic_store(&bar[4], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // decisions readable
-      __hip_atomic_fetch_add(&bar[2], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    } else {
-      const unsigned g = bid % kTailGroups;
-      const unsigned size = (nblk - g + kTailGroups - 1) / kTailGroups;  // workgroups b < nblk with b % kTailGroups == g
-      int32_t* cnt = &bar[16 + 16 * g];
-      const int prev = __hip_atomic_fetch_add(cnt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (prev == (int)size - 1) {
-        __hip_atomic_store(cnt, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // ready for the next launch
-        __hip_atomic_fetch_add(&bar[2], (int)size, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
+// ---- the commit: one wave per sorted position of a batch whose placement a rider decided ------------------------------
+// (the body of ring_update_feat_kernel<true>, and of the commit workgroups of a fused lookup launch that carry the PREVIOUS batch's
+// commit).  Deferred (dhdr set): write_pos is STORED as the batch's header says -- every run-last entry of a node stores the same
+// value, the one commit_write_pos would have left -- instead of added to.
+__device__ __forceinline__ void commit_position(const UpdateArgs& a, long long p) {
+  const int row = a.winner[p];
+  if (lane_id() == 0) {
+    const int kept = a.target[p];
+    if (row >= 0) a.ring[row] = a.sorted_rec[p];
+    if (kept > 0) {
+      const int n = a.sorted_node[p];
+      if (a.dhdr) a.write_pos[n] = (int)(unsigned)a.dhdr[n];
+      else commit_write_pos(&a.write_pos[n], kept, a.B);
     }
+  }
+  if (row < 0 || a.D == 0) return;
+  const long long j = a.sorted_j[p];
+  const long long i = j >= a.n ? j - a.n : j;
+  float* __restrict__ o = a.ring_x + (long long)row * a.D;
+  if (a.edge_x) {
+    const float* __restrict__ x = a.edge_x + i * a.D;
+    for (int c = lane_id(); c < a.D; c += kWave) o[c] = x[c];
+  } else {
+    for (int c = lane_id(); c < a.D; c += kWave) o[c] = 0.f;
   }
 }
 
-// Workgroup `tb` of `tail_blocks`, positions [4 tb, 4 tb + 4), one wave each (the body of ring_update_feat_kernel<COMMIT>).
-// Everything is READ before the launch-wide wait and only written after it: as soon as the rider has published its
-// placement decisions (bar[4], set behind its write-back) the wave fetches its position's decision, record and feature
-// row into registers; once every lookup workgroup has finished (bar[2] == need) what is left is stores.
-__device__ __forceinline__ bool tail_wait(const int32_t* word, unsigned need) {
-  int spins = 0;
-  while ((unsigned)__hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < need) {
-    __builtin_amdgcn_s_sleep(8);
-    if (++spins > (1 << 22)) return false;  // seconds: the count can only be short if the scratch head was not zero at first use
-  }
-  return true;
-}
-
-__device__ __forceinline__ void tail_commit(const UpdateArgs& a, unsigned tb, unsigned tail_blocks, unsigned need) {
-  __shared__ int ok_s;
-  const int lane = lane_id();
-  const long long p = (long long)tb * (blockDim.x >> 6) + (threadIdx.x >> 6);
-  if (threadIdx.x == 0) ok_s = tail_wait(&a.barrier[4], 1u) ? 1 : 0;
-  __syncthreads();
-  bool ok = ok_s != 0;
-  // ---- reads (the rider's scratch device-coherently: it was written through another XCD's L2) ----
-  int row = -1, kept = 0, node = 0;
-  long long rec_lo = 0, rec_hi = 0;
-  constexpr int kMaxCols = 8;  // feature columns per lane held in registers: D <= 512, wider rows are copied after the wait
-  float xv[kMaxCols];
-  const float* x = nullptr;
-  const bool wide = a.D > kMaxCols * kWave;
-  if (ok && p < a.m) {
-    row = ld_agent(&a.winner[p]);
-    kept = ld_agent(&a.target[p]);
-    if (row >= 0) {
-      const long long* src = reinterpret_cast<const long long*>(&a.sorted_rec[p]);
-      rec_lo = ld_agent(&src[0]);
-      rec_hi = ld_agent(&src[1]);
-    }
-    if (kept > 0) node = ld_agent(&a.sorted_node[p]);
-    if (row >= 0 && a.D > 0 && a.edge_x) {
-      const long long j = ld_agent(&a.sorted_j[p]);
-      x = a.edge_x + (j >= a.n ? j - a.n : j) * a.D;
-      if (!wide) {
-#pragma unroll
-        for (int u = 0; u < kMaxCols; ++u) {
-          const int c = lane + u * kWave;
-          xv[u] = c < a.D ? x[c] : 0.f;
-        }
-      }
-    }
-  }
-  // ---- every lookup workgroup and the rider done: nobody reads the rings any more ----
-  if (threadIdx.x == 0) ok_s = (ok && tail_wait(&a.barrier[2], need)) ? 1 : 0;
-  __syncthreads();
-  ok = ok_s != 0;
-  if (!ok) {
-    if (threadIdx.x == 0) atomicOr(a.status, TGMX_ST_SCRATCH);
-  } else if (p < a.m && !update_blocked(a)) {
-    if (lane == 0) {
-      if (row >= 0) {
-        long long* dst = reinterpret_cast<long long*>(&a.ring[row]);
-        dst[0] = rec_lo;
-        dst[1] = rec_hi;
-      }
-      if (kept > 0) commit_write_pos(&a.write_pos[node], kept, a.B);
-    }
-    if (row >= 0 && a.D > 0) {
-      float* __restrict__ o = a.ring_x + (long long)row * a.D;
-      if (!x) {
-        for (int c = lane; c < a.D; c += kWave) o[c] = 0.f;
-      } else if (wide) {
-        for (int c = lane; c < a.D; c += kWave) o[c] = x[c];
-      } else {
-#pragma unroll
-        for (int u = 0; u < kMaxCols; ++u) {
-          const int c = lane + u * kWave;
-          if (c < a.D) o[c] = xv[u];
-        }
-      }
-    }
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const int prev = __hip_atomic_fetch_add(&a.barrier[3], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (prev == (int)tail_blocks - 1) {  // last one out: leave the words zero for the next launch
-      __hip_atomic_store(&a.barrier[2], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(&a.barrier[3], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(&a.barrier[4], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
+// Commit workgroup `cb` of a fused lookup launch: positions [4 cb, 4 cb + 4) of the previous batch, one wave each.  It starts at
+// once -- no barrier, no flag: the launch's lookups and riders read what this writes only through the overlay (LookupArgs.phdr),
+// and the next launch reads it after the kernel boundary.  Why that is safe although they share cache lines: a lookup or rider
+// of this launch may read a ring row, a feature row or a write_pos word that sits on the same line as bytes written here, but it
+// never uses bytes this commit changes (pending slots come from prec / the edge store, stamped nodes' write_pos from phdr).  Its
+// L2's copy of such a line is clean, so it is never written back over the new bytes, and the boundary before the next launch
+// (L2 write-back here, invalidate there) makes the new bytes visible to it exactly as the separate commit launch did.
+__device__ __forceinline__ void commit_block(const UpdateArgs& c, unsigned cb) {
+  const long long p = (long long)cb * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  if (p < c.m) commit_position(c, p);
 }
 
 // PCAP: capacity of the riding placement (entries); 0 = this launch's riders only sort / merge.  The union is static LDS of EVERY
@@ -1124,7 +1103,7 @@ __device__ __forceinline__ Window find_window(const LookupArgs& a, int n, bool l
   if (live) {
     if (RING) {
       w.w0 = (long long)n * a.B;
-      w.wrot = a.write_pos[n] % a.B;  // unrolled position i lives in slot (wrot + i) % B
+      w.wrot = logical_wp(a.write_pos, a.phdr, a.pstamp, n) % a.B;  // unrolled position i lives in slot (wrot + i) % B
       w.wlen = a.B;
     } else {
       const long long ra = a.indptr[n], rz = a.indptr[n + 1];
@@ -1161,14 +1140,31 @@ __device__ __forceinline__ SmallPick small_pick(const LookupArgs& a, int n, long
   const Window w = find_window<RING>(a, n, live, lane);
   Rec r;
   r.nbr = -1; r.eid = 0; r.ts = 0;
+  int src = -1;  // RING: feature row of the record this lane holds (ring row, or N * B + store row of a pending slot)
   if (RING) {
-    // the row is read in slot order (no wait for write_pos) and rotated into time order by a shuffle
-    if (live && lane < B) r = a.recs[(long long)n * B + lane];
+    // the row is read in slot order (no wait for write_pos) and rotated into time order by a shuffle; with a commit pending in
+    // this launch, its records and slot stamps are read beside it (all three depend on n only) and pending slots take them
+    const long long row = (long long)n * B + lane;
+    Rec pr;
+    int ps = 0;
+    if (live && lane < B) {
+      r = a.recs[row];
+      if (a.phdr) {
+        pr = a.prec[row];
+        ps = a.pslot[row];
+      }
+    }
+    src = (int)row;
+    if (a.phdr && live && lane < B && (unsigned)ps == a.pstamp) {
+      r = pr;
+      src = a.pstore ? a.N * B + (r.eid - a.peid0) : -1;  // (no feature rows in the store: the commit writes zeros)
+    }
     int from_slot = w.wrot + lane;
     if (from_slot >= B) from_slot -= B;
     if (lane >= B) from_slot = lane;
     r.nbr = __shfl(r.nbr, from_slot);
     r.ts = __shfl(r.ts, from_slot);
+    src = __shfl(src, from_slot);
     if (a.out_eid || a.out_eid1) r.eid = __shfl(r.eid, from_slot);  // (only a caller that asked for edge ids reads it: wave-uniform)
   } else if (lane < w.wlen) {
     r = a.recs[slot_of<RING>(w, B, lane)];
@@ -1181,11 +1177,12 @@ __device__ __forceinline__ SmallPick small_pick(const LookupArgs& a, int n, long
   const int g_nbr = __shfl(r.nbr, from);
   const int g_eid = __shfl(r.eid, from);
   const long long g_ts = __shfl(r.ts, from);
+  const int g_src = RING ? __shfl(src, from) : 0;
   SmallPick o;
   o.has = i >= 0 && g_nbr >= 0;
   o.nbr = o.has ? g_nbr : -1;
   o.ts = o.has ? g_ts : 0;
-  o.src = o.has ? ((RING || a.x_by_pos) ? (int)slot_of<RING>(w, B, from) : g_eid) : -1;
+  o.src = o.has ? (RING ? g_src : (a.x_by_pos ? (int)slot_of<RING>(w, B, from) : g_eid)) : -1;
   o.eid = o.has ? g_eid : -1;
   return o;
 }
@@ -1198,11 +1195,14 @@ template <int VEC>
 __device__ __forceinline__ void gather_rows(const LookupArgs& a, long long s, int k, int lane, const int* lds_eid, float* out_x, int first_slot) {
   using V = typename VecOf<VEC>::type;
   const V* __restrict__ X = reinterpret_cast<const V*>(a.edge_x);
+  // sources >= N * B: rows of the edge store behind a pending commit's slots (LookupArgs.pstore; none without one)
+  const int lim = a.pstore ? a.N * a.B : 0x7fffffff;
+  const V* __restrict__ P = a.pstore ? reinterpret_cast<const V*>(a.pstore) : X;
   V* __restrict__ O = reinterpret_cast<V*>(out_x + s * (long long)k * a.D);
   const int total = k * a.row_vecs;
   constexpr int U = 8;
   for (int f0 = first_slot * a.row_vecs + lane; f0 < total; f0 += kWave * U) {
-    long long idx[U];
+    const V* ptr[U];
     bool has[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
@@ -1212,11 +1212,12 @@ __device__ __forceinline__ void gather_rows(const LookupArgs& a, long long s, in
       const int col = fc - slot * a.row_vecs;
       const int e = lds_eid[slot];
       has[u] = e >= 0;
-      idx[u] = has[u] ? (long long)e * a.row_vecs + col : 0;
+      const bool st = e >= lim;
+      ptr[u] = (st ? P : X) + (has[u] ? (long long)(st ? e - lim : e) * a.row_vecs + col : 0);
     }
     V v[U];
 #pragma unroll
-    for (int u = 0; u < U; ++u) v[u] = X[idx[u]];
+    for (int u = 0; u < U; ++u) v[u] = *ptr[u];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const int f = f0 + u * kWave;
@@ -1299,15 +1300,10 @@ __global__ __launch_bounds__(256) void recency_lookup_kernel(const LookupArgs a,
   if constexpr (RING && RIDE) {
     if (bid < a.side_blocks) {
       update_side_work(u, a.side_stage, (int)bid);
-      if (a.tail_blocks) tail_signal(u.barrier, true, 0, 0);
       return;
     }
     bid -= a.side_blocks;
-    nblk -= a.side_blocks + a.tail_blocks;
-    if (bid >= nblk) {  // the launch's last workgroups: the update's write-back, once everyone else is done
-      tail_commit(u, bid - nblk, a.tail_blocks, nblk + a.side_blocks);
-      return;
-    }
+    nblk -= a.side_blocks;
   }
   const int lane = lane_id();
   const int wave_in_block = threadIdx.x >> 6;
@@ -1320,9 +1316,6 @@ __global__ __launch_bounds__(256) void recency_lookup_kernel(const LookupArgs a,
     check_seed(a, n, q, a.allow_pad, lane);
     lookup_seed<RING, VEC, SMALL>(a, s, n, q, a.k, lane, lds_eid, a.out_nid, a.out_ts, a.out_x, a.out_valid, a.out_valid_prev, a.out_eid);
   }
-  if constexpr (RING && RIDE) {
-    if (a.tail_blocks) tail_signal(u.barrier, false, bid, nblk);
-  }
 }
 
 // Hop 0 and hop 1 in ONE launch (B, k0, k1 <= 64).  Hop 1's seeds are hop 0's outputs, but the rings do not move
@@ -1332,21 +1325,24 @@ __global__ __launch_bounds__(256) void recency_lookup_kernel(const LookupArgs a,
 // by bandwidth -- run inside the big hop-1 launch instead of in front of it.  Waves [0, S0) are hop 0 (they also
 // publish the concatenated seeds), waves [S0, S0 + S0 k0) are hop 1; results are identical to the two launches.
 template <bool RING, int VEC, int PCAP = kRidePlaceMaxM>
-__global__ __launch_bounds__(256) void recency_lookup_fused01_kernel(const LookupArgs a, const UpdateArgs u) {
+//
+// Deferred commit (a.commit_blocks > 0): the workgroups behind the riders commit the PREVIOUS batch (c) while everything else runs;
+// the lookups see it through the overlay (small_pick, gather_rows), the riders through logical_wp.
+__global__ __launch_bounds__(256) void recency_lookup_fused01_kernel(const LookupArgs a, const UpdateArgs u, const UpdateArgs c) {
   extern __shared__ __attribute__((aligned(16))) int lds_eid_all[];
   unsigned bid = blockIdx.x, nblk = gridDim.x;
   if constexpr (RING) {
     if (bid < a.side_blocks) {
       update_side_work<PCAP>(u, a.side_stage, (int)bid);
-      if (a.tail_blocks) tail_signal(u.barrier, true, 0, 0);
       return;
     }
     bid -= a.side_blocks;
-    nblk -= a.side_blocks + a.tail_blocks;
-    if (bid >= nblk) {  // the launch's last workgroups: the update's write-back, once everyone else is done
-      tail_commit(u, bid - nblk, a.tail_blocks, nblk + a.side_blocks);
+    if (bid < a.commit_blocks) {
+      commit_block(c, bid);
       return;
     }
+    bid -= a.commit_blocks;
+    nblk -= a.side_blocks + a.commit_blocks;
   }
   const int lane = lane_id();
   const int wave_in_block = threadIdx.x >> 6;
@@ -1373,9 +1369,6 @@ __global__ __launch_bounds__(256) void recency_lookup_fused01_kernel(const Looku
       q = __shfl(o.ts, j);
       lookup_seed<RING, VEC, true>(a, idx, n, q, k1, lane, lds_eid, a.out_nid1, a.out_ts1, a.out_x1, a.out_valid1, a.out_valid_prev1, a.out_eid1);
     }
-  }
-  if constexpr (RING) {
-    if (a.tail_blocks) tail_signal(u.barrier, false, bid, nblk);
   }
 }
 
@@ -1506,15 +1499,10 @@ __global__ __launch_bounds__(256) void lookup_packed_kernel(const LookupArgs a, 
   if constexpr (RING && RIDE) {
     if (bid < a.side_blocks) {
       update_side_work(u, a.side_stage, (int)bid);
-      if (a.tail_blocks) tail_signal(u.barrier, true, 0, 0);
       return;
     }
     bid -= a.side_blocks;
-    nblk -= a.side_blocks + a.tail_blocks;
-    if (bid >= nblk) {  // the launch's last workgroups: the update's write-back, once everyone else is done
-      tail_commit(u, bid - nblk, a.tail_blocks, nblk + a.side_blocks);
-      return;
-    }
+    nblk -= a.side_blocks;
   }
   const int lane = lane_id();
   const int sub = lane / GL, gl = lane - sub * GL;
@@ -1544,9 +1532,6 @@ __global__ __launch_bounds__(256) void lookup_packed_kernel(const LookupArgs a, 
     }
     const GroupPick o = group_pick<RING, GL>(a, n, q, k, n >= 0 && n < a.N, gl, sub);
     group_emit<VEC, GL>(a, act, s, k, o, lds_eid, gl, sub, a.out_nid, a.out_ts, a.out_x, a.out_valid, a.out_valid_prev);
-  }
-  if constexpr (RING && RIDE) {
-    if (a.tail_blocks) tail_signal(u.barrier, false, bid, nblk);
   }
 }
 
@@ -1719,15 +1704,10 @@ __global__ __launch_bounds__(256) void lookup_tile_kernel(const LookupArgs a, co
   if constexpr (RING && RIDE) {
     if (bid < a.side_blocks) {
       update_side_work(u, a.side_stage, (int)bid);
-      if (a.tail_blocks) tail_signal(u.barrier, true, 0, 0);
       return;
     }
     bid -= a.side_blocks;
-    nblk -= a.side_blocks + a.tail_blocks;
-    if (bid >= nblk) {
-      tail_commit(u, bid - nblk, a.tail_blocks, nblk + a.side_blocks);
-      return;
-    }
+    nblk -= a.side_blocks;
   }
   const int lane = lane_id();
   const int wave_in_block = threadIdx.x >> 6, wpb = blockDim.x >> 6;
@@ -1887,9 +1867,6 @@ __global__ __launch_bounds__(256) void lookup_tile_kernel(const LookupArgs a, co
     }
     __builtin_amdgcn_wave_barrier();  // the next tile reuses the staging area
   }
-  if constexpr (RING && RIDE) {
-    if (a.tail_blocks) tail_signal(u.barrier, false, bid, nblk);
-  }
 }
 
 // ---- the tile kernel with a COOPERATIVE index phase (round 6) -------------------------------------------------------------------
@@ -1920,15 +1897,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, (RING &&
   if constexpr (RING && RIDE) {
     if (bid < a.side_blocks) {
       update_side_work(u, a.side_stage, (int)bid);
-      if (a.tail_blocks) tail_signal(u.barrier, true, 0, 0);
       return;
     }
     bid -= a.side_blocks;
-    nblk -= a.side_blocks + a.tail_blocks;
-    if (bid >= nblk) {
-      tail_commit(u, bid - nblk, a.tail_blocks, nblk + a.side_blocks);
-      return;
-    }
+    nblk -= a.side_blocks;
   }
   const int lane = lane_id();
   const int wave_in_block = threadIdx.x >> 6, wpb = blockDim.x >> 6;
@@ -2127,9 +2099,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, (RING &&
     }
     __builtin_amdgcn_wave_barrier();  // the next tile reuses the staging area and the header
   }
-  if constexpr (RING && RIDE) {
-    if (a.tail_blocks) tail_signal(u.barrier, false, bid, nblk);
-  }
 }
 
 // > 64 KB of LDS per workgroup (static + dynamic) is a per-DEVICE opt-in of the kernel function
@@ -2195,19 +2164,18 @@ static int packed_group_lanes(const LookupArgs& a, int k, bool ring) {
 
 template <bool RING>
 static int launch_lookup(LookupArgs a, hipStream_t stream, hipEvent_t ev_start, hipEvent_t ev_stop,
-                         const UpdateArgs* side = nullptr, int side_stage = 0, unsigned side_blocks = 0, unsigned tail_blocks = 0) {
+                         const UpdateArgs* side = nullptr, int side_stage = 0, unsigned side_blocks = 0) {
   if (a.S == 0) return TGMX_OK;
   const UpdateArgs u = side ? *side : UpdateArgs{};
   a.side_blocks = (RING && side) ? side_blocks : 0;
   a.side_stage = side_stage;
-  a.tail_blocks = a.side_blocks ? tail_blocks : 0;
   const bool small = a.B <= kWave && a.k <= kWave;
   const int vec = prepare_lookup(a, a.out_x, a.k);
   if (vec < 0) return vec;
   const int waves_per_block = 4;
   long long blocks = (a.S + waves_per_block - 1) / waves_per_block;
   if (blocks > (1 << 20)) blocks = 1 << 20;
-  const dim3 grid((unsigned)blocks + a.side_blocks + a.tail_blocks), block(waves_per_block * kWave);
+  const dim3 grid((unsigned)blocks + a.side_blocks), block(waves_per_block * kWave);
   const size_t lds = (size_t)waves_per_block * a.k * sizeof(int);
   const bool ride = RING && a.side_blocks > 0;
 #define TGMX_LAUNCH(VEC_, SMALL_)                                                                                              \
@@ -2240,7 +2208,7 @@ static int launch_lookup(LookupArgs a, hipStream_t stream, hipEvent_t ev_start, 
       const long long room = (long long)device_cu_count() * 12;
       if (tblocks > room) tblocks = room;
     }
-    const dim3 tgrid((unsigned)tblocks + a.side_blocks + a.tail_blocks), tblock(wpb * kWave);
+    const dim3 tgrid((unsigned)tblocks + a.side_blocks), tblock(wpb * kWave);
     const int bcap = a.B <= 10 ? 10 : (a.B <= 20 ? 20 : 32);
     // the cooperative index phase (windows read as contiguous runs by neighbouring lanes, lookup_tile_coop_kernel): B <= 20, the low 32 bits
     // of a window's base must address it (rings: checked above; static index: fewer than 2^31 records)
@@ -2282,7 +2250,7 @@ static int launch_lookup(LookupArgs a, hipStream_t stream, hipEvent_t ev_start, 
     const int per_wave = 64 / gl;
     long long pblocks = ((a.S + per_wave - 1) / per_wave + waves_per_block - 1) / waves_per_block;
     if (pblocks > (1 << 20)) pblocks = 1 << 20;
-    const dim3 pgrid((unsigned)pblocks + a.side_blocks + a.tail_blocks);
+    const dim3 pgrid((unsigned)pblocks + a.side_blocks);
     const size_t plds = (size_t)waves_per_block * per_wave * a.k * sizeof(int);
 #define TGMX_PACKED(VEC_)                                                                              \
   do {                                                                                                 \
@@ -2311,13 +2279,15 @@ static int launch_lookup(LookupArgs a, hipStream_t stream, hipEvent_t ev_start, 
 
 
 // hop 0 (a: seeds / groups, k, outputs) and hop 1 (k1, out_*1) as one launch; the caller checked can_fuse01
+// commit (RING, optional): the previous batch's deferred commit, run by ceil(m / 4) workgroups behind the riders
 template <bool RING>
 static int launch_fused01(LookupArgs a, hipStream_t stream, hipEvent_t ev_start, hipEvent_t ev_stop, const UpdateArgs* side,
-                          int side_stage, unsigned side_blocks, unsigned tail_blocks = 0) {
+                          int side_stage, unsigned side_blocks, const UpdateArgs* commit = nullptr) {
   const UpdateArgs u = side ? *side : UpdateArgs{};
+  const UpdateArgs c = (RING && commit) ? *commit : UpdateArgs{};
   a.side_blocks = (RING && side) ? side_blocks : 0;
   a.side_stage = side_stage;
-  a.tail_blocks = a.side_blocks ? tail_blocks : 0;
+  a.commit_blocks = (RING && commit) ? (unsigned)((c.m + 3) / 4) : 0u;
   const int kmax = a.k > a.k1 ? a.k : a.k1;
   const int vec = prepare_lookup(a, a.out_x1, kmax);
   if (vec < 0) return vec;
@@ -2325,15 +2295,15 @@ static int launch_fused01(LookupArgs a, hipStream_t stream, hipEvent_t ev_start,
   const long long waves = a.S + a.S * a.k;
   long long blocks = (waves + waves_per_block - 1) / waves_per_block;
   if (blocks > (1 << 20)) blocks = 1 << 20;
-  const dim3 grid((unsigned)blocks + a.side_blocks + a.tail_blocks), block(waves_per_block * kWave);
+  const dim3 grid((unsigned)blocks + a.side_blocks + a.commit_blocks), block(waves_per_block * kWave);
   const size_t lds = (size_t)waves_per_block * kmax * sizeof(int);
   // the riders' static LDS sized for what rides (RiderLds): placement of <= 512 entries, of <= 1024, or sort / merge only
   const int pcap = !(RING && side) ? 1024 : ((side_stage != kSideAll && side_stage != kSideSortMergePlace) ? 0 : (u.m <= 512 ? 512 : 1024));
-  if (vec == 4 && pcap == 512) TGMX_LAUNCH_TIMED((recency_lookup_fused01_kernel<RING, 4, RING ? 512 : 1024>), grid, block, lds, stream, ev_start, ev_stop, a, u);
-  else if (vec == 4 && pcap == 0) TGMX_LAUNCH_TIMED((recency_lookup_fused01_kernel<RING, 4, RING ? 0 : 1024>), grid, block, lds, stream, ev_start, ev_stop, a, u);
-  else if (vec == 4) TGMX_LAUNCH_TIMED((recency_lookup_fused01_kernel<RING, 4>), grid, block, lds, stream, ev_start, ev_stop, a, u);
-  else if (vec == 2) TGMX_LAUNCH_TIMED((recency_lookup_fused01_kernel<RING, 2>), grid, block, lds, stream, ev_start, ev_stop, a, u);
-  else TGMX_LAUNCH_TIMED((recency_lookup_fused01_kernel<RING, 1>), grid, block, lds, stream, ev_start, ev_stop, a, u);
+  if (vec == 4 && pcap == 512) TGMX_LAUNCH_TIMED((recency_lookup_fused01_kernel<RING, 4, RING ? 512 : 1024>), grid, block, lds, stream, ev_start, ev_stop, a, u, c);
+  else if (vec == 4 && pcap == 0) TGMX_LAUNCH_TIMED((recency_lookup_fused01_kernel<RING, 4, RING ? 0 : 1024>), grid, block, lds, stream, ev_start, ev_stop, a, u, c);
+  else if (vec == 4) TGMX_LAUNCH_TIMED((recency_lookup_fused01_kernel<RING, 4>), grid, block, lds, stream, ev_start, ev_stop, a, u, c);
+  else if (vec == 2) TGMX_LAUNCH_TIMED((recency_lookup_fused01_kernel<RING, 2>), grid, block, lds, stream, ev_start, ev_stop, a, u, c);
+  else TGMX_LAUNCH_TIMED((recency_lookup_fused01_kernel<RING, 1>), grid, block, lds, stream, ev_start, ev_stop, a, u, c);
   TGMX_CHECK_LAUNCH("recency_lookup_fused01");
   return TGMX_OK;
 }
@@ -2611,15 +2581,11 @@ template <bool COMMIT>
 __global__ __launch_bounds__(256) void ring_update_feat_kernel(const UpdateArgs a) {
   const long long p = (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   if (p >= a.m) return;
-  if (COMMIT && update_blocked(a)) return;
-  const int row = a.winner[p];
   if constexpr (COMMIT) {
-    if (lane_id() == 0) {
-      const int kept = a.target[p];
-      if (row >= 0) a.ring[row] = a.sorted_rec[p];
-      if (kept > 0) commit_write_pos(&a.write_pos[a.sorted_node[p]], kept, a.B);
-    }
+    if (!update_blocked(a)) commit_position(a, p);
+    return;
   }
+  const int row = a.winner[p];
   if (row < 0 || a.D == 0) return;
   const long long j = a.sorted_j[p];
   const long long i = j >= a.n ? j - a.n : j;
@@ -2884,7 +2850,7 @@ extern "C" int tgmx_ring_lookup(const tgmx_adj_t* ring, const int32_t* write_pos
   return launch_lookup<true>(a, (hipStream_t)stream, (hipEvent_t)ev_start, (hipEvent_t)ev_stop);
 }
 
-constexpr int kScratchHead = 1024;  // ints (4 KiB, zero at first use: barrier words + the tail commit's grouped counters; the layouts behind it stay 256-byte aligned)
+constexpr int kScratchHead = 1024;  // ints (4 KiB, zero at first use: the riders' barrier words; the layouts behind it stay 256-byte aligned)
 
 static int fill_update_args(UpdateArgs& a, tgmx_adj_t* ring, int32_t* write_pos, float* ring_x, int32_t D, int32_t B,
                             int32_t num_nodes, const int32_t* src, const int32_t* dst, const int64_t* ts,
@@ -3092,10 +3058,83 @@ static SideStream* side_stream_for_current_device() {
   return &s;
 }
 
+// ---- deferred commit (tgmx_defer_t) -------------------------------------------------------------------------------------
+struct tgmx_defer {
+  int N, B;
+  void* mem;  // device buffers (both parities), allocated by the first call that defers
+  unsigned long long* hdr[2];
+  Rec* rec[2];
+  int32_t* slot[2];
+  int32_t* scratch[2];  // the plan scratch of each parity: the next batch's riders write one while the pending commit reads the other
+  unsigned stamp;       // stamp of the last batch placed with a deferred commit (0: none yet)
+  bool pending;         // its commit has not run
+  long long deferred;   // batches whose commit was deferred so far (tgmx_defer_count)
+  UpdateArgs pend;      // its update arguments (its scratch, its parity's headers)
+};
+
+extern "C" tgmx_defer_t* tgmx_defer_create(int32_t num_nodes, int32_t B) {
+  if (num_nodes <= 0 || B <= 0) {
+    set_error("defer_create: bad arguments");
+    return nullptr;
+  }
+  auto* d = new tgmx_defer{};
+  d->N = num_nodes;
+  d->B = B;
+  return d;
+}
+
+extern "C" void tgmx_defer_destroy(tgmx_defer_t* d) {
+  if (d && d->mem) (void)hipFree(d->mem);
+  delete d;
+}
+
+// [hdr 2N uint64 | scratch 2 x half | slot 2NB int32 | rec 2NB records]: everything but the records zeroed (stamps start at 1,
+// the riders' barrier words at the head of each scratch half must be zero at first use; a record is read only where stamped)
+static int defer_buffers(tgmx_defer* d, hipStream_t st) {
+  if (d->mem) return TGMX_OK;
+  auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  const size_t nb = (size_t)d->N * d->B;
+  const size_t half = up(tgmx_ring_update_scratch_bytes(kRidePlaceMaxM, 1));  // (m <= 1024 entries)
+  const size_t o_scr = up((size_t)16 * d->N), o_slot = o_scr + 2 * half, o_rec = up(o_slot + 8 * nb), total = o_rec + 32 * nb;
+  void* mem = nullptr;
+  if (hipMalloc(&mem, total) != hipSuccess) {
+    set_error("recency_step: cannot allocate %zu bytes for the deferred commit", total);
+    return TGMX_E_LAUNCH;
+  }
+  (void)hipMemsetAsync(mem, 0, o_rec, st);
+  char* base = static_cast<char*>(mem);
+  d->mem = mem;
+  for (int q = 0; q < 2; ++q) {
+    d->hdr[q] = reinterpret_cast<unsigned long long*>(base) + (size_t)q * d->N;
+    d->scratch[q] = reinterpret_cast<int32_t*>(base + o_scr + q * half);
+    d->slot[q] = reinterpret_cast<int32_t*>(base + o_slot) + q * nb;
+    d->rec[q] = reinterpret_cast<Rec*>(base + o_rec) + q * nb;
+  }
+  return TGMX_OK;
+}
+
+extern "C" int tgmx_defer_pending(const tgmx_defer_t* d) { return d && d->pending ? 1 : 0; }
+
+extern "C" int64_t tgmx_defer_count(const tgmx_defer_t* d) { return d ? d->deferred : 0; }
+
+extern "C" int tgmx_defer_flush(tgmx_defer_t* d, tgmx_stream_t stream) {
+  TGMX_REQUIRE(d, "defer_flush: null state");
+  if (!d->pending) return TGMX_OK;
+  d->pending = false;
+  hipLaunchKernelGGL(ring_update_feat_kernel<true>, dim3((unsigned)((d->pend.m + 3) / 4)), dim3(256), 0, (hipStream_t)stream, d->pend);
+  TGMX_CHECK_LAUNCH("defer_flush");
+  return TGMX_OK;
+}
+
+static bool getenv_no_ride() {
+  static const bool no_ride = getenv("TGMX_NO_RIDE") != nullptr;  // A/B knob: the update as its own launches
+  return no_ride;
+}
+
 // Can hop 0 and hop 1 of this step be one launch?  (B <= 64; hop 1 not better served by the packed narrow-row kernel.)
+
 static bool plan_fuse01(const tgmx_recency_step_t* s, long long S0) {
   static const bool no_fuse = getenv("TGMX_NO_FUSE") != nullptr;  // A/B knob
-  static const bool no_ride = getenv("TGMX_NO_RIDE") != nullptr;
   if (no_fuse || s->n_hops < 2 || S0 <= 0 || s->B > kWave || s->k[0] <= 0 || s->k[1] <= 0) return false;
   // static index: a hop-1 wave would repeat hop 0's two prefix searches (dependent reads); that only pays when its own
   // gather is long (comment-shaped, D = 16: 26.9 -> 19.2 G sampled-edges/s fused; wiki-shaped, D = 172: 4.8 -> 5.1)
@@ -3110,9 +3149,6 @@ static bool plan_fuse01(const tgmx_recency_step_t* s, long long S0) {
     if (prepare_lookup(a, s->out_x[1], s->k[1]) < 0) return false;
     if (packed_group_lanes(a, s->k[1], true) < 64) return false;  // (review-shaped, forced through the fused launch: 38.7 vs 28.9 us/step)
   }
-  const long long m = s->directed ? s->n : 2 * s->n;
-  (void)no_ride;
-  (void)m;
   return true;
 }
 
@@ -3162,21 +3198,40 @@ extern "C" int tgmx_recency_step(const tgmx_recency_step_t* s, tgmx_stream_t str
     grp.out_nid = s->seed_nid0; grp.out_ts = s->seed_ts0; grp.groups = s->n_groups;
   }
 
+  // ---- deferred commit: does this call defer its own (and run the pending one inside its lookup launch)?  Else whatever is
+  // pending is committed first, and the call runs as without deferral
+  tgmx_defer* dfr = csr ? nullptr : s->defer;
+  static const bool defer_on = !(getenv("TGMX_DEFER_COMMIT") && atoi(getenv("TGMX_DEFER_COMMIT")) == 0);  // A/B knob
+  const long long m_all = s->directed ? s->n : 2 * s->n;
+  const bool defer = dfr && defer_on && s->defer_ok && s->n > 0 && m_all <= kRidePlaceMaxM && s->n_hops == 2 && S > 0 && !s->guard_seed_errors &&
+                     s->eid0 >= 0 && dfr->N == s->num_nodes && dfr->B == s->B &&
+                     (long long)s->B * s->num_nodes + s->n < 2147483647LL && plan_fuse01(s, S) && !getenv_no_ride();
+  if (dfr && dfr->pending && !defer)
+    if (const int rf = tgmx_defer_flush(dfr, stream)) return rf;
+  if (defer)
+    if (const int rb = defer_buffers(dfr, st)) return rb;
+
   // ---- ring update, front half: batches of up to kBlockMaxM entries are sorted by workgroups riding along with the
   // lookup launches (chunk sort with hop 0, merge with hop 1); only the placement runs after the lookups
   UpdateArgs u{};
   unsigned side_chunks = 0;
   bool ride_place = false;  // m <= 1024: hop 1 carries the merge AND the placement decisions
+  const unsigned stamp = defer ? dfr->stamp + 1 : 0u;  // (the stamp of this batch: 1, 2, ...; never 0)
+  int32_t* scratch = defer ? dfr->scratch[stamp & 1] : s->scratch;
   if (s->n > 0) {
     const int rc = fill_update_args(u, s->ring, s->write_pos, s->ring_x, s->D, s->B, s->num_nodes, s->src, s->dst, s->ts,
-                                    s->edge_x, s->n, s->eid0, s->directed, s->key_wrap32, s->scratch, s->status);
+                                    s->edge_x, s->n, s->eid0, s->directed, s->key_wrap32, scratch, s->status);
     if (rc) return rc;
     u.ts_bound = s->ts_bound;
     u.guard_mask = s->guard_seed_errors ? (TGMX_ST_SEED_RANGE | TGMX_ST_SEED_TIME) : 0;
     u.sorted_ts = s->sorted_ts;
-    static const bool no_ride = getenv("TGMX_NO_RIDE") != nullptr;  // A/B knob: the update as its own launches
-    if (u.m <= kBlockMaxM && s->n_hops > 0 && S > 0 && !no_ride) side_chunks = set_chunk_scratch(u, s->scratch + kScratchHead);
+    if (u.m <= kBlockMaxM && s->n_hops > 0 && S > 0 && !getenv_no_ride()) side_chunks = set_chunk_scratch(u, scratch + kScratchHead);
     ride_place = side_chunks > 0 && u.m <= kRidePlaceMaxM && s->n_hops >= 2;
+  }
+  if (defer) {
+    const int q = (int)(stamp & 1);
+    u.dhdr = dfr->hdr[q]; u.drec = dfr->rec[q]; u.dslot = dfr->slot[q]; u.dstamp = stamp;
+    if (dfr->pending) { u.phdr = dfr->hdr[q ^ 1]; u.pstamp = dfr->stamp; }
   }
   // 1024 < m <= 4096 (the replicated update of a 4- / 8-rank global wiki batch): the front half -- sort, merge, placement
   // decisions -- CAN run on the side stream next to the lookups instead of riders + a placement launch behind them.
@@ -3191,13 +3246,6 @@ extern "C" int tgmx_recency_step(const tgmx_recency_step_t* s, tgmx_stream_t str
     (void)hipEventRecord(mid->join, mid->stream);
     side_chunks = 0;  // no riders in the lookup launches
   }
-  // m <= 1024 and the placement rides: the write-back (records, write_pos, feature rows) CAN run as the tail of the last
-  // lookup launch -- its last ceil(m / 4) workgroups prefetch their decisions, wait for the others, then store -- instead
-  // of a launch of its own.  Measured on MI355X (wiki shape): lookup 37.9 + commit 5.3 us as two launches, 44.9 us as one
-  // (the launch-wide wait costs more than the launch boundary it replaces), so it is OFF unless TGMX_TAIL=1 (A/B knob;
-  // results identical, covered by the same tests).
-  static const bool use_tail = getenv("TGMX_TAIL") != nullptr;
-  const unsigned tail_blocks = (ride_place && use_tail && s->n_hops == 2) ? (unsigned)((u.m + 3) / 4) : 0u;
   SideStream* side = nullptr;  // set: the large update's front half runs on the side stream next to the lookups
   bool side_pending = false;   // its launches are enqueued BEHIND the first lookup launch (below)
   if (s->n > 0 && u.m > kBlockMaxM && s->n_hops > 0 && S > 0 && (side = side_stream_for_current_device()) != nullptr) {
@@ -3245,11 +3293,17 @@ extern "C" int tgmx_recency_step(const tgmx_recency_step_t* s, tgmx_stream_t str
     // riders: m <= 512 -> one workgroup does it all and only the commit follows; 512 < m <= 1024 -> a rider per chunk, the last one
     // out places (TGMX_THREE_PHASE=0: one workgroup, A/B); else sort | barrier | merge and the placement is its own launch
     static const bool three_phase_on = !(getenv("TGMX_THREE_PHASE") && atoi(getenv("TGMX_THREE_PHASE")) == 0);
-    const bool three_phase = three_phase_on && ride_place && u.m > 512 && !tail_blocks;
+    const bool three_phase = three_phase_on && ride_place && u.m > 512;
+    const bool commit = defer && dfr->pending;  // the previous batch's commit rides this launch
+    if (commit) {
+      a.phdr = u.phdr; a.pstamp = u.pstamp;
+      a.prec = dfr->rec[(stamp & 1) ^ 1]; a.pslot = dfr->slot[(stamp & 1) ^ 1];
+      a.pstore = s->D > 0 ? dfr->pend.edge_x : nullptr; a.peid0 = (int)dfr->pend.eid0;
+    }
     const int rc = csr ? launch_fused01<false>(a, st, e0, e1, nullptr, 0, 0)
                        : launch_fused01<true>(a, st, e0, e1, side_chunks > 0 ? &u : nullptr,
                                               ride_place ? (three_phase ? kSideSortMergePlace : kSideAll) : kSideSortMerge,
-                                              (ride_place && !three_phase) ? 1u : side_chunks, tail_blocks);
+                                              (ride_place && !three_phase) ? 1u : side_chunks, commit ? &dfr->pend : nullptr);
     if (rc) return rc;
     if (const int rs = enqueue_side()) return rs;
     cur_n = s->out_nid[1];
@@ -3288,7 +3342,7 @@ extern "C" int tgmx_recency_step(const tgmx_recency_step_t* s, tgmx_stream_t str
                              : (ride_place ? (merge_late ? kSideMergePlace : (split_merge ? kSidePlaceOnly : kSidePlace)) : kSideMerge);
     const int rc = csr ? launch_lookup<false>(a, st, e0, e1)
                        : launch_lookup<true>(a, st, e0, e1, ride ? &u : nullptr, stage,
-                                             (h == 1 && ride_place && !merge_late) ? 1u : side_chunks, (h == 1 && ride_place) ? tail_blocks : 0u);
+                                             (h == 1 && ride_place && !merge_late) ? 1u : side_chunks);
     if (rc) return rc;
     if (const int rs = enqueue_side()) return rs;
     cur_n = s->out_nid[h];
@@ -3302,8 +3356,12 @@ extern "C" int tgmx_recency_step(const tgmx_recency_step_t* s, tgmx_stream_t str
     if (mid) {
       (void)hipStreamWaitEvent(st, mid->join, 0);
       hipLaunchKernelGGL(ring_update_feat_kernel<true>, dim3((unsigned)((u.m + 3) / 4)), dim3(256), 0, st, u);
-    } else if (ride_place && tail_blocks) {
-      // written by the tail of the last lookup launch
+    } else if (defer) {
+      // deferred: committed by the next deferring call's lookup launch, or by the flush in front of any other call
+      dfr->pend = u;
+      dfr->pending = true;
+      dfr->stamp = stamp;
+      ++dfr->deferred;
     } else if (ride_place) {
       hipLaunchKernelGGL(ring_update_feat_kernel<true>, dim3((unsigned)((u.m + 3) / 4)), dim3(256), 0, st, u);
     } else if (side_chunks > 0) {

@@ -23,8 +23,11 @@ raises ``ValueError`` like the reference; ``'deferred'`` only raises when
 """
 from __future__ import annotations
 
+import ctypes
 import logging
+import os
 import warnings
+import weakref
 from typing import Dict, List, Optional, Sequence
 
 import torch
@@ -149,9 +152,14 @@ class RecencyNeighborHook(StatefulHook, SeedableHook):
         self._device: Optional[torch.device] = None
         self._edge_x_dim: Optional[int] = None
         # ring state (device)
-        self._ring: Optional[Tensor] = None  # [N*B, 2] int64 == 16-byte records
-        self._ring_x: Optional[Tensor] = None  # [N*B, D] float32
-        self._write_pos: Optional[Tensor] = None  # [N] int32
+        self._ring_t: Optional[Tensor] = None  # [N*B, 2] int64 == 16-byte records
+        self._ring_x_t: Optional[Tensor] = None  # [N*B, D] float32
+        self._write_pos_t: Optional[Tensor] = None  # [N] int32
+        # deferred commit (tgmx_recency_step_t.defer): a deferring call leaves its ring writes to the next one's lookup launch; any
+        # reader of the ring state (_ring, _ring_x, _write_pos, reset_state, a device move) flushes first.  False: never defer.
+        self._defer_commit = os.environ.get('TGMX_DEFER_COMMIT', '1') != '0'
+        self._defer = None  # tgmx_defer_t handle (an int); its device buffers are allocated by the first call that defers
+        self._pre_flush = None  # weak method set by a compiled loader pipeline: orders this thread's flush behind its launch worker
         self._scratch: Optional[Tensor] = None
         self._scratch_edges = 0  # batch size the scratch was sized for
         self._status: Optional[Tensor] = None  # [1] int32 device status word
@@ -184,17 +192,83 @@ class RecencyNeighborHook(StatefulHook, SeedableHook):
     def mode(self) -> str:
         return self._mode
 
+    # ring state: every read commits a deferred batch first
+    @property
+    def _ring(self) -> Optional[Tensor]:
+        self.flush_commit()
+        return self._ring_t
+
+    @property
+    def _ring_x(self) -> Optional[Tensor]:
+        self.flush_commit()
+        return self._ring_x_t
+
+    @property
+    def _write_pos(self) -> Optional[Tensor]:
+        self.flush_commit()
+        return self._write_pos_t
+
+    def flush_commit(self) -> None:
+        """Enqueue the deferred commit of the last batch, if one is pending (tgmx_defer_flush), on the device's current stream."""
+        if self._defer is None:
+            return
+        pre = self._pre_flush() if self._pre_flush is not None else None
+        if pre is not None:
+            pre()  # (first: a launch worker may be issuing a step that changes what is pending)
+        lib = _native.load()
+        if not lib.tgmx_defer_pending(self._defer):
+            return
+        with torch.cuda.device(self._device):
+            _native.check(lib.tgmx_defer_flush(self._defer, _native.stream_ptr(self._device.index)), 'tgmx_defer_flush')
+
+    @property
+    def defer_commit(self) -> bool:
+        """May a call leave its ring writes to the next call's lookup launch (tgmx_recency_step_t.defer)?  Results are the same
+        either way; setting it takes effect at the next call (False: what is pending is committed now)."""
+        return self._defer_commit
+
+    @defer_commit.setter
+    def defer_commit(self, on: bool) -> None:
+        self._defer_commit = bool(on)
+        if self._step is None or self._mode != 'ring':
+            return  # (the state is built at the first call)
+        if not on:
+            self._drop_defer()
+        else:
+            self._make_defer()
+        st = _native.RecencyStep()  # a new argument block: a loader pipeline bound to the old one binds again
+        ctypes.memmove(ctypes.byref(st), ctypes.byref(self._step), ctypes.sizeof(_native.RecencyStep))
+        st.defer = self._defer
+        self._step = st
+
+    def _make_defer(self) -> None:
+        if self._defer is None:
+            lib = _native.load()
+            h = lib.tgmx_defer_create(self._num_nodes, self._max_nbrs)
+            if not h:
+                _native.check(-2, 'tgmx_defer_create')
+            self._defer = h
+            self._defer_fin = weakref.finalize(self, lib.tgmx_defer_destroy, h)
+
+    def _drop_defer(self) -> None:
+        """Commit what is pending and release the deferred-commit state (its device buffers live on the current device)."""
+        if self._defer is not None:
+            self.flush_commit()
+            self._defer_fin()
+            self._defer = None
+
     def reset_state(self) -> None:
         """Forget all history (recency.py:111-117)."""
         self._last_batch_t = -(1 << 62)
         self._warned_order = False
         if self._mode == 'ring':
-            if self._ring is not None:
+            if self._ring_t is not None:
+                self.flush_commit()  # (the pending batch belongs to the history being forgotten, but it must not land after the reset)
                 lib = _native.load()
                 with torch.cuda.device(self._device):
                     _native.check(
                         lib.tgmx_ring_reset(
-                            self._ring.data_ptr(), self._write_pos.data_ptr(), self._max_nbrs, self._num_nodes, _native.stream_ptr()
+                            self._ring_t.data_ptr(), self._write_pos_t.data_ptr(), self._max_nbrs, self._num_nodes, _native.stream_ptr()
                         ),
                         'tgmx_ring_reset',
                     )
@@ -216,6 +290,8 @@ class RecencyNeighborHook(StatefulHook, SeedableHook):
     def _refresh_ts_bound(self, dg: DGraph) -> None:
         """The store is time-sorted and keeps a host copy of the timestamps: [0, last] bounds every batch of this graph
         (lets the large-batch update sort only the key bits that can be set); unknown / negative times: no promise."""
+        # a pending commit copies feature rows of the store bound so far: it lands before that store may be released
+        self.flush_commit()
         store = getattr(dg, '_storage', None)  # a foreign DGraph (the reference's) may keep its store elsewhere: no promise then
         self._bound_store = store
         bound = 0
@@ -292,21 +368,28 @@ class RecencyNeighborHook(StatefulHook, SeedableHook):
         if self._status is None or old != device:
             self._status = torch.zeros(1, dtype=torch.int32, device=device)
         if self._mode == 'ring':
-            if self._ring is None:
+            if self._ring_t is None:
                 self._warn_rings_under_world()
-                self._ring = torch.empty((N * B, 2), dtype=torch.int64, device=device)
-                self._ring_x = torch.empty((N * B, max(D, 1)), dtype=torch.float32, device=device) if D else None
-                self._write_pos = torch.empty(N, dtype=torch.int32, device=device)
+                self._ring_t = torch.empty((N * B, 2), dtype=torch.int64, device=device)
+                self._ring_x_t = torch.empty((N * B, max(D, 1)), dtype=torch.float32, device=device) if D else None
+                self._write_pos_t = torch.empty(N, dtype=torch.int32, device=device)
                 self.reset_state()
             elif old != device:  # migrate state (recency.py:401-408)
-                self._ring = self._ring.to(device)
-                self._ring_x = None if self._ring_x is None else self._ring_x.to(device)
-                self._write_pos = self._write_pos.to(device)
+                if self._defer is not None:  # the pending commit lands on the old device first; the overlay is rebuilt on the new one
+                    self._device = old
+                    self._drop_defer()
+                    self._device = device
+                self._ring_t = self._ring_t.to(device)
+                self._ring_x_t = None if self._ring_x_t is None else self._ring_x_t.to(device)
+                self._write_pos_t = self._write_pos_t.to(device)
                 self._scratch = None
                 self._scratch_edges = 0
         st = _native.RecencyStep()
         if self._mode == 'ring':
-            st.ring, st.write_pos, st.ring_x = self._ring.data_ptr(), self._write_pos.data_ptr(), _native.ptr(self._ring_x)
+            st.ring, st.write_pos, st.ring_x = self._ring_t.data_ptr(), self._write_pos_t.data_ptr(), _native.ptr(self._ring_x_t)
+            if self._defer_commit:
+                self._make_defer()
+            st.defer = self._defer
         else:
             self._csr = None  # rebuilt (and its pointers re-bound) on the new device
         st.D, st.B, st.num_nodes = D, B, N
@@ -387,7 +470,8 @@ class RecencyNeighborHook(StatefulHook, SeedableHook):
     def _ensure_scratch(self, n_edges: int, device: torch.device) -> None:
         """Ring-update scratch for batches of up to ``n_edges`` edges (grown, never shrunk)."""
         if n_edges > self._scratch_edges:
-            need = int(_native.load().tgmx_ring_update_scratch_bytes(n_edges, 1 if self._directed else 0))
+            lib = _native.load()
+            need = int(lib.tgmx_ring_update_scratch_bytes(n_edges, 1 if self._directed else 0))
             if need == 0:
                 _native.check(-2, 'tgmx_ring_update_scratch_bytes')
             # torch allocations are 256-byte aligned; zeros: the head of the scratch holds a self-resetting barrier
@@ -537,6 +621,7 @@ class RecencyNeighborHook(StatefulHook, SeedableHook):
 
             n_edges = batch.edge_src.shape[0] if ring_mode else 0
             keep = None
+            st.defer_ok = 0
             if n_edges:
                 self._ensure_scratch(n_edges, device)
                 ex = batch.edge_x
@@ -553,7 +638,12 @@ class RecencyNeighborHook(StatefulHook, SeedableHook):
                 st.eid0 = -1 if batch._edge_lo is None else int(batch._edge_lo)
                 # "time-sorted, 0 <= t <= ts_bound" is the STORE's promise: it covers this batch only if the batch is a zero-copy
                 # slice of the store (a user-built, filtered or permuted batch gets the span reduction and no sortedness claim)
-                st.ts_bound, st.sorted_ts = self._store_promise if self._is_store_slice(batch, tt, device) else (0, 0)
+                slice_ = self._is_store_slice(batch, tt, device)
+                st.ts_bound, st.sorted_ts = self._store_promise if slice_ else (0, 0)
+                # the commit may wait for the next call only if what it reads stays put: feature rows that are the store's own
+                if slice_ and self._defer is not None and batch._edge_lo is not None:
+                    sx = self._bound_store.on(device).edge_x if D else None
+                    st.defer_ok = 1 if (ex is None or (sx is not None and ex.data_ptr() == sx.data_ptr() + 4 * D * int(batch._edge_lo))) else 0
 
             # bad seeds must leave the state untouched (the reference validates before it changes anything): with
             # guard_seed_errors the update of this very call skips its writes when the lookups flagged a seed, so one call and

@@ -47,6 +47,7 @@ from __future__ import annotations
 import ctypes
 import os
 import sys
+import weakref
 from typing import Dict, List, Optional, Sequence
 
 import torch
@@ -197,6 +198,7 @@ class CompiledPipeline:
         p.step.ts_bound, p.step.sorted_ts = nbr._store_promise  # the lowered chain's batches are slices of the resident store
         self._pipe, self._step_ref = p, nbr._step
         self._scratch_ptr = nbr._step.scratch
+        nbr._pre_flush = weakref.WeakMethod(self._order_behind_worker)  # a flush of the hook's deferred commit goes behind the worker's steps
 
     # -- output sets -----------------------------------------------------------------
     def _share(self, n: int) -> int:
