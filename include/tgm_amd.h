@@ -285,6 +285,9 @@ void tgmx_defer_destroy(tgmx_defer_t* d);
 int tgmx_defer_pending(const tgmx_defer_t* d);
 int64_t tgmx_defer_count(const tgmx_defer_t* d);       /* batches whose commit was deferred so far */         /* 1: a commit waits */
 int tgmx_defer_flush(tgmx_defer_t* d, tgmx_stream_t stream); /* enqueue the pending commit (one launch) on `stream` */
+/* hop-1 rows per wave of the fused hop-0 + hop-1 lookup launch from now on (0: one wave per row, the default; -1: back to
+ * TGMX_FUSED_ROWS / the default); returns the previous value.  A/B and tests. */
+int32_t tgmx_set_fused_rows(int32_t rows);
 
 /* ------------------------------------------------------------------------
  * The loader's per-batch call as ONE entry point: DGDataLoader.__call__ (tgm/data/loader.py:158-170: slice,

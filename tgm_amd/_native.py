@@ -308,6 +308,7 @@ SIGNATURES['tgmx_defer_destroy'] = (None, [_P])
 SIGNATURES['tgmx_defer_pending'] = (c_int32, [_P])
 SIGNATURES['tgmx_defer_count'] = (c_int64, [_P])
 SIGNATURES['tgmx_defer_flush'] = (c_int32, [_P, _P])
+SIGNATURES['tgmx_set_fused_rows'] = (c_int32, [c_int32])
 SIGNATURES['tgmx_tgn_gru_gate_backward'] = (c_int32, [_P, _P, _P, _P, c_int32, c_int64, _P, _P, _P])
 SIGNATURES['tgmx_tgn_aggregate_backward'] = (c_int32, [c_int64, _P, _P, _P, _P, _P, _P, c_int32, c_int32, _P, _P, c_int32, c_int32, _P, _P, _P])
 SIGNATURES['tgmx_tconv_edge_attr_backward'] = (c_int32, [_P, _P, _P, _P, _P, _P, c_int32, c_int32, c_int64, _P, _P])

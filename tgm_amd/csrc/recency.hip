@@ -21,9 +21,12 @@
 //   lookup pieces (fetch_seed ... lookup_seed) and the kernels built from them: recency_lookup_kernel (one hop),
 //     recency_lookup_fused01_kernel (hop 0 + hop 1 in one launch), lookup_packed_kernel (narrow rows)
 //   the stand-alone update paths (one workgroup / chunk sort + merge / rocPRIM radix sort), uniform sampler, C entry points
+#include <algorithm>
 #include <atomic>
 #include <cstdlib>
 #include <cstring>
+#include <string>
+#include <vector>
 
 #include <hip/hip_ext.h>
 #include <rocprim/block/block_radix_sort.hpp>
@@ -116,6 +119,9 @@ struct LookupArgs {
   int32_t* out_valid1;
   int32_t* out_valid_prev;   // optional: receives the span a row held BEFORE this call (byte accounting of a timed launch)
   int32_t* out_valid_prev1;
+  // fused launch: hop-1 rows per wave (recency_lookup_fused01_kernel; 0 = one wave per row), and the debug timestamps (TGMX_FUSED_TS)
+  int fused_rows;
+  long long* ts;
 };
 
 template <int VEC>
@@ -1134,41 +1140,40 @@ struct SmallPick {
   long long ts;
 };
 
-template <bool RING>
-__device__ __forceinline__ SmallPick small_pick(const LookupArgs& a, int n, long long q, int k, bool live, int lane) {
-  const int B = a.B;
-  const Window w = find_window<RING>(a, n, live, lane);
-  Rec r;
-  r.nbr = -1; r.eid = 0; r.ts = 0;
-  int src = -1;  // RING: feature row of the record this lane holds (ring row, or N * B + store row of a pending slot)
-  if (RING) {
-    // the row is read in slot order (no wait for write_pos) and rotated into time order by a shuffle; with a commit pending in
-    // this launch, its records and slot stamps are read beside it (all three depend on n only) and pending slots take them
-    const long long row = (long long)n * B + lane;
-    Rec pr;
-    int ps = 0;
-    if (live && lane < B) {
-      r = a.recs[row];
+// the loads of a RING pick: everything the pick of node n reads, all of it depending on n alone (write_pos word, overlay header,
+// the ring row in slot order and, with a commit pending, its records and slot stamps).  Split from the selection below so that a
+// caller can issue the loads of its NEXT row ahead of streaming the current one (the fused launch's row runs)
+struct PickLoads {
+  Rec r, pr;
+  int ps, wp;
+  unsigned long long h;
+};
+
+__device__ __forceinline__ PickLoads pick_issue(const LookupArgs& a, int n, bool live, int lane) {
+  PickLoads L;
+  L.r.nbr = -1; L.r.eid = 0; L.r.ts = 0;
+  L.ps = 0;
+  L.wp = 0;
+  L.h = 0ull;
+  if (live) {
+    L.wp = a.write_pos[n];
+    if (a.phdr) L.h = a.phdr[n];
+    if (lane < a.B) {
+      const long long row = (long long)n * a.B + lane;
+      L.r = a.recs[row];
       if (a.phdr) {
-        pr = a.prec[row];
-        ps = a.pslot[row];
+        L.pr = a.prec[row];
+        L.ps = a.pslot[row];
       }
     }
-    src = (int)row;
-    if (a.phdr && live && lane < B && (unsigned)ps == a.pstamp) {
-      r = pr;
-      src = a.pstore ? a.N * B + (r.eid - a.peid0) : -1;  // (no feature rows in the store: the commit writes zeros)
-    }
-    int from_slot = w.wrot + lane;
-    if (from_slot >= B) from_slot -= B;
-    if (lane >= B) from_slot = lane;
-    r.nbr = __shfl(r.nbr, from_slot);
-    r.ts = __shfl(r.ts, from_slot);
-    src = __shfl(src, from_slot);
-    if (a.out_eid || a.out_eid1) r.eid = __shfl(r.eid, from_slot);  // (only a caller that asked for edge ids reads it: wave-uniform)
-  } else if (lane < w.wlen) {
-    r = a.recs[slot_of<RING>(w, B, lane)];
   }
+  return L;
+}
+
+// the ballot / shuffle selection of a pick: lane c < k gets output slot c, from the records r of a window of wlen entries
+// (src: RING feature row of the record this lane holds)
+template <bool RING>
+__device__ __forceinline__ SmallPick pick_select(const LookupArgs& a, const Window& w, Rec r, int src, long long q, int k, int lane) {
   const bool ok = lane < w.wlen && r.nbr >= 0 && r.ts < q;
   const unsigned long long m = __ballot(ok);
   const int cnt = m ? 64 - __clzll((long long)m) : 0;  // 1 + unrolled position of the rightmost entry with ts < q
@@ -1182,9 +1187,50 @@ __device__ __forceinline__ SmallPick small_pick(const LookupArgs& a, int n, long
   o.has = i >= 0 && g_nbr >= 0;
   o.nbr = o.has ? g_nbr : -1;
   o.ts = o.has ? g_ts : 0;
-  o.src = o.has ? (RING ? g_src : (a.x_by_pos ? (int)slot_of<RING>(w, B, from) : g_eid)) : -1;
+  o.src = o.has ? (RING ? g_src : (a.x_by_pos ? (int)slot_of<RING>(w, a.B, from) : g_eid)) : -1;
   o.eid = o.has ? g_eid : -1;
   return o;
+}
+
+// the RING pick of node n from its issued loads: the row is read in slot order (no wait for write_pos) and rotated into time
+// order by a shuffle; with a commit pending in this launch, its records and slot stamps were read beside it and pending slots
+// take them
+__device__ __forceinline__ SmallPick pick_finish(const LookupArgs& a, const PickLoads& L, int n, long long q, int k, bool live, int lane) {
+  const int B = a.B;
+  Window w;
+  w.w0 = live ? (long long)n * B : 0;
+  w.wlen = live ? B : 0;
+  w.wrot = live ? ((a.phdr && (unsigned)(L.h >> 32) == a.pstamp) ? (int)(unsigned)L.h : L.wp) % B : 0;
+  Rec r = L.r;
+  const long long row = (long long)n * B + lane;
+  int src = (int)row;  // feature row of the record this lane holds (ring row, or N * B + store row of a pending slot)
+  if (a.phdr && live && lane < B && (unsigned)L.ps == a.pstamp) {
+    r = L.pr;
+    src = a.pstore ? a.N * B + (r.eid - a.peid0) : -1;  // (no feature rows in the store: the commit writes zeros)
+  }
+  int from_slot = w.wrot + lane;
+  if (from_slot >= B) from_slot -= B;
+  if (lane >= B) from_slot = lane;
+  r.nbr = __shfl(r.nbr, from_slot);
+  r.ts = __shfl(r.ts, from_slot);
+  src = __shfl(src, from_slot);
+  if (a.out_eid || a.out_eid1) r.eid = __shfl(r.eid, from_slot);  // (only a caller that asked for edge ids reads it: wave-uniform)
+  return pick_select<true>(a, w, r, src, q, k, lane);
+}
+
+// (RING: the two halves above.  Built this way, the default fused kernel asks for a 68-byte private segment that no instruction
+// touches, and runs ~4 % faster than with the one-piece small_pick of before (fewer SGPR spills: DESIGN.md section 5))
+template <bool RING>
+__device__ __forceinline__ SmallPick small_pick(const LookupArgs& a, int n, long long q, int k, bool live, int lane) {
+  if constexpr (RING) {
+    return pick_finish(a, pick_issue(a, n, live, lane), n, q, k, live, lane);
+  } else {
+    const Window w = find_window<RING>(a, n, live, lane);
+    Rec r;
+    r.nbr = -1; r.eid = 0; r.ts = 0;
+    if (lane < w.wlen) r = a.recs[slot_of<RING>(w, a.B, lane)];
+    return pick_select<RING>(a, w, r, -1, q, k, lane);
+  }
 }
 
 // phase B: stream the [k, D] block of row s; lds_eid[c] = feature row of output slot c (-1: zeros)
@@ -1318,46 +1364,91 @@ __global__ __launch_bounds__(256) void recency_lookup_kernel(const LookupArgs a,
   }
 }
 
+// Debug timestamps of the fused launch (TGMX_FUSED_TS, off by default; launch_fused01).  Lane 0 of every wave writes one record
+// of kFusedTsWords words at ts[wave of the grid]: wall_clock64() at start and end, the role, and for hop-1 waves the end of the seed
+// phase (hop 0's pick for s0) and the clock spent in the rows' index phase (the pick: waiting for its loads) and gather phase.
+constexpr int kFusedTsWords = 8;
+// hop-1 rows per wave of the fused launch (TGMX_FUSED_ROWS): 0, the one-wave-per-row schedule, measured fastest at the wiki
+// shape (row runs of G = 1 - 5 were not faster)
+constexpr int kFusedRowsDefault = 0;
+enum FusedTsRole : long long { kTsRider = 1, kTsCommit = 2, kTsHop0 = 3, kTsHop1 = 4 };
+// the clock read after `v` is known: the empty asm consumes it, and nothing moves a side-effecting read across it
+__device__ __forceinline__ long long ts_after(int v) {
+  asm volatile("" ::"v"(v));
+  return (long long)wall_clock64();
+}
+
+// one hop-1 row of the fused launch from its issued pick loads: ids and times, then the delta feature write (lookup_seed's tail)
+template <bool RING>
+__device__ __forceinline__ SmallPick fused_row_pick(const LookupArgs& a, const PickLoads& L, int n, long long q, bool live, int lane) {
+  if constexpr (RING) return pick_finish(a, L, n, q, a.k1, live, lane);
+  else return small_pick<false>(a, n, q, a.k1, live, lane);  // (static index: the window search is a chain of its own, not prefetched)
+}
+
 // Hop 0 and hop 1 in ONE launch (B, k0, k1 <= 64).  Hop 1's seeds are hop 0's outputs, but the rings do not move
 // between the two, so the wave of hop-1 row (s0, j) re-derives its seed itself: it repeats hop 0's window search for
 // seed s0 (one 16-byte read per lane of a row that 1 + k0 waves share: L2 hits) and takes output slot j.  That removes
 // the dependency between the launches: the few hundred hop-0 seeds -- a launch bound by its three dependent reads, not
 // by bandwidth -- run inside the big hop-1 launch instead of in front of it.  Waves [0, S0) are hop 0 (they also
-// publish the concatenated seeds), waves [S0, S0 + S0 k0) are hop 1; results are identical to the two launches.
-template <bool RING, int VEC, int PCAP = kRidePlaceMaxM>
+// publish the concatenated seeds), the rest hop 1; results are identical to the two launches.
+//
+// Row runs (a.fused_rows = G > 0, TGMX_FUSED_ROWS; not the default, measured slower): a hop-1 wave takes G consecutive rows j0 .. j0 + G - 1 of ONE hop-0 seed s0
+// (ceil(k0 / G) waves per seed).  It picks hop 0 for s0 once, keeps the picked (n_j, q_j) in its lanes, reads the G rows' spans
+// (out_valid) up front, and issues the pick loads of row r + 1 before streaming row r's [k1, D] block, so that a wave exposes
+// the chain seed -> hop-0 pick -> hop-1 pick once instead of once per row.  A pad seed issues no pick loads at all.
+// a.fused_rows = 0 (the default, kFusedRowsDefault): one wave per hop-1 row, every wave repeating the hop-0 pick.
+// ROWS: the kernel is built apart for each schedule, so that the old one keeps its registers (and its occupancy).
+template <bool RING, int VEC, int PCAP = kRidePlaceMaxM, bool ROWS = false, bool TS = false>
 //
 // Deferred commit (a.commit_blocks > 0): the workgroups behind the riders commit the PREVIOUS batch (c) while everything else runs;
 // the lookups see it through the overlay (small_pick, gather_rows), the riders through logical_wp.
 __global__ __launch_bounds__(256) void recency_lookup_fused01_kernel(const LookupArgs a, const UpdateArgs u, const UpdateArgs c) {
   extern __shared__ __attribute__((aligned(16))) int lds_eid_all[];
   unsigned bid = blockIdx.x, nblk = gridDim.x;
+  const int lane = lane_id();
+  const int wave_in_block = threadIdx.x >> 6;
+  long long* ts_rec = TS ? a.ts + ((long long)blockIdx.x * (blockDim.x >> 6) + wave_in_block) * kFusedTsWords : nullptr;
+  const long long t_start = TS ? (long long)wall_clock64() : 0;
   if constexpr (RING) {
     if (bid < a.side_blocks) {
       update_side_work<PCAP>(u, a.side_stage, (int)bid);
+      if (TS && lane == 0) {
+        ts_rec[0] = t_start;
+        ts_rec[1] = (long long)wall_clock64();
+        ts_rec[2] = kTsRider;
+      }
       return;
     }
     bid -= a.side_blocks;
     if (bid < a.commit_blocks) {
       commit_block(c, bid);
+      if (TS && lane == 0) {
+        ts_rec[0] = t_start;
+        ts_rec[1] = (long long)wall_clock64();
+        ts_rec[2] = kTsCommit;
+      }
       return;
     }
     bid -= a.commit_blocks;
     nblk -= a.side_blocks + a.commit_blocks;
   }
-  const int lane = lane_id();
-  const int wave_in_block = threadIdx.x >> 6;
   const int k0 = a.k, k1 = a.k1;
   int* lds_eid = lds_eid_all + wave_in_block * (k0 > k1 ? k0 : k1);
   const long long waves_total = (long long)nblk * (blockDim.x >> 6);
-  const long long S0 = a.S, S1 = a.S * k0;
-  for (long long w = (long long)bid * (blockDim.x >> 6) + wave_in_block; w < S0 + S1; w += waves_total) {
+  const long long S0 = a.S;
+  const int G = ROWS ? a.fused_rows : 0;
+  const int runs = G > 0 ? (k0 + G - 1) / G : k0;  // hop-1 waves per hop-0 seed
+  long long role = 0, t_seed = 0, t_index = 0, t_gather = 0;
+  for (long long w = (long long)bid * (blockDim.x >> 6) + wave_in_block; w < S0 + S0 * runs; w += waves_total) {
     int n;
     long long q;
     if (w < S0) {
+      role = kTsHop0;
       fetch_seed(a, w, lane, true, n, q);
       check_seed(a, n, q, 0, lane);
       lookup_seed<RING, VEC, true>(a, w, n, q, k0, lane, lds_eid, a.out_nid, a.out_ts, a.out_x, a.out_valid, a.out_valid_prev, a.out_eid);
-    } else {
+    } else if (!ROWS) {
+      role = kTsHop1;
       const long long idx = w - S0;
       const long long s0 = idx / k0;
       const int j = (int)(idx - s0 * k0);
@@ -1368,7 +1459,74 @@ __global__ __launch_bounds__(256) void recency_lookup_fused01_kernel(const Looku
       n = __shfl(o.nbr, j);
       q = __shfl(o.ts, j);
       lookup_seed<RING, VEC, true>(a, idx, n, q, k1, lane, lds_eid, a.out_nid1, a.out_ts1, a.out_x1, a.out_valid1, a.out_valid_prev1, a.out_eid1);
+    } else {
+      const long long run = w - S0;
+      const long long s0 = run / runs;
+      const int j0 = (int)(run - s0 * runs) * G;
+      const int rows = k0 - j0 < G ? k0 - j0 : G;
+      const long long base = s0 * k0 + j0;  // hop-1 row of the run's first seed
+      const bool feats = a.D > 0 && a.out_x1 != nullptr;
+      // the spans of the run's rows depend on nothing: lane r holds row r's
+      const int v_old_run = (feats && a.out_valid1 && lane < rows) ? a.out_valid1[base + lane] : 0;
+      int n0;
+      long long q0;
+      fetch_seed(a, s0, lane, false, n0, q0);
+      const SmallPick o0 = small_pick<RING>(a, n0, q0, k0, n0 >= 0 && n0 < a.N, lane);
+      n = __shfl(o0.nbr, j0);
+      q = __shfl(o0.ts, j0);
+      bool live = n >= 0 && n < a.N;
+      if (TS) {
+        role = kTsHop1 | ((long long)rows << 8);
+        t_seed = ts_after(n);
+      }
+      PickLoads L = RING ? pick_issue(a, n, live, lane) : PickLoads{};
+      for (int r = 0; r < rows; ++r) {
+        const long long s = base + r;
+        const long long t0 = TS ? (long long)wall_clock64() : 0;
+        const SmallPick o = fused_row_pick<RING>(a, L, n, q, live, lane);
+        if (lane < k1) {
+          a.out_nid1[s * k1 + lane] = o.nbr;
+          a.out_ts1[s * k1 + lane] = o.ts;
+          if (a.out_eid1) a.out_eid1[s * k1 + lane] = o.eid;
+          lds_eid[lane] = o.src;
+        }
+        const unsigned long long m = __ballot(lane < k1 && o.has);
+        const int v_new = m ? k1 - __builtin_ctzll(m) : 0;
+        if (TS) {
+          const long long t1 = ts_after(v_new);
+          t_index += t1 - t0;
+        }
+        if (r + 1 < rows) {  // the next row's pick loads go out before this row's block is streamed
+          n = __shfl(o0.nbr, j0 + r + 1);
+          q = __shfl(o0.ts, j0 + r + 1);
+          live = n >= 0 && n < a.N;
+          if (RING) L = pick_issue(a, n, live, lane);
+        }
+        if (!feats) continue;  // no features, or the consumer gathers them by edge id (out_eid1)
+        int first_slot = 0;
+        if (a.out_valid1) {  // delta writes: lookup_seed's rule
+          const int v_old = __shfl(v_old_run, r);
+          first_slot = k1 - (v_old > v_new ? v_old : v_new);
+          if (lane == 0) {
+            a.out_valid1[s] = v_new;
+            if (a.out_valid_prev1) a.out_valid_prev1[s] = v_old;
+          }
+        }
+        const long long t2 = TS ? (long long)wall_clock64() : 0;
+        __builtin_amdgcn_wave_barrier();  // lds_eid written above is read cross-lane below
+        gather_rows<VEC>(a, s, k1, lane, lds_eid, a.out_x1, first_slot);
+        __builtin_amdgcn_wave_barrier();  // the next row reuses lds_eid
+        if (TS) t_gather += (long long)wall_clock64() - t2;
+      }
     }
+  }
+  if (TS && lane == 0) {
+    ts_rec[0] = t_start;
+    ts_rec[1] = (long long)wall_clock64();
+    ts_rec[2] = role;
+    ts_rec[3] = t_seed;
+    ts_rec[4] = t_index;
+    ts_rec[5] = t_gather;
   }
 }
 
@@ -2278,6 +2436,51 @@ static int launch_lookup(LookupArgs a, hipStream_t stream, hipEvent_t ev_start, 
 }
 
 
+// TGMX_FUSED_TS=<path> (debug only): the fused launch of the headline shape (rings, VEC 4, riders placing <= 512) runs with
+// timestamps (recency_lookup_fused01_kernel, TS), and after each launch the host waits for it and writes its records to
+// <path>.<launch % 16>: a header of 8 int64 (magic, waves, side_blocks, commit_blocks, S0, k0, rows per wave, clock kHz),
+// then kFusedTsWords int64 per wave of the grid.  tools/fused_ts_report.py summarises them.
+static const char* fused_ts_path() {
+  static const char* p = getenv("TGMX_FUSED_TS");
+  return (p && *p) ? p : nullptr;
+}
+
+static int fused_ts_dump(const LookupArgs& a, hipStream_t stream, unsigned blocks_total, unsigned waves_per_block) {
+  static unsigned long long launches = 0;
+  const long long waves = (long long)blocks_total * waves_per_block;
+  std::vector<long long> h((size_t)(8 + waves * kFusedTsWords));
+  if (hipStreamSynchronize(stream) != hipSuccess ||
+      hipMemcpy(h.data() + 8, a.ts, (size_t)waves * kFusedTsWords * sizeof(long long), hipMemcpyDeviceToHost) != hipSuccess) {
+    set_error("recency_lookup_fused01: reading the timestamps failed");
+    return TGMX_E_LAUNCH;
+  }
+  int dev = 0, khz = 0;
+  (void)hipGetDevice(&dev);
+  (void)hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, dev);
+  const long long hdr[8] = {0x54474d5854530001ll, waves, (long long)a.side_blocks, (long long)a.commit_blocks, a.S, a.k, a.fused_rows, khz};
+  std::copy(hdr, hdr + 8, h.begin());
+  const std::string path = std::string(fused_ts_path()) + "." + std::to_string(launches++ % 16);
+  if (FILE* f = fopen(path.c_str(), "wb")) {
+    fwrite(h.data(), sizeof(long long), h.size(), f);
+    fclose(f);
+  }
+  return TGMX_OK;
+}
+
+// hop-1 rows per wave of the fused launch: TGMX_FUSED_ROWS (0 = one wave per row; A/B knob), read once like the other TGMX_*
+// knobs; tgmx_set_fused_rows overrides it in a running process (tests compare the schedules in one process)
+static std::atomic<int> g_fused_rows{-1};  // -1: not read yet
+
+static int fused_rows_per_wave(int k0) {
+  int g = g_fused_rows.load(std::memory_order_relaxed);
+  if (g < 0) {
+    const char* e = getenv("TGMX_FUSED_ROWS");
+    g = (e && *e && atoi(e) >= 0) ? atoi(e) : kFusedRowsDefault;
+    g_fused_rows.store(g, std::memory_order_relaxed);
+  }
+  return g > k0 ? k0 : g;
+}
+
 // hop 0 (a: seeds / groups, k, outputs) and hop 1 (k1, out_*1) as one launch; the caller checked can_fuse01
 // commit (RING, optional): the previous batch's deferred commit, run by ceil(m / 4) workgroups behind the riders
 template <bool RING>
@@ -2288,22 +2491,50 @@ static int launch_fused01(LookupArgs a, hipStream_t stream, hipEvent_t ev_start,
   a.side_blocks = (RING && side) ? side_blocks : 0;
   a.side_stage = side_stage;
   a.commit_blocks = (RING && commit) ? (unsigned)((c.m + 3) / 4) : 0u;
+  a.fused_rows = fused_rows_per_wave(a.k);
   const int kmax = a.k > a.k1 ? a.k : a.k1;
   const int vec = prepare_lookup(a, a.out_x1, kmax);
   if (vec < 0) return vec;
   const int waves_per_block = 4;
-  const long long waves = a.S + a.S * a.k;
+  const long long runs = a.fused_rows > 0 ? (a.k + a.fused_rows - 1) / a.fused_rows : a.k;  // hop-1 waves per hop-0 seed
+  const long long waves = a.S + a.S * runs;
   long long blocks = (waves + waves_per_block - 1) / waves_per_block;
   if (blocks > (1 << 20)) blocks = 1 << 20;
   const dim3 grid((unsigned)blocks + a.side_blocks + a.commit_blocks), block(waves_per_block * kWave);
   const size_t lds = (size_t)waves_per_block * kmax * sizeof(int);
   // the riders' static LDS sized for what rides (RiderLds): placement of <= 512 entries, of <= 1024, or sort / merge only
   const int pcap = !(RING && side) ? 1024 : ((side_stage != kSideAll && side_stage != kSideSortMergePlace) ? 0 : (u.m <= 512 ? 512 : 1024));
-  if (vec == 4 && pcap == 512) TGMX_LAUNCH_TIMED((recency_lookup_fused01_kernel<RING, 4, RING ? 512 : 1024>), grid, block, lds, stream, ev_start, ev_stop, a, u, c);
-  else if (vec == 4 && pcap == 0) TGMX_LAUNCH_TIMED((recency_lookup_fused01_kernel<RING, 4, RING ? 0 : 1024>), grid, block, lds, stream, ev_start, ev_stop, a, u, c);
-  else if (vec == 4) TGMX_LAUNCH_TIMED((recency_lookup_fused01_kernel<RING, 4>), grid, block, lds, stream, ev_start, ev_stop, a, u, c);
-  else if (vec == 2) TGMX_LAUNCH_TIMED((recency_lookup_fused01_kernel<RING, 2>), grid, block, lds, stream, ev_start, ev_stop, a, u, c);
-  else TGMX_LAUNCH_TIMED((recency_lookup_fused01_kernel<RING, 1>), grid, block, lds, stream, ev_start, ev_stop, a, u, c);
+  if (RING && vec == 4 && pcap == 512 && fused_ts_path()) {
+    static long long* ts_buf = nullptr;
+    static size_t ts_cap = 0;
+    const size_t need = (size_t)grid.x * waves_per_block * kFusedTsWords * sizeof(long long);
+    if (need > ts_cap) {
+      if (ts_buf) (void)hipFree(ts_buf);
+      ts_buf = nullptr;
+      if (hipMalloc(&ts_buf, need) != hipSuccess) {
+        set_error("recency_lookup_fused01: no memory for the timestamps");
+        return TGMX_E_LAUNCH;
+      }
+      ts_cap = need;
+    }
+    a.ts = ts_buf;
+    (void)hipMemsetAsync(a.ts, 0, need, stream);
+    if (a.fused_rows > 0) TGMX_LAUNCH_TIMED((recency_lookup_fused01_kernel<true, 4, 512, true, true>), grid, block, lds, stream, ev_start, ev_stop, a, u, c);
+    else TGMX_LAUNCH_TIMED((recency_lookup_fused01_kernel<true, 4, 512, false, true>), grid, block, lds, stream, ev_start, ev_stop, a, u, c);
+    TGMX_CHECK_LAUNCH("recency_lookup_fused01");
+    return fused_ts_dump(a, stream, grid.x, waves_per_block);
+  }
+#define TGMX_FUSED(ROWS_)                                                                                                                            \
+  do {                                                                                                                                               \
+    if (vec == 4 && pcap == 512) TGMX_LAUNCH_TIMED((recency_lookup_fused01_kernel<RING, 4, RING ? 512 : 1024, ROWS_>), grid, block, lds, stream, ev_start, ev_stop, a, u, c); \
+    else if (vec == 4 && pcap == 0) TGMX_LAUNCH_TIMED((recency_lookup_fused01_kernel<RING, 4, RING ? 0 : 1024, ROWS_>), grid, block, lds, stream, ev_start, ev_stop, a, u, c); \
+    else if (vec == 4) TGMX_LAUNCH_TIMED((recency_lookup_fused01_kernel<RING, 4, kRidePlaceMaxM, ROWS_>), grid, block, lds, stream, ev_start, ev_stop, a, u, c);            \
+    else if (vec == 2) TGMX_LAUNCH_TIMED((recency_lookup_fused01_kernel<RING, 2, kRidePlaceMaxM, ROWS_>), grid, block, lds, stream, ev_start, ev_stop, a, u, c);            \
+    else TGMX_LAUNCH_TIMED((recency_lookup_fused01_kernel<RING, 1, kRidePlaceMaxM, ROWS_>), grid, block, lds, stream, ev_start, ev_stop, a, u, c);                          \
+  } while (0)
+  if (a.fused_rows > 0) TGMX_FUSED(true);
+  else TGMX_FUSED(false);
+#undef TGMX_FUSED
   TGMX_CHECK_LAUNCH("recency_lookup_fused01");
   return TGMX_OK;
 }
@@ -3116,6 +3347,11 @@ static int defer_buffers(tgmx_defer* d, hipStream_t st) {
 extern "C" int tgmx_defer_pending(const tgmx_defer_t* d) { return d && d->pending ? 1 : 0; }
 
 extern "C" int64_t tgmx_defer_count(const tgmx_defer_t* d) { return d ? d->deferred : 0; }
+extern "C" int32_t tgmx_set_fused_rows(int32_t rows) {
+  const int old = fused_rows_per_wave(1 << 30);
+  g_fused_rows.store(rows < 0 ? -1 : rows, std::memory_order_relaxed);
+  return old;
+}
 
 extern "C" int tgmx_defer_flush(tgmx_defer_t* d, tgmx_stream_t stream) {
   TGMX_REQUIRE(d, "defer_flush: null state");
