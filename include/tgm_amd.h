@@ -996,6 +996,76 @@ typedef struct tgmx_graphmixer_fwd {
 } tgmx_graphmixer_fwd_t;
 int tgmx_graphmixer_forward(const tgmx_graphmixer_fwd_t* args, tgmx_stream_t stream);
 
+/* ---- DyGFormer (the reference's tgm/nn/encoder/dygformer.py), inference ---- */
+
+/* Sequences: P (source, destination) pairs; sequence q = 2 p + side (side 0 = src[p], 1 = dst[p]) has L = k + 1 slots, slot 0 the seed
+ * itself and slot j > 0 the sampler's slot j - 1 of row src_rows[p] / dst_rows[p] of the hop-0 output nbr_* [S, k(, dE)] (src_rows /
+ * dst_rows NULL: rows p and P + p).  A row index outside [0, S) makes the sequence all pads.  Slot (q, j) is row q L + j of every output.
+ *
+ * Co-occurrence: for every slot the number of occurrences of its id in its own and in the other sequence of the pair (pads compare equal
+ * in the raw count and are zeroed afterwards) -> counts [2 P L, 2] int32 (may be NULL); with feat != NULL also the encoded feature
+ * feat[row, :C] = enc(own) + enc(other), enc(c) = W2 relu(w1 c + b1) + b2 read from a table over c = 0 .. L that the call fills first
+ * (table: [L + 1, C] floats of scratch), columns [C, ldf) zeroed.  k < 2048.  No device -> host read. */
+int tgmx_dygformer_cooccurrence(const int32_t* src, const int32_t* dst, int64_t P, const int32_t* nbr_nids, int64_t S, int32_t k,
+                                const int32_t* src_rows, const int32_t* dst_rows, const float* co_w1, const float* co_b1,
+                                const float* co_w2, const float* co_b2, int32_t C, float* table, int32_t* counts, float* feat,
+                                int64_t ldf, tgmx_stream_t stream);
+
+/* The node / edge / time channel inputs in one launch: node_out[row] = node_x[id] (0 for pads), edge_out[row] = nbr_x of the slot as the
+ * sampler wrote it (0 in slot 0), time_out[row] = cos(fma(float(edge_time[p] - nbr_t), tw, tb)) (int64 difference, then float; slot 0:
+ * 0; 0 for pads); columns past dN / dE / dT up to the leading dimensions zeroed. */
+int tgmx_dygformer_prologue(const float* node_x, int64_t num_nodes, int32_t dN, const int32_t* src, const int32_t* dst,
+                            const int64_t* edge_time, int64_t P, const int32_t* nbr_nids, const int64_t* nbr_t, const float* nbr_x,
+                            int64_t S, int32_t k, int32_t dE, const int32_t* src_rows, const int32_t* dst_rows, const float* tw,
+                            const float* tb, int32_t dT, float* node_out, int64_t ldn, float* edge_out, int64_t lde, float* time_out,
+                            int64_t ldt, tgmx_stream_t stream);
+
+/* y[r, :d] = LayerNorm(x[r, :d]) gamma + beta over the columns of each of R rows (biased variance). */
+int tgmx_layernorm_rows(const float* x, int64_t ldx, int64_t R, int32_t d, const float* gamma, const float* beta, float eps, float* y,
+                        int64_t ldy, tgmx_stream_t stream);
+
+/* out[b T + i, h dh : (h + 1) dh] = softmax_j(Q_i . K_j / sqrt(dh)) V over the T rows of group b, per head h; Q / K / V are columns
+ * [0, H dh), [H dh, 2 H dh), [2 H dh, 3 H dh) of qkv [B T, ldq] (nn.MultiheadAttention's in-projection output).  Exact-fp32 MFMA; scores
+ * and probabilities stay in LDS / registers.  T <= 128 and dh <= 128, otherwise TGMX_E_UNSUPPORTED. */
+int tgmx_mha_small(const float* qkv, int64_t ldq, int64_t B, int32_t T, int32_t H, int32_t dh, float* out, int64_t ldo,
+                   tgmx_stream_t stream);
+
+/* mean[side P + p, :D] = mean over the Np token rows (2 p + side) Np + t of x (columns [D, ldm) zeroed), then
+ * out [2 P, E] = mean out_w^T + out_b: sources in rows [0, P), destinations in [P, 2 P). */
+int tgmx_dygformer_tail(const float* x, int64_t ldx, int64_t P, int32_t Np, int32_t D, float* mean, int64_t ldm, const float* out_w,
+                        const float* out_b, int32_t E, float* out, tgmx_stream_t stream);
+
+/* One transformer layer on x [B T, ldx], in place: y = LN0(x); qkv = y in_w^T + in_b; att = tgmx_mha_small(qkv);
+ * x1 = att out_w^T + out_b + x; y = LN1(x1); h = gelu(y w1^T + b1); x = h w2^T + b2 + x1.  Leading dimensions: multiples of 4. */
+typedef struct tgmx_dygformer_layer {
+  const float *ln0_g, *ln0_b, *in_w, *in_b, *out_w, *out_b;  /* norm_layers.0, multi_head_attention */
+  const float *ln1_g, *ln1_b, *w1, *b1, *w2, *b2;            /* norm_layers.1, linear_layers.{0,1} */
+} tgmx_dygformer_layer_t;
+int tgmx_dygformer_layer(const tgmx_dygformer_layer_t* layer, int64_t B, int32_t T, int32_t H, int32_t D, float eps, float* x, float* y,
+                         float* x1, float* att, int64_t ldx, float* qkv, int64_t ldq, float* h, int64_t ldh, tgmx_stream_t stream);
+
+/* The DyGFormer inference forward as ONE call: tgmx_dygformer_cooccurrence (features), tgmx_dygformer_prologue, the four patch
+ * projections (patching is a view: channel c is [2 P Np, patch ldch[c]], its GEMM writes columns [c C, (c + 1) C) of x),
+ * tgmx_dygformer_layer per layer, tgmx_dygformer_tail -- the same launches in the same order as those entry points called one by one
+ * (identical results).  proj_w[c]: [C, patch ldch[c]] (each slot's columns zero-padded to ldch[c]).  Scratch: table [(k + 2) C],
+ * ch[c] [2 P L, ldch[c]], x / y / x1 / att [2 P Np, ldx], mean [2 P, ldx], qkv [2 P Np, ldq], h [2 P Np, ldh]. */
+#define TGMX_DYGFORMER_MAX_LAYERS 8
+typedef struct tgmx_dygformer_fwd {
+  const float* node_x; int64_t num_nodes;
+  const int32_t *src, *dst; const int64_t* edge_time; int64_t P;
+  const int32_t* nbr_nids; const int64_t* nbr_t; const float* nbr_x; int64_t S;  /* hop 0: [S, k], [S, k], [S, k, dE] */
+  const int32_t *src_rows, *dst_rows;                                            /* [P] rows of hop 0, or NULL */
+  int32_t k, dN, dE, dT, C, patch, heads, E, num_layers; float eps;
+  const float *tw, *tb, *co_w1, *co_b1, *co_w2, *co_b2;
+  const float* proj_w[4]; const float* proj_b[4];                                /* node, edge, time, co-occurrence */
+  const float *out_w, *out_b;
+  tgmx_dygformer_layer_t layers[TGMX_DYGFORMER_MAX_LAYERS];
+  float* table; float* ch[4]; int64_t ldch[4];
+  float *x, *y, *x1, *att, *qkv, *h, *mean; int64_t ldx, ldq, ldh;
+  float* out;                                                                    /* [2 P, E] */
+} tgmx_dygformer_fwd_t;
+int tgmx_dygformer_forward(const tgmx_dygformer_fwd_t* args, tgmx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

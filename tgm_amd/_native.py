@@ -260,6 +260,39 @@ class GraphMixerFwd(ctypes.Structure):
     ]  # fmt: skip
 
 
+DYGFORMER_MAX_LAYERS = 8  # TGMX_DYGFORMER_MAX_LAYERS
+DYGFORMER_MAX_SEQ = 2048  # slots per sequence (tgmx_dygformer_cooccurrence keeps both id sequences in LDS)
+MHA_SMALL_MAX_TOKENS = 128  # tgmx_mha_small's envelope
+MHA_SMALL_MAX_HEAD_DIM = 128
+
+
+class DyGFormerLayer(ctypes.Structure):
+    """tgmx_dygformer_layer_t (include/tgm_amd.h)."""
+
+    _fields_ = [(n, c_void_p) for n in ('ln0_g', 'ln0_b', 'in_w', 'in_b', 'out_w', 'out_b', 'ln1_g', 'ln1_b', 'w1', 'b1', 'w2', 'b2')]
+
+
+class DyGFormerFwd(ctypes.Structure):
+    """tgmx_dygformer_fwd_t (include/tgm_amd.h)."""
+
+    _fields_ = [
+        ('node_x', c_void_p), ('num_nodes', c_int64),
+        ('src', c_void_p), ('dst', c_void_p), ('edge_time', c_void_p), ('P', c_int64),
+        ('nbr_nids', c_void_p), ('nbr_t', c_void_p), ('nbr_x', c_void_p), ('S', c_int64),
+        ('src_rows', c_void_p), ('dst_rows', c_void_p),
+        ('k', c_int32), ('dN', c_int32), ('dE', c_int32), ('dT', c_int32), ('C', c_int32), ('patch', c_int32), ('heads', c_int32), ('E', c_int32),
+        ('num_layers', c_int32), ('eps', ctypes.c_float),
+        ('tw', c_void_p), ('tb', c_void_p), ('co_w1', c_void_p), ('co_b1', c_void_p), ('co_w2', c_void_p), ('co_b2', c_void_p),
+        ('proj_w', c_void_p * 4), ('proj_b', c_void_p * 4),
+        ('out_w', c_void_p), ('out_b', c_void_p),
+        ('layers', DyGFormerLayer * DYGFORMER_MAX_LAYERS),
+        ('table', c_void_p), ('ch', c_void_p * 4), ('ldch', c_int64 * 4),
+        ('x', c_void_p), ('y', c_void_p), ('x1', c_void_p), ('att', c_void_p), ('qkv', c_void_p), ('h', c_void_p), ('mean', c_void_p),
+        ('ldx', c_int64), ('ldq', c_int64), ('ldh', c_int64),
+        ('out', c_void_p),
+    ]  # fmt: skip
+
+
 class TconvFwd(ctypes.Structure):
     """tgmx_tconv_fwd_t (include/tgm_amd.h)."""
 
@@ -372,6 +405,19 @@ SIGNATURES['tgmx_mixer_tail'] = (
     [_P, c_int64, c_int64, c_int32, c_int32, _P, _P, c_int64, c_int32, _P, _P, _P, _P, c_int64, _P, c_int64, _P, _P, c_int64, _P],
 )
 SIGNATURES['tgmx_graphmixer_forward'] = (c_int32, [ctypes.POINTER(GraphMixerFwd), _P])
+SIGNATURES['tgmx_dygformer_cooccurrence'] = (c_int32, [_P, _P, c_int64, _P, c_int64, c_int32, _P, _P, _P, _P, _P, _P, c_int32, _P, _P, _P, c_int64, _P])
+SIGNATURES['tgmx_dygformer_prologue'] = (
+    c_int32,
+    [_P, c_int64, c_int32, _P, _P, _P, c_int64, _P, _P, _P, c_int64, c_int32, c_int32, _P, _P, _P, _P, c_int32, _P, c_int64, _P, c_int64, _P, c_int64, _P],
+)
+SIGNATURES['tgmx_layernorm_rows'] = (c_int32, [_P, c_int64, c_int64, c_int32, _P, _P, ctypes.c_float, _P, c_int64, _P])
+SIGNATURES['tgmx_mha_small'] = (c_int32, [_P, c_int64, c_int64, c_int32, c_int32, c_int32, _P, c_int64, _P])
+SIGNATURES['tgmx_dygformer_tail'] = (c_int32, [_P, c_int64, c_int64, c_int32, c_int32, _P, c_int64, _P, _P, c_int32, _P, _P])
+SIGNATURES['tgmx_dygformer_layer'] = (
+    c_int32,
+    [ctypes.POINTER(DyGFormerLayer), c_int64, c_int32, c_int32, c_int32, ctypes.c_float, _P, _P, _P, _P, c_int64, _P, c_int64, _P, c_int64, _P],
+)
+SIGNATURES['tgmx_dygformer_forward'] = (c_int32, [ctypes.POINTER(DyGFormerFwd), _P])
 
 _lib: Optional[ctypes.CDLL] = None
 

@@ -34,6 +34,8 @@ extern "C" size_t tgmx_abi_sizeof(int32_t which) {
     case 12: return sizeof(tgmx_tgn_step_t);
     case 13: return sizeof(tgmx_mixer_layer_t);
     case 14: return sizeof(tgmx_graphmixer_fwd_t);
+    case 15: return sizeof(tgmx_dygformer_layer_t);
+    case 16: return sizeof(tgmx_dygformer_fwd_t);
     default: return 0;
   }
 }

@@ -1,6 +1,7 @@
 from ._paramver import invalidate_parameter_caches
 from .attention import TemporalAttention
 from .base import EncoderModule
+from .dygformer import DyGFormer, NeighborCooccurrenceEncoder, TransformerEncoder
 from .graphmixer import GraphMixerEncoder
 from .mlp_mixer import FeedForwardNet, MLPMixer
 from .tgat import TGAT, MergeLayer
@@ -10,7 +11,7 @@ from .time_encoding import Time2Vec
 from . import encoder, modules  # noqa: E402,F401  (the reference's import paths: tgm.nn.encoder.tgn, tgm.nn.modules.attention, ...)
 
 __all__ = [
-    'EncoderModule', 'FeedForwardNet', 'GCNConv', 'GraphAttentionEmbedding', 'GraphMixerEncoder', 'IdentityMessage', 'LastAggregator',
-    'MLPMixer', 'MeanAggregator', 'MergeLayer', 'TGAT', 'TGCN',
-    'TGNMemory', 'TGNStep', 'TemporalAttention', 'Time2Vec', 'TransformerConv', 'invalidate_parameter_caches', 'sampled_edge_list',
+    'DyGFormer', 'EncoderModule', 'FeedForwardNet', 'GCNConv', 'GraphAttentionEmbedding', 'GraphMixerEncoder', 'IdentityMessage', 'LastAggregator',
+    'MLPMixer', 'MeanAggregator', 'MergeLayer', 'NeighborCooccurrenceEncoder', 'TGAT', 'TGCN',
+    'TGNMemory', 'TGNStep', 'TemporalAttention', 'Time2Vec', 'TransformerConv', 'TransformerEncoder', 'invalidate_parameter_caches', 'sampled_edge_list',
 ]  # fmt: skip

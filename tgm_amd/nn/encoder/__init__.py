@@ -3,12 +3,13 @@
 them.  The submodule names resolve to the modules that hold the implementations -- nothing is defined here."""
 import sys
 
-from .. import tgat, tgcn, tgn
+from .. import dygformer, tgat, tgcn, tgn
+from ..dygformer import DyGFormer
 from ..tgat import TGAT
 from ..tgcn import TGCN
 from ..tgn import GraphAttentionEmbedding, IdentityMessage, LastAggregator, MeanAggregator, TGNMemory
 
-for _m in (tgat, tgcn, tgn):
+for _m in (dygformer, tgat, tgcn, tgn):
     sys.modules[f'{__name__}.{_m.__name__.rsplit(".", 1)[1]}'] = _m
 
-__all__ = ['GraphAttentionEmbedding', 'IdentityMessage', 'LastAggregator', 'MeanAggregator', 'TGAT', 'TGCN', 'TGNMemory']
+__all__ = ['DyGFormer', 'GraphAttentionEmbedding', 'IdentityMessage', 'LastAggregator', 'MeanAggregator', 'TGAT', 'TGCN', 'TGNMemory']
