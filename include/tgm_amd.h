@@ -1066,6 +1066,75 @@ typedef struct tgmx_dygformer_fwd {
 } tgmx_dygformer_fwd_t;
 int tgmx_dygformer_forward(const tgmx_dygformer_fwd_t* args, tgmx_stream_t stream);
 
+/* ---- TPNet (the reference's tgm/nn/encoder/tpnet.py): temporal walk matrices as random projections, pair features, inference ---- */
+
+/* The num_layer + 1 tables P[0 .. levels) of RandomProjectionModule, each [num_nodes, dim] float32, row-major, contiguous. */
+#define TGMX_TPNET_MAX_LEVELS 8
+#define TGMX_TPNET_HEAD_EMPTY 0x7f7f7f7f
+typedef struct tgmx_tpnet_tables {
+  float* P[TGMX_TPNET_MAX_LEVELS];
+  int32_t levels, dim;
+  int64_t num_nodes;
+} tgmx_tpnet_tables_t;
+
+/* RandomProjectionModule.update for one batch of n edges (src, dst int32 [n], time int64 [n]), deterministic, no float atomics:
+ * next = time[n - 1]; w_e = exp(-lambda (next - time[e])); every level i >= 1 is scaled by exp(-lambda (next - now) i); then row src[e] of
+ * P[i] gains P[i-1][dst[e]] w_e and row dst[e] gains P[i-1][src[e]] w_e, where P[i-1] is the (scaled) table BEFORE this batch adds to
+ * it.  A row's contributions are added in the order all sources (e = 0 .. n-1), then all destinations.  Two launches: the first stages
+ * every message into msg [(levels - 1) 2 n dim] floats reading the tables only, the second rescales and adds, each element written by
+ * one thread.  now: int64 (now_is_f64 = 0) or double on the device; *now_out = next afterwards (may alias now when that is int64).
+ * head: [num_nodes] int32 of scratch that holds TGMX_TPNET_HEAD_EMPTY in every entry on entry, and again on exit.  Edges with an endpoint
+ * outside [0, num_nodes) contribute nothing.  n = 0: nothing happens.  No device -> host read. */
+int tgmx_tpnet_update(const tgmx_tpnet_tables_t* tables, const int32_t* src, const int32_t* dst, const int64_t* time, int64_t n,
+                      double lambda, const void* now, int32_t now_is_f64, int64_t* now_out, float* msg, int32_t* head,
+                      tgmx_stream_t stream);
+
+/* Pair features of n items (n a multiple of k): item t = q k + j pairs node a[(a_rows ? a_rows[q] : q) k + j] (a row index outside
+ * [0, a_num_rows) reads as id -1) with node b0[q mod bmod].  With R_x = the levels rows P[0 .. levels)[x] of a node (a negative id
+ * indexes from the end: -1 is the last row), out[t] holds, row-major, concat != 0: the (2 levels)^2 Gram matrix of [R_a; R_b];
+ * concat = 0: the levels^2 products R_a R_b^T.  scale != 0: negatives clamped to 0, then log(x + 1).  b1 != NULL: rows [n, 2 n) of out
+ * hold the same for b1.  Columns up to ldo zeroed.  levels <= 4, otherwise TGMX_E_UNSUPPORTED.  [n, 2 levels, dim] is never stored. */
+int tgmx_tpnet_pair_features(const tgmx_tpnet_tables_t* tables, const int32_t* a, const int32_t* a_rows, int64_t a_num_rows, int32_t k,
+                             const int32_t* b0, const int32_t* b1, int64_t bmod, int64_t n, int32_t concat, int32_t scale, float* out,
+                             int64_t ldo, tgmx_stream_t stream);
+
+/* TPNet's token matrix, row (q, j) for q < 2 B sequences (sources, then destinations) of k slots read from row rows[q] (NULL: q) of the
+ * hop-0 output nbr_* [S, k(, dE)]: [node_x[id] (0 on pad slots) | cos(tw log(edge_time[q mod B] - nbr_t + 1) + tb) (0 on pad slots) |
+ * nbr_x as given | pf[row, :pf_dim] | pf[2 B k + row, :pf_dim] | 0 up to ldo].  A row index outside [0, S) reads as all pads, zero
+ * edge features. */
+int tgmx_tpnet_tokens(const float* node_x, int64_t num_nodes, int32_t dN, const int64_t* edge_time, int64_t B, const int32_t* nbr_nids,
+                      const int64_t* nbr_t, const float* nbr_x, int64_t S, int32_t k, int32_t dE, const int32_t* rows, const float* tw,
+                      const float* tb, int32_t dT, const float* pf, int64_t ldpf, int32_t pf_dim, float* out, int64_t ldo,
+                      tgmx_stream_t stream);
+
+/* tgmx_mixer_token with one correction step on each column's mean (mean += sum(x - mean) / K): the K tokens of an all-pad sequence are
+ * identical, and the token LayerNorm of a constant column turns an error d of its mean into d / sqrt(eps) where the exact answer is 0. */
+int tgmx_tpnet_token_mix(const float* x, int64_t ldx, int64_t S, int32_t K, int32_t C, const float* tok_g, const float* tok_b,
+                         const float* w1, const float* b1, int32_t Ht, const float* w2, const float* b2, const float* ch_g,
+                         const float* ch_b, float eps, float* z1, float* y, int64_t ldo, tgmx_stream_t stream);
+
+/* out[q, :C] = mean over the k rows q k .. q k + k - 1 of z. */
+int tgmx_tpnet_mean(const float* z, int64_t ldz, int64_t Q, int32_t k, int32_t C, float* out, int64_t ldo, tgmx_stream_t stream);
+
+/* The TPNet inference forward as ONE call: tgmx_tpnet_pair_features for (neighbour, source) and (neighbour, destination), the
+ * pair-feature MLP (two GEMMs, ReLU), tgmx_tpnet_tokens, the two projection GEMMs (ReLU between), per layer tgmx_tpnet_token_mix and the
+ * channel FFN's two GEMMs, tgmx_tpnet_mean.  tables.levels = 0: no pair-feature columns.  Scratch: feat / pf [4 B k, ldf],
+ * feat_h [4 B k, ldfh], x0 [2 B k, ldx0], hp [2 B k, ldhp], z / z1 / y [2 B k, ldz], h [2 B k, ldh]; leading dimensions multiples of 4. */
+typedef struct tgmx_tpnet_fwd {
+  const float* node_x; int64_t num_nodes;
+  const int32_t *src, *dst; const int64_t* edge_time; int64_t B;                   /* the pairs */
+  const int32_t* nbr_nids; const int64_t* nbr_t; const float* nbr_x; int64_t S;    /* hop 0: [S, k], [S, k], [S, k, dE] */
+  const int32_t* rows;                                                             /* [2 B] rows of hop 0 (sources, destinations), or NULL */
+  int32_t k, dN, dE, dT, E, num_layers, rp_concat, rp_scale, rp_out_dim; float eps;
+  tgmx_tpnet_tables_t tables;
+  const float *rp_w1, *rp_b1, *rp_w2, *rp_b2;                                      /* random_projections.mlp.{0,2} */
+  const float *tw, *tb, *proj_w0, *proj_b0, *proj_w2, *proj_b2;                    /* time_encoder.w, projection_layer.{0,2} */
+  tgmx_mixer_layer_t layers[TGMX_MIXER_MAX_LAYERS];
+  float *feat, *feat_h, *pf, *x0, *hp, *z, *z1, *y, *h; int64_t ldf, ldfh, ldx0, ldhp, ldz, ldh;
+  float* out;                                                                      /* [2 B, E] */
+} tgmx_tpnet_fwd_t;
+int tgmx_tpnet_forward(const tgmx_tpnet_fwd_t* args, tgmx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

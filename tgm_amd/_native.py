@@ -419,6 +419,47 @@ SIGNATURES['tgmx_dygformer_layer'] = (
 )
 SIGNATURES['tgmx_dygformer_forward'] = (c_int32, [ctypes.POINTER(DyGFormerFwd), _P])
 
+TPNET_MAX_LEVELS = 8  # TGMX_TPNET_MAX_LEVELS
+TPNET_PAIR_MAX_LEVELS = 4  # tgmx_tpnet_pair_features' envelope (tables per side)
+TPNET_HEAD_EMPTY = 0x7F7F7F7F  # TGMX_TPNET_HEAD_EMPTY
+
+
+class TPNetTables(ctypes.Structure):
+    """tgmx_tpnet_tables_t (include/tgm_amd.h)."""
+
+    _fields_ = [('P', c_void_p * TPNET_MAX_LEVELS), ('levels', c_int32), ('dim', c_int32), ('num_nodes', c_int64)]
+
+
+class TPNetFwd(ctypes.Structure):
+    """tgmx_tpnet_fwd_t (include/tgm_amd.h)."""
+
+    _fields_ = [
+        ('node_x', c_void_p), ('num_nodes', c_int64),
+        ('src', c_void_p), ('dst', c_void_p), ('edge_time', c_void_p), ('B', c_int64),
+        ('nbr_nids', c_void_p), ('nbr_t', c_void_p), ('nbr_x', c_void_p), ('S', c_int64),
+        ('rows', c_void_p),
+        ('k', c_int32), ('dN', c_int32), ('dE', c_int32), ('dT', c_int32), ('E', c_int32), ('num_layers', c_int32), ('rp_concat', c_int32),
+        ('rp_scale', c_int32), ('rp_out_dim', c_int32), ('eps', ctypes.c_float),
+        ('tables', TPNetTables),
+        ('rp_w1', c_void_p), ('rp_b1', c_void_p), ('rp_w2', c_void_p), ('rp_b2', c_void_p),
+        ('tw', c_void_p), ('tb', c_void_p), ('proj_w0', c_void_p), ('proj_b0', c_void_p), ('proj_w2', c_void_p), ('proj_b2', c_void_p),
+        ('layers', MixerLayer * MIXER_MAX_LAYERS),
+        ('feat', c_void_p), ('feat_h', c_void_p), ('pf', c_void_p), ('x0', c_void_p), ('hp', c_void_p), ('z', c_void_p), ('z1', c_void_p),
+        ('y', c_void_p), ('h', c_void_p),
+        ('ldf', c_int64), ('ldfh', c_int64), ('ldx0', c_int64), ('ldhp', c_int64), ('ldz', c_int64), ('ldh', c_int64),
+        ('out', c_void_p),
+    ]  # fmt: skip
+
+
+SIGNATURES['tgmx_tpnet_update'] = (c_int32, [ctypes.POINTER(TPNetTables), _P, _P, _P, c_int64, ctypes.c_double, _P, c_int32, _P, _P, _P, _P])
+SIGNATURES['tgmx_tpnet_pair_features'] = (c_int32, [ctypes.POINTER(TPNetTables), _P, _P, c_int64, c_int32, _P, _P, c_int64, c_int64, c_int32, c_int32,
+                                                    _P, c_int64, _P])
+SIGNATURES['tgmx_tpnet_tokens'] = (c_int32, [_P, c_int64, c_int32, _P, c_int64, _P, _P, _P, c_int64, c_int32, c_int32, _P, _P, _P, c_int32, _P, c_int64,
+                                             c_int32, _P, c_int64, _P])
+SIGNATURES['tgmx_tpnet_token_mix'] = SIGNATURES['tgmx_mixer_token']
+SIGNATURES['tgmx_tpnet_mean'] = (c_int32, [_P, c_int64, c_int64, c_int32, c_int32, _P, c_int64, _P])
+SIGNATURES['tgmx_tpnet_forward'] = (c_int32, [ctypes.POINTER(TPNetFwd), _P])
+
 _lib: Optional[ctypes.CDLL] = None
 
 

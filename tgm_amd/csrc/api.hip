@@ -36,6 +36,8 @@ extern "C" size_t tgmx_abi_sizeof(int32_t which) {
     case 14: return sizeof(tgmx_graphmixer_fwd_t);
     case 15: return sizeof(tgmx_dygformer_layer_t);
     case 16: return sizeof(tgmx_dygformer_fwd_t);
+    case 17: return sizeof(tgmx_tpnet_tables_t);
+    case 18: return sizeof(tgmx_tpnet_fwd_t);
     default: return 0;
   }
 }

@@ -88,6 +88,10 @@ constexpr size_t kTokMaxLds = 64 * 1024;
 
 __device__ __forceinline__ float gelu_erf(float v) { return 0.5f * v * (1.f + erff(v * 0.70710678118654752f)); }
 
+// kRefine (TPNet): one correction step on the column mean, mean += sum(x - mean) / K.  The K tokens of an all-pad TPNet sequence are identical,
+// so the column is constant; an error d in its mean leaves the LayerNorm as d / sqrt(eps) = 316 d where the exact answer is 0.  With the
+// correction the mean of K equal values is that value, bit for bit.  GraphMixer keeps the plain mean (its results stay as they were).
+template <bool kRefine>
 __global__ __launch_bounds__(kTokThreads) void mixer_token_kernel(const float* __restrict__ x, long long ldx, int K, int C,
                                                                   const float* __restrict__ tg, const float* __restrict__ tbeta,
                                                                   const float* __restrict__ w1, const float* __restrict__ b1, int Ht,
@@ -110,7 +114,12 @@ __global__ __launch_bounds__(kTokThreads) void mixer_token_kernel(const float* _
       for (int k = 0; k < K; ++k) zt[k * C + c] = xs[k * ldx + c];
       float sum = 0.f;
       for (int k = 0; k < K; ++k) sum += zt[k * C + c];
-      const float mean = sum / (float)K;
+      float mean = sum / (float)K;
+      if constexpr (kRefine) {
+        float rest = 0.f;
+        for (int k = 0; k < K; ++k) rest += zt[k * C + c] - mean;
+        mean += rest / (float)K;
+      }
       float var = 0.f;
       for (int k = 0; k < K; ++k) {
         const float d = zt[k * C + c] - mean;
@@ -269,9 +278,9 @@ extern "C" int tgmx_mixer_prologue(const float* edge_x, const int64_t* seed_t, c
   return TGMX_OK;
 }
 
-extern "C" int tgmx_mixer_token(const float* x, int64_t ldx, int64_t S, int32_t K, int32_t C, const float* tok_g, const float* tok_b,
-                                const float* w1, const float* b1, int32_t Ht, const float* w2, const float* b2, const float* ch_g,
-                                const float* ch_b, float eps, float* z1, float* y, int64_t ldo, tgmx_stream_t stream) {
+static int mixer_token_run(bool refine, const float* x, int64_t ldx, int64_t S, int32_t K, int32_t C, const float* tok_g, const float* tok_b,
+                           const float* w1, const float* b1, int32_t Ht, const float* w2, const float* b2, const float* ch_g, const float* ch_b,
+                           float eps, float* z1, float* y, int64_t ldo, tgmx_stream_t stream) {
   TGMX_REQUIRE(S >= 0 && K > 0 && C > 0 && Ht >= 0 && ldx >= C && ldo >= C, "mixer_token: bad sizes S=%lld K=%d C=%d Ht=%d", (long long)S, K, C, Ht);
   if (S == 0) return TGMX_OK;
   TGMX_REQUIRE(x && tok_g && tok_b && (Ht == 0 || (w1 && b1 && w2)) && b2 && ch_g && ch_b && z1 && y, "mixer_token: null pointer");
@@ -280,10 +289,26 @@ extern "C" int tgmx_mixer_token(const float* x, int64_t ldx, int64_t S, int32_t 
     set_error("mixer_token: K=%d tokens x C=%d channels (token hidden %d) need %zu bytes of LDS per seed, more than %zu", K, C, Ht, lds, kTokMaxLds);
     return TGMX_E_UNSUPPORTED;
   }
-  hipLaunchKernelGGL(mixer_token_kernel, dim3((unsigned)S), dim3(kTokThreads), lds, (hipStream_t)stream, x, (long long)ldx, K, C, tok_g, tok_b,
-                     w1, b1, Ht, w2, b2, ch_g, ch_b, eps, z1, y, (long long)ldo);
+  if (refine)
+    hipLaunchKernelGGL(mixer_token_kernel<true>, dim3((unsigned)S), dim3(kTokThreads), lds, (hipStream_t)stream, x, (long long)ldx, K, C, tok_g,
+                       tok_b, w1, b1, Ht, w2, b2, ch_g, ch_b, eps, z1, y, (long long)ldo);
+  else
+    hipLaunchKernelGGL(mixer_token_kernel<false>, dim3((unsigned)S), dim3(kTokThreads), lds, (hipStream_t)stream, x, (long long)ldx, K, C, tok_g,
+                       tok_b, w1, b1, Ht, w2, b2, ch_g, ch_b, eps, z1, y, (long long)ldo);
   TGMX_CHECK_LAUNCH("mixer_token");
   return TGMX_OK;
+}
+
+extern "C" int tgmx_mixer_token(const float* x, int64_t ldx, int64_t S, int32_t K, int32_t C, const float* tok_g, const float* tok_b,
+                                const float* w1, const float* b1, int32_t Ht, const float* w2, const float* b2, const float* ch_g,
+                                const float* ch_b, float eps, float* z1, float* y, int64_t ldo, tgmx_stream_t stream) {
+  return mixer_token_run(false, x, ldx, S, K, C, tok_g, tok_b, w1, b1, Ht, w2, b2, ch_g, ch_b, eps, z1, y, ldo, stream);
+}
+
+extern "C" int tgmx_tpnet_token_mix(const float* x, int64_t ldx, int64_t S, int32_t K, int32_t C, const float* tok_g, const float* tok_b,
+                                    const float* w1, const float* b1, int32_t Ht, const float* w2, const float* b2, const float* ch_g,
+                                    const float* ch_b, float eps, float* z1, float* y, int64_t ldo, tgmx_stream_t stream) {
+  return mixer_token_run(true, x, ldx, S, K, C, tok_g, tok_b, w1, b1, Ht, w2, b2, ch_g, ch_b, eps, z1, y, ldo, stream);
 }
 
 extern "C" int tgmx_mixer_tail(const float* z, int64_t ldz, int64_t S, int32_t K, int32_t C, const int32_t* nbr_nids, const float* node_x,

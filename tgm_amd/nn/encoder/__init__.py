@@ -3,13 +3,14 @@
 them.  The submodule names resolve to the modules that hold the implementations -- nothing is defined here."""
 import sys
 
-from .. import dygformer, tgat, tgcn, tgn
+from .. import dygformer, tgat, tgcn, tgn, tpnet
 from ..dygformer import DyGFormer
 from ..tgat import TGAT
 from ..tgcn import TGCN
+from ..tpnet import RandomProjectionModule, TPNet
 from ..tgn import GraphAttentionEmbedding, IdentityMessage, LastAggregator, MeanAggregator, TGNMemory
 
-for _m in (dygformer, tgat, tgcn, tgn):
+for _m in (dygformer, tgat, tgcn, tgn, tpnet):
     sys.modules[f'{__name__}.{_m.__name__.rsplit(".", 1)[1]}'] = _m
 
-__all__ = ['DyGFormer', 'GraphAttentionEmbedding', 'IdentityMessage', 'LastAggregator', 'MeanAggregator', 'TGAT', 'TGCN', 'TGNMemory']
+__all__ = ['DyGFormer', 'GraphAttentionEmbedding', 'IdentityMessage', 'LastAggregator', 'MeanAggregator', 'RandomProjectionModule', 'TGAT', 'TGCN', 'TGNMemory', 'TPNet']
