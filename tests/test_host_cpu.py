@@ -479,3 +479,58 @@ def test_splits_are_contiguous_ranges_equal_to_the_mask_formulation():
     assert a.edge_index.shape[0] + b.edge_index.shape[0] + c.edge_index.shape[0] == E and int(b.time[b.edge_mask.long()].min()) >= 100
     with pytest.raises(ValueError, match='Cannot override'):
         data.split(TemporalRatioSplit())
+
+
+def test_forward_plumbing_scratch_carver():
+    """One buffer per owner: regrown when too small or on another device, never empty, the views 256-byte granules that do not overlap."""
+    from tgm_amd.nn._fwd_plumbing import carve_scratch
+
+    owner = torch.nn.Linear(1, 1)
+    cpu, meta = torch.device('cpu'), torch.device('meta')
+    views = carve_scratch(owner, [5, 0, 64, 65], cpu)
+    ws = owner.__dict__['_tgmx_ws']
+    assert [v.numel() for v in views] == [64, 0, 64, 128] and ws.numel() == 256 and ws.dtype == torch.float32
+    offs = [v.storage_offset() for v in views]
+    assert all(v.untyped_storage().data_ptr() == ws.untyped_storage().data_ptr() for v in views)
+    assert offs[0] == 0 and all(o % 64 == 0 for o in offs)
+    spans = sorted((o, o + v.numel()) for o, v in zip(offs, views) if v.numel())
+    assert all(a[1] <= b[0] for a, b in zip(spans, spans[1:])) and spans[-1][1] <= ws.numel()
+    for i, v in enumerate(views):  # a write through one view reaches no other
+        v.fill_(float(i))
+    assert all(bool((v == float(i)).all()) for i, v in enumerate(views))
+    assert carve_scratch(owner, [64, 64], cpu)[1].data_ptr() == ws.data_ptr() + 256 and owner.__dict__['_tgmx_ws'] is ws  # smaller: kept
+    carve_scratch(owner, [300], cpu)
+    grown = owner.__dict__['_tgmx_ws']
+    assert grown is not ws and grown.numel() == 320  # too small: regrown
+    moved = carve_scratch(owner, [10], meta)
+    assert owner.__dict__['_tgmx_ws'] is not grown and moved[0].device == meta and owner.__dict__['_tgmx_ws'].numel() == 64  # other device
+    fresh = torch.nn.Linear(1, 1)
+    empty = carve_scratch(fresh, [0, 0], cpu)
+    assert [v.numel() for v in empty] == [0, 0] and fresh.__dict__['_tgmx_ws'].numel() == 1  # never a zero-element allocation
+
+
+def test_forward_plumbing_needs_torch_truth_table():
+    from tgm_amd.nn import MLPMixer, TPNet
+    from tgm_amd.nn._fwd_plumbing import needs_torch, up4
+
+    assert [up4(n) for n in (0, 1, 4, 5)] == [0, 4, 4, 8]
+    x, xg = torch.zeros(2), torch.zeros(2, requires_grad=True)
+    for m in (MLPMixer(4, 3, dropout=0.1), TPNet(4, 3, 6, 8, 5)):  # module.parameters() / the cached list of a TransientCaches module
+        frozen = [p.requires_grad_(False) for p in m.parameters()]
+        m.eval()
+        assert not needs_torch(m, 0.1, x) and needs_torch(m, 0.1, x, xg) and not needs_torch(m, 0.0)
+        with torch.no_grad():
+            assert not needs_torch(m, 0.1, x, xg)
+        m.train()
+        assert needs_torch(m, 0.1, x) and not needs_torch(m, 0.0, x)  # dropout is active only in train mode with p > 0
+        with torch.no_grad():
+            assert needs_torch(m, 0.1, x) and not needs_torch(m, 0.0, x, xg)
+        m.eval()
+        frozen[-1].requires_grad_(True)
+        assert needs_torch(m, 0.0, x)  # one trainable parameter is enough
+        with torch.no_grad():
+            assert not needs_torch(m, 0.0, x)
+    # a plain nn.Module keeps no parameter-list cache behind (nothing would strip it on pickle / deepcopy)
+    m = MLPMixer(4, 3)
+    needs_torch(m, 0.0, x)
+    assert not any(k.startswith('_tgmx_') for k in m.__dict__)

@@ -321,6 +321,12 @@ struct GemmCall {
   int relu, batch;
   long long sA, sB, sC;
 };
+
+// num_layers MLPMixer layers on z [S K, ldz] in place (csrc/mixer.hip): per layer the token block (z -> z1, y; refine: TPNet's corrected column
+// mean), then the channel FFN as two GEMMs (y -> h with GELU, h -> z with the residual z1).  The loop of tgmx_graphmixer_forward and
+// tgmx_tpnet_forward.
+int mixer_layers_run(bool refine, const tgmx_mixer_layer_t* layers, int num_layers, int64_t S, int32_t K, int32_t C, float eps, float* z, float* z1,
+                     float* y, int64_t ldz, float* h, int64_t ldh, tgmx_stream_t stream);
 }  // namespace tgmx
 // two independent GEMMs as one launch (bit for bit what two tgmx_sgemm_nt calls give; falls back to them when either problem would not
 // take the K-split kernel on its own)

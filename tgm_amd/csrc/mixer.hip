@@ -299,6 +299,21 @@ static int mixer_token_run(bool refine, const float* x, int64_t ldx, int64_t S, 
   return TGMX_OK;
 }
 
+int tgmx::mixer_layers_run(bool refine, const tgmx_mixer_layer_t* layers, int num_layers, int64_t S, int32_t K, int32_t C, float eps, float* z,
+                           float* z1, float* y, int64_t ldz, float* h, int64_t ldh, tgmx_stream_t stream) {
+  const long long R = (long long)S * K;
+  int rc;
+  for (int l = 0; l < num_layers; ++l) {
+    const tgmx_mixer_layer_t& ly = layers[l];
+    if ((rc = mixer_token_run(refine, z, ldz, S, K, C, ly.tok_g, ly.tok_b, ly.tok_w1, ly.tok_b1, ly.tok_hidden, ly.tok_w2, ly.tok_b2, ly.ch_g, ly.ch_b,
+                              eps, z1, y, ldz, stream)))
+      return rc;
+    if ((rc = tgmx_sgemm_nt_ep(y, ldz, ly.ch_w1, C, h, ldh, R, ly.ch_hidden, C, ly.ch_b1, 2, nullptr, 0, stream))) return rc;
+    if ((rc = tgmx_sgemm_nt_ep(h, ldh, ly.ch_w2, ly.ch_hidden, z, ldz, R, C, ly.ch_hidden, ly.ch_b2, 0, z1, ldz, stream))) return rc;
+  }
+  return TGMX_OK;
+}
+
 extern "C" int tgmx_mixer_token(const float* x, int64_t ldx, int64_t S, int32_t K, int32_t C, const float* tok_g, const float* tok_b,
                                 const float* w1, const float* b1, int32_t Ht, const float* w2, const float* b2, const float* ch_g,
                                 const float* ch_b, float eps, float* z1, float* y, int64_t ldo, tgmx_stream_t stream) {
@@ -336,14 +351,7 @@ extern "C" int tgmx_graphmixer_forward(const tgmx_graphmixer_fwd_t* a, tgmx_stre
   int rc;
   if ((rc = tgmx_mixer_prologue(a->nbr_edge_x, a->seed_t, a->nbr_t, S, a->K, D, a->tw, a->tb, T, a->x0, a->ldx0, stream))) return rc;
   if ((rc = tgmx_sgemm_nt_ep(a->x0, a->ldx0, a->proj_w, D + T, a->z, a->ldz, R, D, D + T, a->proj_b, 0, nullptr, 0, stream))) return rc;
-  for (int l = 0; l < a->num_layers; ++l) {
-    const tgmx_mixer_layer_t& ly = a->layers[l];
-    if ((rc = tgmx_mixer_token(a->z, a->ldz, S, a->K, D, ly.tok_g, ly.tok_b, ly.tok_w1, ly.tok_b1, ly.tok_hidden, ly.tok_w2, ly.tok_b2, ly.ch_g,
-                               ly.ch_b, a->eps, a->z1, a->y, a->ldz, stream)))
-      return rc;
-    if ((rc = tgmx_sgemm_nt_ep(a->y, a->ldz, ly.ch_w1, D, a->h, a->ldh, R, ly.ch_hidden, D, ly.ch_b1, 2, nullptr, 0, stream))) return rc;
-    if ((rc = tgmx_sgemm_nt_ep(a->h, a->ldh, ly.ch_w2, ly.ch_hidden, a->z, a->ldz, R, D, ly.ch_hidden, ly.ch_b2, 0, a->z1, a->ldz, stream))) return rc;
-  }
+  if ((rc = mixer_layers_run(false, a->layers, a->num_layers, S, a->K, D, a->eps, a->z, a->z1, a->y, a->ldz, a->h, a->ldh, stream))) return rc;
   if ((rc = tgmx_mixer_tail(a->z, a->ldz, S, a->K, D, a->nbr_nids, a->node_x, a->num_nodes, a->F, a->tg_nbr, a->tg_lo, a->tg_cnt, a->seeds[0],
                             a->n_seeds[0], a->seeds[1], a->n_seeds[1], a->seeds[2], a->cat, a->ldcat, stream)))
     return rc;

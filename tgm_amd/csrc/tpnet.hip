@@ -373,13 +373,6 @@ extern "C" int tgmx_tpnet_forward(const tgmx_tpnet_fwd_t* a, tgmx_stream_t strea
   if ((rc = tgmx_sgemm_nt_ep(a->x0, a->ldx0, a->proj_w0, W, a->hp, a->ldhp, R, 2 * E, W, a->proj_b0, 1, nullptr, 0, stream))) return rc;
   // (the reference's masked_fill after the projection discards its result: pad tokens stay as projected)
   if ((rc = tgmx_sgemm_nt_ep(a->hp, a->ldhp, a->proj_w2, 2 * E, a->z, a->ldz, R, E, 2 * E, a->proj_b2, 0, nullptr, 0, stream))) return rc;
-  for (int l = 0; l < a->num_layers; ++l) {
-    const tgmx_mixer_layer_t& ly = a->layers[l];
-    if ((rc = tgmx_tpnet_token_mix(a->z, a->ldz, Q, a->k, E, ly.tok_g, ly.tok_b, ly.tok_w1, ly.tok_b1, ly.tok_hidden, ly.tok_w2, ly.tok_b2, ly.ch_g,
-                               ly.ch_b, a->eps, a->z1, a->y, a->ldz, stream)))
-      return rc;
-    if ((rc = tgmx_sgemm_nt_ep(a->y, a->ldz, ly.ch_w1, E, a->h, a->ldh, R, ly.ch_hidden, E, ly.ch_b1, 2, nullptr, 0, stream))) return rc;
-    if ((rc = tgmx_sgemm_nt_ep(a->h, a->ldh, ly.ch_w2, ly.ch_hidden, a->z, a->ldz, R, E, ly.ch_hidden, ly.ch_b2, 0, a->z1, a->ldz, stream))) return rc;
-  }
+  if ((rc = mixer_layers_run(true, a->layers, a->num_layers, Q, a->k, E, a->eps, a->z, a->z1, a->y, a->ldz, a->h, a->ldh, stream))) return rc;
   return tgmx_tpnet_mean(a->z, a->ldz, Q, a->k, E, a->out, E, stream);
 }

@@ -1,4 +1,5 @@
-"""Thin typed wrappers over the TGAT entry points of libtgm_amd.so (forward only)."""
+"""Thin typed wrappers every encoder shares: the contiguous-float32 conversion of an input on the device (``_f32c``) and the
+``tgmx_time2vec``, ``tgmx_gather_rows`` and ``tgmx_sgemm_nt`` entry points of libtgm_amd.so."""
 from __future__ import annotations
 
 from typing import Optional

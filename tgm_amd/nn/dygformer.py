@@ -35,31 +35,9 @@ from torch import Tensor
 
 from .. import _native
 from ..constants import PADDED_NODE_ID
-from . import _ops
-from ._paramver import TransientCaches, param_key
+from ._fwd_plumbing import Unsupported, cached_block, carve_scratch, check_supported, i32, i64, needs_torch, pair_inputs, up4, weight_keeper
+from ._paramver import TransientCaches
 from .time_encoding import Time2Vec
-
-_up4 = lambda n: (n + 3) // 4 * 4
-_i32 = lambda t: t if (t.dtype == torch.int32 and t.is_contiguous()) else t.to(torch.int32).contiguous()
-_i64 = lambda t: t if (t.dtype == torch.int64 and t.is_contiguous()) else t.to(torch.int64).contiguous()
-
-
-def _needs_torch(module: nn.Module, dropout: float, *inputs: Tensor) -> bool:
-    """The composed torch path: autograd has something to track, or dropout is active."""
-    if module.training and dropout > 0:
-        return True
-    return torch.is_grad_enabled() and (any(t.requires_grad for t in inputs) or any(p.requires_grad for p in module.parameters()))
-
-
-class _Unsupported(RuntimeError):
-    """A native entry point answered TGMX_E_UNSUPPORTED: the caller takes the composed path."""
-
-
-def _check(rc: int, what: str) -> None:
-    if rc == _native.E_UNSUPPORTED:
-        msg = _native.load().tgmx_last_error()
-        raise _Unsupported(f'{what}: {msg.decode() if msg else "unsupported"}')
-    _native.check(rc, what)
 
 
 def _cooccurrence(enc: Optional['NeighborCooccurrenceEncoder'], src: Tensor, dst: Tensor, nids: Tensor, src_rows: Optional[Tensor],
@@ -92,7 +70,7 @@ class NeighborCooccurrenceEncoder(nn.Module):
             raise ValueError(f'expected two [P, L] id matrices of one shape, got {list(src_ids.shape)} and {list(dst_ids.shape)}')
         if src_ids.shape[1] > _native.DYGFORMER_MAX_SEQ:
             raise NotImplementedError(f'tgm_amd NeighborCooccurrenceEncoder: at most {_native.DYGFORMER_MAX_SEQ} slots per sequence')
-        s, d = _i32(src_ids), _i32(dst_ids)
+        s, d = i32(src_ids), i32(dst_ids)
         return s[:, 0].contiguous(), d[:, 0].contiguous(), torch.cat([s[:, 1:], d[:, 1:]], dim=0).contiguous()
 
     def _count_nodes_freq(self, src_nbrs: Tensor, dst_nbrs: Tensor) -> Tuple[Tensor, Tensor]:
@@ -107,8 +85,8 @@ class NeighborCooccurrenceEncoder(nn.Module):
     def forward(self, src_neighbour_nodes_ids: Tensor, dst_neighbour_nodes_ids: Tensor) -> Tuple[Tensor, Tensor]:
         src, dst, nids = self._split(src_neighbour_nodes_ids, dst_neighbour_nodes_ids)
         P, L = src_neighbour_nodes_ids.shape
-        if _needs_torch(self, 0.0):
-            return self._torch_forward(_i64(src_neighbour_nodes_ids), _i64(dst_neighbour_nodes_ids))  # training: torch ops (not native)
+        if needs_torch(self, 0.0):
+            return self._torch_forward(i64(src_neighbour_nodes_ids), i64(dst_neighbour_nodes_ids))  # training: torch ops (not native)
         C = self.feat_dim
         feat = torch.empty((P, 2, L, C), dtype=torch.float32, device=src.device)
         if P:
@@ -127,7 +105,7 @@ class NeighborCooccurrenceEncoder(nn.Module):
         return out[0], out[1]
 
 
-def _layer_block(t: 'TransformerEncoder', keep: Optional[list] = None) -> '_native.DyGFormerLayer':
+def _layer_block(t: 'TransformerEncoder', f32: Callable[..., int]) -> '_native.DyGFormerLayer':
     mha, ln, lin = t.multi_head_attention, t.norm_layers, t.linear_layers
     if mha.in_proj_weight is None or mha.in_proj_bias is None or mha.bias_k is not None or mha.batch_first:
         raise NotImplementedError('tgm_amd TransformerEncoder: the native layer needs the packed in-projection with bias')
@@ -136,19 +114,16 @@ def _layer_block(t: 'TransformerEncoder', keep: Optional[list] = None) -> '_nati
     tensors = (ln[0].weight, ln[0].bias, mha.in_proj_weight, mha.in_proj_bias, mha.out_proj.weight, mha.out_proj.bias, ln[1].weight, ln[1].bias,
                lin[0].weight, lin[0].bias, lin[1].weight, lin[1].bias)  # fmt: skip
     for n, p in zip(names, tensors):
-        v = _ops._f32c(p.detach(), n)
-        if keep is not None:
-            keep.append(v)
-        setattr(ly, n, v.data_ptr())
+        setattr(ly, n, f32(p, n))
     return ly
 
 
 def _native_layer(t: 'TransformerEncoder', B: int, T: int, x: Tensor, y: Tensor, x1: Tensor, att: Tensor, ldx: int, qkv: Tensor, ldq: int, h: Tensor,
                   ldh: int) -> None:  # fmt: skip
     """``tgmx_dygformer_layer`` on x [B T, ldx], in place."""
-    keep: list = []
-    ly = _layer_block(t, keep)
-    _check(
+    keep, f32 = weight_keeper()  # (keep: the converted weights outlive the launch)
+    ly = _layer_block(t, f32)
+    check_supported(
         _native.load().tgmx_dygformer_layer(ctypes.byref(ly), B, T, t.num_heads, t.attention_dim, float(t.norm_layers[0].eps), x.data_ptr(), y.data_ptr(),
                                             x1.data_ptr(), att.data_ptr(), ldx, qkv.data_ptr(), ldq, h.data_ptr(), ldh, _native.stream_ptr()),
         'tgmx_dygformer_layer',
@@ -188,18 +163,18 @@ class TransformerEncoder(nn.Module):
         if inputs.dim() != 3 or inputs.shape[2] != self.attention_dim:
             raise ValueError(f'TransformerEncoder expects [B, T, {self.attention_dim}], got {list(inputs.shape)}')
         B, T, D = inputs.shape
-        if _needs_torch(self, self.dropout_rate, inputs) or not _mha_in_envelope(T, D, self.num_heads) or B * T == 0:
+        if needs_torch(self, self.dropout_rate, inputs) or not _mha_in_envelope(T, D, self.num_heads) or B * T == 0:
             return self._torch_forward(inputs)
         self._check_native()
-        ldx = _up4(D)
+        ldx = up4(D)
         f32 = dict(dtype=torch.float32, device=inputs.device)
         x = torch.zeros((B * T, ldx), **f32)
         x[:, :D] = inputs.reshape(B * T, D)
         y, x1, att = (torch.empty((B * T, ldx), **f32) for _ in range(3))
-        qkv, h = torch.empty((B * T, _up4(3 * D)), **f32), torch.empty((B * T, 4 * D), **f32)
+        qkv, h = torch.empty((B * T, up4(3 * D)), **f32), torch.empty((B * T, 4 * D), **f32)
         try:
-            _native_layer(self, B, T, x, y, x1, att, ldx, qkv, _up4(3 * D), h, 4 * D)
-        except _Unsupported:  # the device cannot give tgmx_mha_small its LDS: compose
+            _native_layer(self, B, T, x, y, x1, att, ldx, qkv, up4(3 * D), h, 4 * D)
+        except Unsupported:  # the device cannot give tgmx_mha_small its LDS: compose
             return self._torch_forward(inputs)
         return x[:, :D].reshape(B, T, D)
 
@@ -232,33 +207,15 @@ class DyGFormer(TransientCaches, nn.Module):
         self.output_layer = nn.Linear(num_channels * channel_embedding_dim, output_dim).to(device)
 
     # -- inputs ------------------------------------------------------------------------------------------------------------------------
-    def _inputs(self, node_x, src, dst, edge_time, nids, nbr_t, nbr_x, src_rows, dst_rows) -> dict:
-        if nids.dim() != 2 or nbr_x.dim() != 3 or tuple(nbr_t.shape) != tuple(nids.shape) or tuple(nbr_x.shape[:2]) != tuple(nids.shape):
-            raise ValueError(f'expected neighbour ids / times [S, k] and edge features [S, k, d], got {list(nids.shape)}, {list(nbr_t.shape)}, {list(nbr_x.shape)}')
-        L = 1 + nids.shape[1]
-        if L != self.max_input_sequence_length:
-            raise ValueError(f'a sequence is the seed plus its k = {nids.shape[1]} sampled neighbours: L = {L} slots, which must equal '
+    def _check_slots(self, k: int) -> None:
+        if 1 + k != self.max_input_sequence_length:
+            raise ValueError(f'a sequence is the seed plus its k = {k} sampled neighbours: L = {1 + k} slots, which must equal '
                              f'max_input_sequence_length = {self.max_input_sequence_length} (sample max_input_sequence_length - 1 neighbours)')
-        if nbr_x.shape[2] != self.edge_x_dim or node_x.dim() != 2 or node_x.shape[1] != self.node_feat_dim:
-            raise ValueError(f'expected node_x [N, {self.node_feat_dim}] and edge features of width {self.edge_x_dim}, got {list(node_x.shape)} and '
-                             f'{list(nbr_x.shape)}')
-        for name, t in (('node_x', node_x), ('src', src), ('dst', dst), ('edge_time', edge_time), ('neighbours', nids), ('neighbours_time', nbr_t),
-                        ('neighbours_edge_feat', nbr_x)):  # fmt: skip
-            _native.require_device(t, name)
-        P = src.numel()
-        if dst.numel() != P or edge_time.numel() != P:
-            raise ValueError('src, dst and edge_time must have one entry per pair')
-        if src_rows is None:
-            if nids.shape[0] < 2 * P:
-                raise ValueError(f'{P} pairs need neighbour rows [:P] for the sources and [P:2P] for the destinations, got {nids.shape[0]} rows')
-        else:
-            _native.require_device(src_rows, 'src_rows')
-            _native.require_device(dst_rows, 'dst_rows')
-            if src_rows.numel() != P or dst_rows.numel() != P:
-                raise ValueError('src_rows and dst_rows must have one entry per pair')
-            src_rows, dst_rows = _i32(src_rows.reshape(-1)), _i32(dst_rows.reshape(-1))
-        return dict(node_x=_ops._f32c(node_x, 'node_x'), src=_i32(src.reshape(-1)), dst=_i32(dst.reshape(-1)), t=_i64(edge_time.reshape(-1)),
-                    nids=_i32(nids), nbr_t=_i64(nbr_t), nbr_x=_ops._f32c(nbr_x, 'neighbours_edge_feat'), src_rows=src_rows, dst_rows=dst_rows, P=P, L=L)  # fmt: skip
+
+    def _inputs(self, *tensors) -> dict:
+        """(node_x, src, dst, edge_time, nids, nbr_t, nbr_x, src_rows, dst_rows), checked and converted."""
+        a = pair_inputs(*tensors, self.node_feat_dim, self.edge_x_dim, self._check_slots, 'P')
+        return dict(a, P=a['src'].numel(), L=1 + a['nids'].shape[1])
 
     def forward(self, node_x: Tensor, edge_index: Tensor, edge_time: Tensor, neighbours: Tensor, neighbours_time: Tensor,
                 neighbours_edge_feat: Tensor) -> Tuple[Tensor, Tensor]:  # fmt: skip
@@ -276,7 +233,7 @@ class DyGFormer(TransientCaches, nn.Module):
 
     def _run(self, a: dict) -> Tuple[Tensor, Tensor]:
         grad_inputs = (a['node_x'], a['nbr_x'])
-        if _needs_torch(self, self.dropout, *grad_inputs) or not self._native_ok(a['L']):
+        if needs_torch(self, self.dropout, *grad_inputs) or not self._native_ok(a['L']):
             return self._torch_forward(a)
         for t in self.transformers:
             t._check_native()
@@ -288,7 +245,7 @@ class DyGFormer(TransientCaches, nn.Module):
                     self._forward_launches(a, out)
                 else:
                     self._forward_native(a, out)
-            except _Unsupported:  # the device cannot give tgmx_mha_small its LDS: compose
+            except Unsupported:  # the device cannot give tgmx_mha_small its LDS: compose
                 return self._torch_forward(a)
         return out[:P], out[P:]
 
@@ -321,31 +278,19 @@ class DyGFormer(TransientCaches, nn.Module):
     def _dims(self) -> dict:
         C = self.channel_embedding_dim
         D = 4 * C
-        return dict(ldch=[_up4(self.node_feat_dim), _up4(self.edge_x_dim), _up4(self.time_feat_dim), _up4(C)], ldx=_up4(D), ldq=_up4(3 * D), ldh=4 * D)
+        return dict(ldch=[up4(self.node_feat_dim), up4(self.edge_x_dim), up4(self.time_feat_dim), up4(C)], ldx=up4(D), ldq=up4(3 * D), ldh=4 * D)
 
     def _scratch(self, P: int, L: int, device) -> List[Tensor]:
-        """table, ch[0..3], x, y, x1, att, qkv, h, mean: views into one buffer kept between batches (each region 256-byte aligned)."""
+        """table, ch[0..3], x, y, x1, att, qkv, h, mean: views into one buffer kept between batches."""
         d = self._dims()
         R = 2 * P * self.num_patches
-        up = lambda n: (n + 63) // 64 * 64
-        sizes = [up((L + 1) * self.channel_embedding_dim)] + [up(2 * P * L * ld) for ld in d['ldch']] + [up(R * d['ldx'])] * 4
-        sizes += [up(R * d['ldq']), up(R * d['ldh']), up(2 * P * d['ldx'])]
-        ws = self.__dict__.get('_tgmx_ws')
-        if ws is None or ws.numel() < sum(sizes) or ws.device != device:
-            ws = self.__dict__['_tgmx_ws'] = torch.empty(sum(sizes), dtype=torch.float32, device=device)
-        out, off = [], 0
-        for n in sizes:
-            out.append(ws.narrow(0, off, n))
-            off += n
-        return out
+        sizes = [(L + 1) * self.channel_embedding_dim] + [2 * P * L * ld for ld in d['ldch']] + [R * d['ldx']] * 4
+        return carve_scratch(self, sizes + [R * d['ldq'], R * d['ldh'], 2 * P * d['ldx']], device)
 
     def _weights(self) -> tuple:
         """(argument block with the weights filled in, the tensors it points at), cached against the parameters' versions."""
-        d = self.__dict__
-        key = param_key(self)
-        if d.get('_tgmx_wkey') != key:
-            keep: list = []
-            f32 = lambda t: keep.append(_ops._f32c(t.detach(), 'weight')) or keep[-1].data_ptr()
+
+        def build(f32) -> '_native.DyGFormerFwd':
             blk = _native.DyGFormerFwd()
             tw, co = self.time_encoder.w, self.co_occurrence_encoder.neighbor_co_occurrence_encoder
             blk.tw, blk.tb = f32(tw.weight.reshape(-1)), f32(tw.bias)
@@ -355,7 +300,7 @@ class DyGFormer(TransientCaches, nn.Module):
             for c, (n, dc) in enumerate(zip(self.CHANNELS, dims)):
                 w = self.projection_layer[n].weight.detach()
                 if dc % 4:  # each slot's columns padded to the channel input's leading dimension (zeros)
-                    w = F.pad(w.reshape(C, ps, dc), (0, _up4(dc) - dc)).reshape(C, ps * _up4(dc))
+                    w = F.pad(w.reshape(C, ps, dc), (0, up4(dc) - dc)).reshape(C, ps * up4(dc))
                 blk.proj_w[c], blk.proj_b[c] = f32(w), f32(self.projection_layer[n].bias)
             blk.out_w, blk.out_b = f32(self.output_layer.weight), f32(self.output_layer.bias)
             blk.num_layers = self.num_layers
@@ -364,12 +309,12 @@ class DyGFormer(TransientCaches, nn.Module):
             for i, t in enumerate(self.transformers):
                 if float(t.norm_layers[0].eps) != eps:
                     raise NotImplementedError('tgm_amd DyGFormer: the native forward takes one LayerNorm eps for every layer')
-                blk.layers[i] = _layer_block(t, keep)
+                blk.layers[i] = _layer_block(t, f32)
             blk.k, blk.dN, blk.dE, blk.dT = self.max_input_sequence_length - 1, self.node_feat_dim, self.edge_x_dim, self.time_feat_dim
             blk.C, blk.patch, blk.heads, blk.E = C, ps, self.num_heads, self.output_dim
-            d['_tgmx_w'] = (blk, keep)
-            d['_tgmx_wkey'] = key
-        return d['_tgmx_w']
+            return blk
+
+        return cached_block(self, build)
 
     def _forward_native(self, a: dict, out: Tensor) -> None:
         blk, _ = self._weights()
@@ -386,7 +331,7 @@ class DyGFormer(TransientCaches, nn.Module):
         blk.x, blk.y, blk.x1, blk.att, blk.qkv, blk.h, blk.mean = (b.data_ptr() for b in bufs[5:12])
         blk.ldx, blk.ldq, blk.ldh = d['ldx'], d['ldq'], d['ldh']
         blk.out = out.data_ptr()
-        _check(_native.load().tgmx_dygformer_forward(ctypes.byref(blk), _native.stream_ptr()), 'tgmx_dygformer_forward')
+        check_supported(_native.load().tgmx_dygformer_forward(ctypes.byref(blk), _native.stream_ptr()), 'tgmx_dygformer_forward')
 
     def _forward_launches(self, a: dict, out: Tensor) -> None:
         """The native forward's launches one ctypes call each (the A/B and test twin of ``_forward_native``)."""

@@ -28,11 +28,10 @@ from torch import Tensor
 from .. import _native
 from ..constants import PADDED_NODE_ID
 from . import _ops
-from ._paramver import TransientCaches, param_key
+from ._fwd_plumbing import cached_block, carve_scratch, fill_mixer_layers, i32, i64, needs_torch, up4
+from ._paramver import TransientCaches
 from .mlp_mixer import MLPMixer, sgemm_ep, token_block
 from .time_encoding import Time2Vec
-
-_up4 = lambda n: (n + 3) // 4 * 4
 
 
 class GraphMixerEncoder(TransientCaches, nn.Module):
@@ -71,8 +70,6 @@ class GraphMixerEncoder(TransientCaches, nn.Module):
             if getattr(batch, name, None) is None:
                 raise ValueError(f'GraphMixerEncoder needs batch.{name}')
             _native.require_device(getattr(batch, name), f'batch.{name}')
-        i32 = lambda t: t if (t.dtype == torch.int32 and t.is_contiguous()) else t.to(torch.int32).contiguous()
-        i64 = lambda t: t if (t.dtype == torch.int64 and t.is_contiguous()) else t.to(torch.int64).contiguous()
         ex = _ops._f32c(batch.nbr_edge_x[0], 'nbr_edge_x')
         seeds = [i32(batch.edge_src), i32(batch.edge_dst), i32(batch.neg)]
         S = sum(t.numel() for t in seeds)
@@ -91,8 +88,7 @@ class GraphMixerEncoder(TransientCaches, nn.Module):
 
     def forward(self, batch: Any, node_feat: Tensor) -> Tensor:
         a = self._inputs(batch, node_feat)
-        grad = torch.is_grad_enabled() and (node_feat.requires_grad or a['ex'].requires_grad or any(p.requires_grad for p in self.parameters()))
-        if grad or (self.training and self.dropout > 0):
+        if needs_torch(self, self.dropout, node_feat, a['ex']):
             return self._torch_forward(a)
         for m in self.mlp_mixers:
             m._check_native()
@@ -123,22 +119,13 @@ class GraphMixerEncoder(TransientCaches, nn.Module):
     def _dims(self, S: int) -> dict:
         K, D, T, F_ = self.num_tokens, self.edge_dim, self.time_dim, self.node_dim
         Hc = max(m.channel_feedforward.ffn[0].out_features for m in self.mlp_mixers) if self.num_layers else 4
-        return dict(R=S * K, ldx0=_up4(D + T), ldz=_up4(D), ldh=_up4(Hc), ldcat=_up4(D + F_))
+        return dict(R=S * K, ldx0=up4(D + T), ldz=up4(D), ldh=up4(Hc), ldcat=up4(D + F_))
 
     def _scratch(self, S: int, device) -> List[Tensor]:
-        """x0, z, z1, y, h, cat: views into one buffer kept between batches (each region 256-byte aligned)."""
+        """x0, z, z1, y, h, cat: views into one buffer kept between batches."""
         d = self._dims(S)
         R = d['R']
-        up = lambda n: (n + 63) // 64 * 64
-        sizes = [up(R * d['ldx0']), up(R * d['ldz']), up(R * d['ldz']), up(R * d['ldz']), up(R * d['ldh']), up(S * d['ldcat'])]
-        ws = self.__dict__.get('_tgmx_ws')
-        if ws is None or ws.numel() < sum(sizes) or ws.device != device:
-            ws = self.__dict__['_tgmx_ws'] = torch.empty(sum(sizes), dtype=torch.float32, device=device)
-        out, off = [], 0
-        for n in sizes:
-            out.append(ws.narrow(0, off, n))
-            off += n
-        return out
+        return carve_scratch(self, [R * d['ldx0'], R * d['ldz'], R * d['ldz'], R * d['ldz'], R * d['ldh'], S * d['ldcat']], device)
 
     def _forward_launches(self, a: dict) -> Tensor:
         """The native forward's launches one ctypes call each (the A/B and test twin of ``_forward_native``)."""
@@ -175,30 +162,18 @@ class GraphMixerEncoder(TransientCaches, nn.Module):
 
     def _weights(self) -> tuple:
         """(argument block with the weights filled in, the tensors it points at), cached against the parameters' versions."""
-        d = self.__dict__
-        key = param_key(self)
-        if d.get('_tgmx_wkey') != key:
-            keep = []
-            f32 = lambda t: keep.append(_ops._f32c(t.detach(), 'weight')) or keep[-1].data_ptr()
+
+        def build(f32) -> '_native.GraphMixerFwd':
             blk = _native.GraphMixerFwd()
             tw = self.time_encoder.w
             blk.tw, blk.tb = f32(tw.weight.reshape(-1)), f32(tw.bias)
             blk.proj_w, blk.proj_b = f32(self.projection_layer.weight), f32(self.projection_layer.bias)
             blk.out_w, blk.out_b = f32(self.output_layer.weight), f32(self.output_layer.bias)
-            eps = float(self.mlp_mixers[0].token_norm.eps) if self.num_layers else 1e-5
-            blk.num_layers, blk.eps = self.num_layers, eps
-            for i, m in enumerate(self.mlp_mixers):
-                ly, tf, cf = blk.layers[i], m.token_feedforward.ffn, m.channel_feedforward.ffn
-                if float(m.token_norm.eps) != eps:
-                    raise NotImplementedError('tgm_amd GraphMixerEncoder: the native forward takes one LayerNorm eps for every layer')
-                ly.tok_g, ly.tok_b, ly.ch_g, ly.ch_b = f32(m.token_norm.weight), f32(m.token_norm.bias), f32(m.channel_norm.weight), f32(m.channel_norm.bias)
-                ly.tok_w1, ly.tok_b1, ly.tok_w2, ly.tok_b2 = f32(tf[0].weight), f32(tf[0].bias), f32(tf[3].weight), f32(tf[3].bias)
-                ly.ch_w1, ly.ch_b1, ly.ch_w2, ly.ch_b2 = f32(cf[0].weight), f32(cf[0].bias), f32(cf[3].weight), f32(cf[3].bias)
-                ly.tok_hidden, ly.ch_hidden = tf[0].out_features, cf[0].out_features
+            blk.num_layers, blk.eps = self.num_layers, fill_mixer_layers(blk, self.mlp_mixers, f32, 'GraphMixerEncoder')
             blk.K, blk.D, blk.T, blk.E, blk.F = self.num_tokens, self.edge_dim, self.time_dim, self.embed_dim, self.node_dim
-            d['_tgmx_w'] = (blk, keep)
-            d['_tgmx_wkey'] = key
-        return d['_tgmx_w']
+            return blk
+
+        return cached_block(self, build)
 
     def _forward_native(self, a: dict) -> Tensor:
         blk, _ = self._weights()

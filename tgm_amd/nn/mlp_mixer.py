@@ -17,13 +17,7 @@ from torch import Tensor
 
 from .. import _native
 from . import _ops
-
-
-def _needs_torch(module: nn.Module, x: Tensor, dropout: float) -> bool:
-    """The composed torch path: autograd has something to track, or dropout is active."""
-    if module.training and dropout > 0:
-        return True
-    return torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in module.parameters()))
+from ._fwd_plumbing import needs_torch
 
 
 class FeedForwardNet(nn.Module):
@@ -37,7 +31,7 @@ class FeedForwardNet(nn.Module):
 
     def forward(self, X: Tensor) -> Tensor:
         _native.require_device(X, 'FeedForwardNet input')
-        if _needs_torch(self, X, self.dropout):
+        if needs_torch(self, self.dropout, X):
             return self.ffn(X)  # training: torch ops under autograd (not native)
         x = _ops._f32c(X, 'FeedForwardNet input')
         lin0, lin1 = self.ffn[0], self.ffn[3]
@@ -95,7 +89,7 @@ class MLPMixer(nn.Module):
         _native.require_device(node_x, 'MLPMixer input')
         if node_x.dim() != 3 or node_x.shape[1] != self.num_tokens or node_x.shape[2] != self.num_channels:
             raise ValueError(f'MLPMixer expects [B, {self.num_tokens}, {self.num_channels}], got {list(node_x.shape)}')
-        if _needs_torch(self, node_x, self.dropout):
+        if needs_torch(self, self.dropout, node_x):
             return self._torch_forward(node_x)
         return self._native_forward(node_x)
 

@@ -21,6 +21,7 @@ from torch import Tensor
 
 from .. import _native
 from . import _ops
+from ._fwd_plumbing import carve_scratch, up4
 from ._paramver import TransientCaches
 
 _MAX_DENSE_NODES = 16384  # A_hat is dense: 16384^2 floats = 1 GiB
@@ -62,7 +63,7 @@ def normalized_adjacency(edge_index: Tensor, edge_weight: Optional[Tensor], N: i
     ei = edge_index.to(torch.int64)
     src, dst = ei[0].contiguous(), ei[1].contiguous()
     w = None if edge_weight is None else _ops._f32c(edge_weight, 'edge_weight')
-    ld = (N + 3) // 4 * 4
+    ld = up4(N)
     A = torch.empty((N, ld), dtype=torch.float32, device=dev)
     ws = torch.empty(2 * N, dtype=torch.float32, device=dev)
     _native.check(
@@ -136,13 +137,8 @@ class TGCN(TransientCaches, nn.Module):
                              [_ops._f32c(l.weight.detach(), 'weight') for l in lins], [_ops._f32c(l.bias.detach(), 'bias') for l in lins])
             d['_tgmx_w3_key'] = key
         W3, b3, lw, lb = d['_tgmx_w3']
-        ws = d.get('_tgmx_ws')
-        ld = (N + 3) // 4 * 4
-        up = lambda n: (n + 63) // 64 * 64  # 256-byte granules: every region a 16-byte aligned GEMM operand
-        sizes = [up(N * ld), up(2 * N), up(3 * C * N), up(3 * C * N), up(2 * C * N), up(C * N), up(C * N), up(C * N)]
-        need = sum(sizes)
-        if ws is None or ws.numel() < need or ws.device != dev:
-            ws = d['_tgmx_ws'] = torch.empty(need, dtype=torch.float32, device=dev)
+        ld = up4(N)
+        bufs = carve_scratch(self, [N * ld, 2 * N, 3 * C * N, 3 * C * N, 2 * C * N, C * N, C * N, C * N], dev)  # A, norm_ws, xwt, G, cat, pre[0..2]
         ei = edge_index if edge_index.dtype in (torch.int64, torch.int32) else edge_index.to(torch.int64)
         src, dst = ei[0], ei[1]
         if not src.is_contiguous():
@@ -154,7 +150,6 @@ class TGCN(TransientCaches, nn.Module):
         a = d.get('_tgmx_args')
         if a is None:
             a = d['_tgmx_args'] = _native.TgcnFwd()
-        base = ws.data_ptr()
         a.x, a.N, a.in_ch, a.C = x.data_ptr(), N, x.shape[1], C
         a.src, a.dst, a.edge_w, a.E = src.data_ptr(), dst.data_ptr(), _native.ptr(w), src.numel()
         a.idx32 = 1 if ei.dtype == torch.int32 else 0
@@ -163,13 +158,10 @@ class TGCN(TransientCaches, nn.Module):
         for g in range(3):
             a.lin_w[g], a.lin_b[g] = lw[g].data_ptr(), lb[g].data_ptr()
         a.H = H.data_ptr()
-        ptrs, off = [], 0
-        for n_ in sizes:
-            ptrs.append(base + 4 * off)
-            off += n_
-        a.A, a.ldA, a.norm_ws, a.xwt, a.G, a.cat = ptrs[0], ld, ptrs[1], ptrs[2], ptrs[3], ptrs[4]
+        a.ldA = ld
+        a.A, a.norm_ws, a.xwt, a.G, a.cat = (b.data_ptr() for b in bufs[:5])
         for g in range(3):
-            a.pre[g] = ptrs[5 + g]
+            a.pre[g] = bufs[5 + g].data_ptr()
         a.out = out.data_ptr()
         _native.check(lib.tgmx_tgcn_forward(ctypes.byref(a), _native.stream_ptr()), 'tgmx_tgcn_forward')
         return out

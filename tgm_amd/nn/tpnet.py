@@ -48,24 +48,10 @@ from torch import Tensor
 from .. import _native
 from ..constants import PADDED_NODE_ID
 from . import _ops
-from ._paramver import TransientCaches, param_key, param_list
+from ._fwd_plumbing import Unsupported, cached_block, carve_scratch, check_supported, fill_mixer_layers, i32, i64, needs_torch, pair_inputs, up4
+from ._paramver import TransientCaches
 from .mlp_mixer import MLPMixer, sgemm_ep
 from .time_encoding import Time2Vec
-
-_up4 = lambda n: (n + 3) // 4 * 4
-_i32 = lambda t: t if (t.dtype == torch.int32 and t.is_contiguous()) else t.to(torch.int32).contiguous()
-_i64 = lambda t: t if (t.dtype == torch.int64 and t.is_contiguous()) else t.to(torch.int64).contiguous()
-
-
-class _Unsupported(RuntimeError):
-    """A native entry point answered TGMX_E_UNSUPPORTED: the caller takes the composed path."""
-
-
-def _check(rc: int, what: str) -> None:
-    if rc == _native.E_UNSUPPORTED:
-        msg = _native.load().tgmx_last_error()
-        raise _Unsupported(f'{what}: {msg.decode() if msg else "unsupported"}')
-    _native.check(rc, what)
 
 
 class RandomProjectionModule(TransientCaches, nn.Module):
@@ -133,7 +119,7 @@ class RandomProjectionModule(TransientCaches, nn.Module):
     def _pair_features(self, a: Tensor, a_rows: Optional[Tensor], a_num_rows: int, k: int, b0: Tensor, b1: Optional[Tensor], bmod: int, n: int,
                        out: Tensor, ldo: int) -> None:  # fmt: skip
         tb = self._tables()
-        _check(
+        check_supported(
             _native.load().tgmx_tpnet_pair_features(ctypes.byref(tb), a.data_ptr(), _native.ptr(a_rows), a_num_rows, k, b0.data_ptr(), _native.ptr(b1),
                                                     bmod, n, int(self.concat_src_dst), int(self.scale), out.data_ptr(), ldo, _native.stream_ptr()),
             'tgmx_tpnet_pair_features',
@@ -143,10 +129,10 @@ class RandomProjectionModule(TransientCaches, nn.Module):
         """[P, out_dim]: the pair features before the MLP (the native kernel alone)."""
         _native.require_device(src, 'src')
         _native.require_device(dst, 'dst')
-        a, b = _i32(src.reshape(-1)), _i32(dst.reshape(-1))
+        a, b = i32(src.reshape(-1)), i32(dst.reshape(-1))
         if a.numel() != b.numel():
             raise ValueError('src and dst must have one entry per pair')
-        n, ld = a.numel(), _up4(self.out_dim)
+        n, ld = a.numel(), up4(self.out_dim)
         feat = torch.empty((n, ld), dtype=torch.float32, device=a.device)
         if n:
             self._pair_features(a, None, n, 1, b, None, n, n, feat, ld)
@@ -185,7 +171,7 @@ class RandomProjectionModule(TransientCaches, nn.Module):
         for name, t in (('src', src), ('dst', dst), ('time', time), ('now_time', self.now_time)):
             _native.require_device(t, name)
         tb = self._tables()
-        s, d, t = _i32(src.reshape(-1)), _i32(dst.reshape(-1)), _i64(time.reshape(-1))
+        s, d, t = i32(src.reshape(-1)), i32(dst.reshape(-1)), i64(time.reshape(-1))
         n = s.numel()
         if d.numel() != n or t.numel() != n:
             raise ValueError('src, dst and time must have one entry per edge')
@@ -269,32 +255,15 @@ class TPNet(TransientCaches, nn.Module):
         ])  # fmt: skip
 
     # -- inputs ------------------------------------------------------------------------------------------------------------------------
-    def _inputs(self, node_x, src, dst, edge_time, nids, nbr_t, nbr_x, src_rows, dst_rows) -> dict:
-        if nids.dim() != 2 or nbr_x.dim() != 3 or tuple(nbr_t.shape) != tuple(nids.shape) or tuple(nbr_x.shape[:2]) != tuple(nids.shape):
-            raise ValueError(f'expected neighbour ids / times [S, k] and edge features [S, k, d], got {list(nids.shape)}, {list(nbr_t.shape)}, {list(nbr_x.shape)}')
-        if nids.shape[1] != self.num_neighbors:
-            raise ValueError(f'TPNet(num_neighbors={self.num_neighbors}) got {nids.shape[1]} neighbour slots per row')
-        if nbr_x.shape[2] != self.edge_x_dim or node_x.dim() != 2 or node_x.shape[1] != self.node_feat_dim:
-            raise ValueError(f'expected node_x [N, {self.node_feat_dim}] and edge features of width {self.edge_x_dim}, got {list(node_x.shape)} and '
-                             f'{list(nbr_x.shape)}')
-        for name, t in (('node_x', node_x), ('src', src), ('dst', dst), ('edge_time', edge_time), ('neighbours', nids), ('neighbours_time', nbr_t),
-                        ('neighbours_edge_feat', nbr_x)):  # fmt: skip
-            _native.require_device(t, name)
-        B = src.numel()
-        if dst.numel() != B or edge_time.numel() != B:
-            raise ValueError('src, dst and edge_time must have one entry per pair')
-        rows = None
-        if src_rows is None:
-            if nids.shape[0] < 2 * B:
-                raise ValueError(f'{B} pairs need neighbour rows [:B] for the sources and [B:2B] for the destinations, got {nids.shape[0]} rows')
-        else:
-            _native.require_device(src_rows, 'src_rows')
-            _native.require_device(dst_rows, 'dst_rows')
-            if src_rows.numel() != B or dst_rows.numel() != B:
-                raise ValueError('src_rows and dst_rows must have one entry per pair')
-            rows = torch.cat([_i32(src_rows.reshape(-1)), _i32(dst_rows.reshape(-1))])
-        return dict(node_x=_ops._f32c(node_x, 'node_x'), src=_i32(src.reshape(-1)), dst=_i32(dst.reshape(-1)), t=_i64(edge_time.reshape(-1)),
-                    nids=_i32(nids), nbr_t=_i64(nbr_t), nbr_x=_ops._f32c(nbr_x, 'neighbours_edge_feat'), rows=rows, B=B, k=nids.shape[1])  # fmt: skip
+    def _check_slots(self, k: int) -> None:
+        if k != self.num_neighbors:
+            raise ValueError(f'TPNet(num_neighbors={self.num_neighbors}) got {k} neighbour slots per row')
+
+    def _inputs(self, *tensors) -> dict:
+        """(node_x, src, dst, edge_time, nids, nbr_t, nbr_x, src_rows, dst_rows), checked and converted."""
+        a = pair_inputs(*tensors, self.node_feat_dim, self.edge_x_dim, self._check_slots, 'B')
+        src_rows, dst_rows = a.pop('src_rows'), a.pop('dst_rows')
+        return dict(a, rows=None if src_rows is None else torch.cat([src_rows, dst_rows]), B=a['src'].numel(), k=a['nids'].shape[1])
 
     def forward(self, node_x: Tensor, edge_index: Tensor, edge_time: Tensor, neighbours: Tensor, neighbours_time: Tensor,
                 neighbours_edge_feat: Tensor) -> Tuple[Tensor, Tensor]:  # fmt: skip
@@ -305,18 +274,13 @@ class TPNet(TransientCaches, nn.Module):
         """``forward`` on ``nbr_*[cat(src_rows, dst_rows)]`` without making those copies (same results, bit for bit)."""
         return self._run(self._inputs(node_x, src, dst, edge_time, nbr_nids, nbr_edge_time, nbr_edge_x, src_rows, dst_rows))
 
-    def _needs_torch(self, *inputs: Tensor) -> bool:
-        if self.training and self.dropout > 0:
-            return True
-        return torch.is_grad_enabled() and (any(t.requires_grad for t in inputs) or any(p.requires_grad for p in param_list(self)))
-
     def _native_ok(self) -> bool:
         rp = self.random_projections
         return (hasattr(self.time_encoder, 'w') and self.num_layers <= _native.MIXER_MAX_LAYERS
                 and (rp is None or rp.num_layer + 1 <= _native.TPNET_PAIR_MAX_LEVELS))  # fmt: skip
 
     def _run(self, a: dict) -> Tuple[Tensor, Tensor]:
-        if self._needs_torch(a['node_x'], a['nbr_x']):
+        if needs_torch(self, self.dropout, a['node_x'], a['nbr_x']):
             return self._torch_forward(a)
         if not self._native_ok():
             self._warn_composed('its shape is outside the native envelope (num_layer <= 3, at most 8 mixer layers, Time2Vec)')
@@ -328,7 +292,7 @@ class TPNet(TransientCaches, nn.Module):
         if B:
             try:
                 self._forward_native(a, out)
-            except _Unsupported as e:  # the token block does not fit LDS: compose
+            except Unsupported as e:  # the token block does not fit LDS: compose
                 self._warn_composed(str(e))
                 return self._torch_forward(a)
         return out[:B], out[B:]
@@ -367,32 +331,20 @@ class TPNet(TransientCaches, nn.Module):
         od = 0 if self.random_projections is None else self.random_projections.out_dim
         E = self.output_dim
         Hc = max(m.channel_feedforward.ffn[0].out_features for m in self.mlp_mixers) if self.num_layers else 4
-        return dict(od=od, ldf=_up4(max(od, 1)), ldfh=_up4(max(4 * od, 1)), ldx0=_up4(self.node_feat_dim + self.time_feat_dim + self.edge_x_dim + 2 * od),
-                    ldhp=_up4(2 * E), ldz=_up4(E), ldh=_up4(Hc))  # fmt: skip
+        return dict(od=od, ldf=up4(max(od, 1)), ldfh=up4(max(4 * od, 1)), ldx0=up4(self.node_feat_dim + self.time_feat_dim + self.edge_x_dim + 2 * od),
+                    ldhp=up4(2 * E), ldz=up4(E), ldh=up4(Hc))  # fmt: skip
 
     def _scratch(self, B: int, k: int, device) -> List[Tensor]:
-        """feat, feat_h, pf, x0, hp, z, z1, y, h: views into one buffer kept between batches (each region 256-byte aligned)."""
+        """feat, feat_h, pf, x0, hp, z, z1, y, h: views into one buffer kept between batches."""
         d = self._dims()
         R = 2 * B * k
-        up = lambda n: (n + 63) // 64 * 64
         R2 = 2 * R if d['od'] else 0
-        sizes = [up(R2 * d['ldf']), up(R2 * d['ldfh']), up(R2 * d['ldf']), up(R * d['ldx0']), up(R * d['ldhp'])] + [up(R * d['ldz'])] * 3 + [up(R * d['ldh'])]
-        ws = self.__dict__.get('_tgmx_ws')
-        if ws is None or ws.numel() < sum(sizes) or ws.device != device:
-            ws = self.__dict__['_tgmx_ws'] = torch.empty(max(1, sum(sizes)), dtype=torch.float32, device=device)
-        out, off = [], 0
-        for n in sizes:
-            out.append(ws.narrow(0, off, n))
-            off += n
-        return out
+        return carve_scratch(self, [R2 * d['ldf'], R2 * d['ldfh'], R2 * d['ldf'], R * d['ldx0'], R * d['ldhp']] + [R * d['ldz']] * 3 + [R * d['ldh']], device)
 
     def _weights(self) -> tuple:
         """(argument block with the weights filled in, the tensors it points at), cached against the parameters' versions."""
-        d = self.__dict__
-        key = param_key(self)
-        if d.get('_tgmx_wkey') != key:
-            keep: list = []
-            f32 = lambda t: keep.append(_ops._f32c(t.detach(), 'weight')) or keep[-1].data_ptr()
+
+        def build(f32) -> '_native.TPNetFwd':
             blk = _native.TPNetFwd()
             tw, pl, rp = self.time_encoder.w, self.projection_layer, self.random_projections
             blk.tw, blk.tb = f32(tw.weight.reshape(-1)), f32(tw.bias)
@@ -400,20 +352,11 @@ class TPNet(TransientCaches, nn.Module):
             if rp is not None:
                 blk.rp_w1, blk.rp_b1, blk.rp_w2, blk.rp_b2 = f32(rp.mlp[0].weight), f32(rp.mlp[0].bias), f32(rp.mlp[2].weight), f32(rp.mlp[2].bias)
                 blk.rp_concat, blk.rp_scale, blk.rp_out_dim = int(rp.concat_src_dst), int(rp.scale), rp.out_dim
-            eps = float(self.mlp_mixers[0].token_norm.eps) if self.num_layers else 1e-5
-            blk.num_layers, blk.eps = self.num_layers, eps
-            for i, m in enumerate(self.mlp_mixers):
-                ly, tf, cf = blk.layers[i], m.token_feedforward.ffn, m.channel_feedforward.ffn
-                if float(m.token_norm.eps) != eps:
-                    raise NotImplementedError('tgm_amd TPNet: the native forward takes one LayerNorm eps for every layer')
-                ly.tok_g, ly.tok_b, ly.ch_g, ly.ch_b = f32(m.token_norm.weight), f32(m.token_norm.bias), f32(m.channel_norm.weight), f32(m.channel_norm.bias)
-                ly.tok_w1, ly.tok_b1, ly.tok_w2, ly.tok_b2 = f32(tf[0].weight), f32(tf[0].bias), f32(tf[3].weight), f32(tf[3].bias)
-                ly.ch_w1, ly.ch_b1, ly.ch_w2, ly.ch_b2 = f32(cf[0].weight), f32(cf[0].bias), f32(cf[3].weight), f32(cf[3].bias)
-                ly.tok_hidden, ly.ch_hidden = tf[0].out_features, cf[0].out_features
+            blk.num_layers, blk.eps = self.num_layers, fill_mixer_layers(blk, self.mlp_mixers, f32, 'TPNet')
             blk.k, blk.dN, blk.dE, blk.dT, blk.E = self.num_neighbors, self.node_feat_dim, self.edge_x_dim, self.time_feat_dim, self.output_dim
-            d['_tgmx_w'] = (blk, keep)
-            d['_tgmx_wkey'] = key
-        return d['_tgmx_w']
+            return blk
+
+        return cached_block(self, build)
 
     def _forward_native(self, a: dict, out: Tensor) -> None:
         blk, _ = self._weights()
@@ -431,4 +374,4 @@ class TPNet(TransientCaches, nn.Module):
         blk.feat, blk.feat_h, blk.pf, blk.x0, blk.hp, blk.z, blk.z1, blk.y, blk.h = (b.data_ptr() for b in bufs)
         blk.ldf, blk.ldfh, blk.ldx0, blk.ldhp, blk.ldz, blk.ldh = d['ldf'], d['ldfh'], d['ldx0'], d['ldhp'], d['ldz'], d['ldh']
         blk.out = out.data_ptr()
-        _check(_native.load().tgmx_tpnet_forward(ctypes.byref(blk), _native.stream_ptr()), 'tgmx_tpnet_forward')
+        check_supported(_native.load().tgmx_tpnet_forward(ctypes.byref(blk), _native.stream_ptr()), 'tgmx_tpnet_forward')
