@@ -1135,6 +1135,44 @@ typedef struct tgmx_tpnet_fwd {
 } tgmx_tpnet_fwd_t;
 int tgmx_tpnet_forward(const tgmx_tpnet_fwd_t* args, tgmx_stream_t stream);
 
+/* ---- NCNPredictor (the reference's tgm/nn/decoder/ncnpred.py): the common-neighbour decoder of TNCN, inference ---- */
+
+/* The symmetric adjacency of edge_index [2, E] (int64 when is64, else int32; row 1 starts row_stride entries after row 0) over N local
+ * node ids, as sorted rows: A[a, b] = how often (a, b) or (b, a) occurs, so a self-loop counts twice.  indptr [N + 1]; cols [2 E] holds
+ * every row's neighbour ids ascending, an id repeated as often as it occurs.  One radix sort of the 2 E (row, col) keys: the result does
+ * not depend on scheduling, and a row may be as long as 2 E.  An edge with an endpoint outside [0, N) is left out.  2 E < 2^31.
+ * workspace: tgmx_ncn_adj_workspace_bytes(E) bytes (0: E out of range). */
+size_t tgmx_ncn_adj_workspace_bytes(int64_t E);
+int tgmx_ncn_adj_build(const void* edge_index, int32_t is64, int64_t row_stride, int64_t E, int64_t N, int32_t* indptr, int32_t* cols,
+                       void* workspace, size_t workspace_bytes, tgmx_stream_t stream);
+
+/* xs [B, ldxs] for the pairs tar [2, B] (int64 / int32, row stride tar_stride), k = 2 or 4 blocks of C columns:
+ *   x[i] * x[j] | (k = 4: A[j, i] W[r, i] x[i] | A[i, j] W[r, j] x[j]) | sum over n of A[i, n] A[j, n] W[r, n] x[n]   (ascending n)
+ * with W[r, n] = exp(-(float32(edge_time[r] - last_update[n]) / 10000)), or 1 when last_update and edge_time are NULL.  last [2 N] int32
+ * of scratch: a pair keeps its blocks after the first only where r is the LAST position of tar[0][r] in tar[0] and of tar[1][r] in tar[1]
+ * (the reference's CPU behaviour); last = NULL: every pair keeps them.  A pair with a target outside [0, N) gets a zero row.  Columns up
+ * to ldxs zeroed.  One wave per pair, fixed summation order, no float atomics. */
+int tgmx_ncn_cn_emb(const float* x, int64_t N, int32_t C, int32_t k, const int32_t* indptr, const int32_t* cols, const void* tar,
+                    int32_t tar_is64, int64_t tar_stride, int64_t B, const int64_t* last_update, const int64_t* edge_time, int32_t* last,
+                    float* xs, int64_t ldxs, tgmx_stream_t stream);
+
+/* The NCNPredictor inference forward as ONE call: tgmx_ncn_adj_build (skipped when have_adj: indptr / cols hold a prepared adjacency),
+ * tgmx_ncn_cn_emb, out = W2 relu(W1 xs + b1) + b2 (two GEMMs).  Scratch: indptr [N + 1], cols [2 E], adj_ws, last [2 N], xs [B, ldxs],
+ * h [B, ldh]; ldxs and ldh multiples of 4. */
+typedef struct tgmx_ncn_fwd {
+  const float* x; int64_t N;
+  int32_t C, k, H, out_ch, decay, dup_all;                      /* dup_all: every duplicate target keeps its adjacency row */
+  const void* edge_index; int64_t ei_stride, E; int32_t ei_is64, have_adj;
+  const void* tar; int64_t tar_stride, B; int32_t tar_is64, reserved_;
+  const int64_t *last_update, *edge_time;                       /* [N], [B]; read when decay */
+  const float *w1, *b1, *w2, *b2;                               /* xsmlp.{0,2} */
+  int32_t *indptr, *cols; void* adj_ws; size_t adj_ws_bytes;
+  int32_t* last;
+  float *xs, *h; int64_t ldxs, ldh;
+  float* out;                                                   /* [B, out_ch] */
+} tgmx_ncn_fwd_t;
+int tgmx_ncn_forward(const tgmx_ncn_fwd_t* args, tgmx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -460,6 +460,29 @@ SIGNATURES['tgmx_tpnet_token_mix'] = SIGNATURES['tgmx_mixer_token']
 SIGNATURES['tgmx_tpnet_mean'] = (c_int32, [_P, c_int64, c_int64, c_int32, c_int32, _P, c_int64, _P])
 SIGNATURES['tgmx_tpnet_forward'] = (c_int32, [ctypes.POINTER(TPNetFwd), _P])
 
+
+class NCNFwd(ctypes.Structure):
+    """tgmx_ncn_fwd_t (include/tgm_amd.h)."""
+
+    _fields_ = [
+        ('x', c_void_p), ('N', c_int64),
+        ('C', c_int32), ('k', c_int32), ('H', c_int32), ('out_ch', c_int32), ('decay', c_int32), ('dup_all', c_int32),
+        ('edge_index', c_void_p), ('ei_stride', c_int64), ('E', c_int64), ('ei_is64', c_int32), ('have_adj', c_int32),
+        ('tar', c_void_p), ('tar_stride', c_int64), ('B', c_int64), ('tar_is64', c_int32), ('reserved_', c_int32),
+        ('last_update', c_void_p), ('edge_time', c_void_p),
+        ('w1', c_void_p), ('b1', c_void_p), ('w2', c_void_p), ('b2', c_void_p),
+        ('indptr', c_void_p), ('cols', c_void_p), ('adj_ws', c_void_p), ('adj_ws_bytes', c_size_t),
+        ('last', c_void_p),
+        ('xs', c_void_p), ('h', c_void_p), ('ldxs', c_int64), ('ldh', c_int64),
+        ('out', c_void_p),
+    ]  # fmt: skip
+
+
+SIGNATURES['tgmx_ncn_adj_workspace_bytes'] = (c_size_t, [c_int64])
+SIGNATURES['tgmx_ncn_adj_build'] = (c_int32, [_P, c_int32, c_int64, c_int64, c_int64, _P, _P, _P, c_size_t, _P])
+SIGNATURES['tgmx_ncn_cn_emb'] = (c_int32, [_P, c_int64, c_int32, c_int32, _P, _P, _P, c_int32, c_int64, c_int64, _P, _P, _P, _P, c_int64, _P])
+SIGNATURES['tgmx_ncn_forward'] = (c_int32, [ctypes.POINTER(NCNFwd), _P])
+
 _lib: Optional[ctypes.CDLL] = None
 
 

@@ -38,6 +38,7 @@ extern "C" size_t tgmx_abi_sizeof(int32_t which) {
     case 16: return sizeof(tgmx_dygformer_fwd_t);
     case 17: return sizeof(tgmx_tpnet_tables_t);
     case 18: return sizeof(tgmx_tpnet_fwd_t);
+    case 19: return sizeof(tgmx_ncn_fwd_t);
     default: return 0;
   }
 }

@@ -4,15 +4,16 @@ from .base import EncoderModule
 from .dygformer import DyGFormer, NeighborCooccurrenceEncoder, TransformerEncoder
 from .graphmixer import GraphMixerEncoder
 from .mlp_mixer import FeedForwardNet, MLPMixer
+from .ncn import NCNPredictor
 from .tgat import TGAT, MergeLayer
 from .tgcn import TGCN, GCNConv
 from .tgn import GraphAttentionEmbedding, IdentityMessage, LastAggregator, MeanAggregator, TGNMemory, TGNStep, TransformerConv, sampled_edge_list
 from .time_encoding import Time2Vec
 from .tpnet import RandomProjectionModule, TPNet
-from . import encoder, modules  # noqa: E402,F401  (the reference's import paths: tgm.nn.encoder.tgn, tgm.nn.modules.attention, ...)
+from . import decoder, encoder, modules  # noqa: E402,F401  (the reference's import paths: tgm.nn.encoder.tgn, tgm.nn.modules.attention, ...)
 
 __all__ = [
     'DyGFormer', 'EncoderModule', 'FeedForwardNet', 'GCNConv', 'GraphAttentionEmbedding', 'GraphMixerEncoder', 'IdentityMessage', 'LastAggregator',
-    'MLPMixer', 'MeanAggregator', 'MergeLayer', 'NeighborCooccurrenceEncoder', 'RandomProjectionModule', 'TGAT', 'TGCN',
+    'MLPMixer', 'MeanAggregator', 'MergeLayer', 'NCNPredictor', 'NeighborCooccurrenceEncoder', 'RandomProjectionModule', 'TGAT', 'TGCN',
     'TGNMemory', 'TGNStep', 'TPNet', 'TemporalAttention', 'Time2Vec', 'TransformerConv', 'TransformerEncoder', 'invalidate_parameter_caches', 'sampled_edge_list',
 ]  # fmt: skip
