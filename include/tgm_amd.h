@@ -270,9 +270,44 @@ typedef struct tgmx_recency_step {
 } tgmx_recency_step_t;
 
 int tgmx_recency_step(const tgmx_recency_step_t* step, tgmx_stream_t stream);
-/* How tgmx_recency_step would schedule this argument block: bit 0 = hop 0 and hop 1 run as ONE launch (B <= 64, hop 1
- * not served by the narrow-row kernel; static index: wide rows only).  Informational (bench.py
- * attributes the timed launch's bytes with it); results never depend on it. */
+/* How tgmx_recency_step would schedule this argument block, from its sizes and pointer values alone (nothing is dereferenced, no
+ * device is needed).  Informational (bench.py attributes the timed launch's bytes with bit 0; a test pins the schedule table
+ * with the rest); results never depend on it.
+ *   bit 0        TGMX_PLAN_FUSED01: hop 0 and hop 1 run as ONE launch (B <= 64, hop 1 not served by the narrow-row kernel;
+ *                static index: wide rows only)
+ *   bits 4-7     TGMX_RIDE_*: the part of the ring update that rides lookup launch 0 (hop 0, or the fused launch)
+ *   bits 8-11    TGMX_RIDE_*: what rides lookup launch 1 (hop 1 when it is a launch of its own)
+ *   bits 12-16   rider workgroups of launch 0        bits 17-21   rider workgroups of launch 1
+ *   bits 22-23   fused launch: placement capacity of the riders' LDS (0: none, 1: 512 entries, 2: 1024 entries)
+ *   bits 24-27   TGMX_AFTER_*: what follows the last lookup (a call that defers its commit, tgmx_recency_step_t.defer, leaves
+ *                TGMX_AFTER_COMMIT to the next call's lookup launch; the plan does not look at `defer`)
+ * The schedule, for streaming rings with n > 0, at least one hop and one seed (m = ring entries: n, or 2 n undirected; chunks =
+ * ceil(m / 256); hops >= 2 carry nothing):
+ *   launches         m            launch 0                   launch 1               LDS    after
+ *   fused hop 0+1    <= 512       ALL x 1                    -                      512    COMMIT
+ *   fused hop 0+1    513..1024    SORT_MERGE_PLACE x chunks  -                      1024   COMMIT
+ *   fused hop 0+1    1025..4096   SORT_MERGE x chunks        -                      0      PRESORTED
+ *   hop 0 only       <= 4096      SORT x chunks              -                      -      MERGE_PRESORTED
+ *   hop 0, hop 1     <= 256       SORT_MERGE x 1             PLACE_ONLY x 1         -      COMMIT
+ *   hop 0, hop 1     257..1024    SORT x chunks              MERGE_PLACE x chunks   -      COMMIT
+ *   hop 0, hop 1     1025..4096   SORT x chunks              MERGE x chunks         -      PRESORTED
+ * Nothing rides when there is no hop or no seed, with TGMX_NO_RIDE, or for m > 4096: TGMX_AFTER_BLOCK (m <= 4096) or
+ * TGMX_AFTER_LARGE.  n = 0 and the static index: TGMX_AFTER_NONE. */
+#define TGMX_PLAN_FUSED01 1
+#define TGMX_RIDE_NONE 0
+#define TGMX_RIDE_SORT 1             /* workgroup c sorts entries [256 c, 256 c + 256) */
+#define TGMX_RIDE_MERGE 2            /* workgroup c ranks chunk c's entries among all chunks */
+#define TGMX_RIDE_SORT_MERGE 3       /* both, a barrier between the riders in between */
+#define TGMX_RIDE_PLACE_ONLY 4       /* one workgroup decides the placement of a merged batch */
+#define TGMX_RIDE_ALL 5              /* one workgroup: chunk sorts, merge, placement decisions */
+#define TGMX_RIDE_SORT_MERGE_PLACE 6 /* SORT_MERGE, then the last rider out decides the placement */
+#define TGMX_RIDE_MERGE_PLACE 7      /* MERGE, then the last rider out decides the placement */
+#define TGMX_AFTER_NONE 0            /* no update */
+#define TGMX_AFTER_COMMIT 1          /* one launch writes what the riders decided: records, write_pos, feature rows */
+#define TGMX_AFTER_PRESORTED 2       /* placement of the batch the riders sorted, then the feature rows */
+#define TGMX_AFTER_MERGE_PRESORTED 3 /* the merge as a launch of its own, then TGMX_AFTER_PRESORTED */
+#define TGMX_AFTER_BLOCK 4           /* the whole update of <= 4096 entries as launches of its own */
+#define TGMX_AFTER_LARGE 5           /* m > 4096: the radix-sort path (its front half beside the lookups on a side stream) */
 int tgmx_recency_step_plan(const tgmx_recency_step_t* step);
 
 /* Deferred ring commit (tgmx_recency_step_t.defer): the state of one ring -- the pending batch's update arguments, the stamp

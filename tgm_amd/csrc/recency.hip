@@ -17,7 +17,8 @@
 // File map (one translation unit: the lookup launches carry pieces of the ring update, so both live here):
 //   UpdateArgs, keys, the single-workgroup sort / placement body (update_block_body)
 //   riders: update_chunk_sort, update_merge_riding, rider_barrier, update_side_work -- the state-independent half of
-//     the ring update as workgroup-sized pieces that ride inside the lookup launches
+//     the ring update as workgroup-sized pieces that ride inside the lookup launches; which piece rides
+//     which launch is one table: the comment above SideStage, plan_riders on the host
 //   lookup pieces (fetch_seed ... lookup_seed) and the kernels built from them: recency_lookup_kernel (one hop),
 //     recency_lookup_fused01_kernel (hop 0 + hop 1 in one launch), lookup_packed_kernel (narrow rows)
 //   the stand-alone update paths (one workgroup / chunk sort + merge / rocPRIM radix sort), uniform sampler, C entry points
@@ -592,15 +593,6 @@ __global__ __launch_bounds__(kBlockThreads) void ring_update_block_kernel(const 
   update_block_body<E, MAXM, PRESORTED, false>(a, L, S, (int)blockIdx.x, (int)gridDim.x);
 }
 
-// placement DECISIONS only (PRESORTED, DEFER): reads write_pos, writes winner / target to the scratch -- may run next to the
-// lookups of the same batch; ring_update_feat_kernel<COMMIT> applies them afterwards
-template <int E, int MAXM>
-__global__ __launch_bounds__(kBlockThreads) void ring_update_decide_kernel(const UpdateArgs a) {
-  __shared__ PlaceLds<MAXM> L;
-  __shared__ SortLds<1> S;
-  update_block_body<E, MAXM, true, true>(a, L, S, (int)blockIdx.x, (int)gridDim.x);
-}
-
 // ---- the state-independent half of the ring update, as workgroup-sized pieces -------------------------------------
 // The order of a batch's entries depends on the batch alone, not on the rings, so `tgmx_recency_step` lets it ride
 // along with the lookups: the first `side_blocks` workgroups of the hop-0 launch chunk-sort the entries, the first
@@ -845,21 +837,37 @@ __device__ __forceinline__ void update_merge_riding(const UpdateArgs& a, int c0,
   }
 }
 
-// What rides along with which launch (tgmx_recency_step):
-//   kSideSort  (hop 0): workgroup c chunk-sorts entries [256 c, 256 c + 256)
-//   kSideMerge (hop 1, 1024 < m <= 4096): workgroup c ranks chunk c's entries; the placement is its own launch
-//   kSideSortMerge / kSidePlaceOnly (hop 0 / hop 1 as two launches, m <= 1024, round 3): the chunk riders of hop 0 merge too (barrier between
-//     them), hop 1's ONE rider only decides the placement -- review shape: hop 1 17.9 -> 7.9 us, step 29.0 -> 25.0 us
-//   kSidePlace (hop 1, m <= 1024): ONE workgroup merges the whole batch and decides the placement (DEFER): after the
-//              lookups a single launch commits records, write_pos and feature rows
-//   kSideAll   (fused hop 0 + 1 launch, m <= 1024): ONE workgroup does all of it -- chunk sorts one after the other,
-//              merge, placement decisions -- inside the single lookup launch
-//   kSideSort / kSideMergePlace (hop 0 / hop 1 as two launches, m <= 1024, round 6): hop 0's riders only chunk-sort (no barrier inside a
-//     launch: the launch boundary is the barrier), hop 1's riders rank their chunks and the last one out decides the placement -- the
-//     update's chain is spread over BOTH lookup launches instead of pacing the first (review shape: 13.4 + 7.1 us -> see DESIGN 3.2)
-//   kSideSortMerge (fused hop 0 + 1 launch, 1024 < m <= 4096): workgroup c chunk-sorts, all riders meet at a barrier of
-//              their own (they are the launch's first <= 16 workgroups: resident together), then workgroup c merges
-constexpr int kSideSort = 1, kSideMerge = 2, kSidePlace = 3, kSideAll = 4, kSideSortMerge = 5, kSidePlaceOnly = 6, kSideSortMergePlace = 7, kSideMergePlace = 8;
+// What rides along with which lookup launch, and what follows the last lookup (plan_riders, called once by tgmx_recency_step;
+// tgmx_recency_step_plan reports it).  m = ring entries of the batch (n, or 2 n undirected), chunks = ceil(m / 256).  Riders
+// exist for streaming rings with n > 0, at least one hop, at least one seed, m <= 4096 and no TGMX_NO_RIDE; without them the
+// update follows the lookups whole (kAfterBlock; m > 4096: kAfterLarge).
+//
+//   launches         m            launch 0                      launch 1                   pcap  after
+//   fused hop 0+1    <= 512       kSideAll x 1                  -                          512   commit
+//   fused hop 0+1    513..1024    kSideSortMergePlace x chunks  -                          1024  commit
+//   fused hop 0+1    1025..4096   kSideSortMerge x chunks       -                          0     presorted placement
+//   hop 0 only       <= 4096      kSideSort x chunks            -                          -     merge launch + presorted
+//   hop 0, hop 1     <= 256       kSideSortMerge x 1            kSidePlaceOnly x 1         -     commit
+//   hop 0, hop 1     257..1024    kSideSort x chunks            kSideMergePlace x chunks   -     commit
+//   hop 0, hop 1     1025..4096   kSideSort x chunks            kSideMerge x chunks        -     presorted placement
+//
+// Hops h >= 2 carry nothing.  A call that defers its commit (tgmx_defer_t) leaves "commit" to the next call's lookup launch.
+//   kSideSort            workgroup c chunk-sorts entries [256 c, 256 c + 256)
+//   kSideMerge           workgroup c ranks chunk c's entries among all chunks (the sorts ran in the previous launch)
+//   kSideSortMerge       both, with the riders' barrier between them (they are the launch's first <= 16 workgroups: resident together)
+//   kSidePlaceOnly       ONE workgroup decides the placement of a batch the previous launch's riders sorted and merged
+//   kSideAll             ONE workgroup does all of it: chunk sorts one after the other, merge, placement decisions
+//   kSideSortMergePlace  kSideSortMerge, then the last rider out decides the placement
+//   kSideMergePlace      kSideMerge, then the last rider out decides the placement: the update's chain is spread over BOTH lookup
+//                        launches and the launch boundary is the barrier
+// A placement decided by a rider writes only the scratch; the commit (ring_update_feat_kernel<true>) writes the rings.
+enum SideStage : int { kSideNone, kSideSort, kSideMerge, kSideSortMerge, kSidePlaceOnly, kSideAll, kSideSortMergePlace, kSideMergePlace };
+enum AfterLookups : int { kAfterNone, kAfterCommit, kAfterPresorted, kAfterMergePresorted, kAfterBlock, kAfterLarge };
+// (tgmx_recency_step_plan reports both as the header's TGMX_RIDE_* / TGMX_AFTER_*)
+static_assert(kSideSort == TGMX_RIDE_SORT && kSideMerge == TGMX_RIDE_MERGE && kSideSortMerge == TGMX_RIDE_SORT_MERGE &&
+              kSidePlaceOnly == TGMX_RIDE_PLACE_ONLY && kSideAll == TGMX_RIDE_ALL && kSideSortMergePlace == TGMX_RIDE_SORT_MERGE_PLACE &&
+              kSideMergePlace == TGMX_RIDE_MERGE_PLACE && kAfterCommit == TGMX_AFTER_COMMIT && kAfterPresorted == TGMX_AFTER_PRESORTED &&
+              kAfterMergePresorted == TGMX_AFTER_MERGE_PRESORTED && kAfterBlock == TGMX_AFTER_BLOCK && kAfterLarge == TGMX_AFTER_LARGE, "tgm_amd.h");
 
 // Barrier between the `parts` rider workgroups of one launch: bar[0] counts arrivals, bar[1] is the generation.  It
 // resets itself, so the words only have to be zero when the scratch buffer is first used.  What crosses it (the
@@ -947,6 +955,24 @@ union RiderLds<0> {
   SampleLds smp;
 };
 
+// The tail of a chunk rider that ranked its chunk with device-coherent stores: count the riders out; the last one decides the
+// placement of the whole batch (NCH chunks, one entry of every chunk per thread).
+template <int NCH, int PCAP>
+__device__ __forceinline__ void rider_last_out_places(const UpdateArgs& u, PlaceLds<PCAP>& place) {
+  const int chunks = (int)((u.m + kChunk - 1) / kChunk);
+  __shared__ int last_out;
+  __syncthreads();  // every thread's device-coherent stores have completed
+  if (threadIdx.x == 0) {
+    const int prev = __hip_atomic_fetch_add(&u.barrier[5], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    last_out = prev == chunks - 1;
+    if (last_out) __hip_atomic_store(&u.barrier[5], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // zero for the next launch
+  }
+  __syncthreads();
+  if (!last_out) return;
+  SortLds<1> none;
+  update_block_body<NCH, PCAP, true, true, true>(u, place, none);
+}
+
 template <int PCAP = kRidePlaceMaxM>
 __device__ __forceinline__ void update_side_work(const UpdateArgs& u, int stage, int block) {
   __shared__ RiderLds<PCAP> W;
@@ -961,41 +987,17 @@ __device__ __forceinline__ void update_side_work(const UpdateArgs& u, int stage,
   } else if constexpr (PCAP > 0) {
     constexpr int NCH = PCAP / kChunk;  // chunks of a batch this rider takes whole: one entry of every chunk per thread
     if (stage == kSideSortMergePlace) {
-      // fused hop 0 + 1 launch, 512 < m <= 1024 (a 2-rank share of the wiki batch: m = 800): one rider PER CHUNK sorts and, behind the
-      // riders' barrier, ranks its chunk; the last one out decides the placement.  (One rider doing the four chunk sorts one after
-      // the other, the merge and the placement took longer than the lookups around it: 42.7 us per step instead of 34.)
-      const int chunks = (int)((u.m + kChunk - 1) / kChunk);
-      __shared__ int last_out;
+      // One rider PER CHUNK (a 2-rank share of the wiki batch: m = 800).  One rider doing the four chunk sorts one after the
+      // other, the merge and the placement took longer than the lookups around it: 42.7 us per step instead of 34.
       update_chunk_sort<true>(u, block, W.sort);
-      if (!rider_barrier(u.barrier, chunks) && threadIdx.x == 0) atomicOr(u.status, TGMX_ST_SCRATCH);
+      if (!rider_barrier(u.barrier, (int)((u.m + kChunk - 1) / kChunk)) && threadIdx.x == 0) atomicOr(u.status, TGMX_ST_SCRATCH);
       update_merge_riding<1, NCH, true>(u, block, W.smp);
-      __syncthreads();  // every thread's device-coherent stores have completed
-      if (threadIdx.x == 0) {
-        const int prev = __hip_atomic_fetch_add(&u.barrier[5], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        last_out = prev == chunks - 1;
-        if (last_out) __hip_atomic_store(&u.barrier[5], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // zero for the next launch
-      }
-      __syncthreads();
-      if (!last_out) return;
-      SortLds<1> none;
-      update_block_body<NCH, PCAP, true, true, true>(u, W.place, none);
+      rider_last_out_places<NCH>(u, W.place);
       return;
     }
     if (stage == kSideMergePlace) {
-      // the chunk sorts ran in the PREVIOUS launch (hop 0, kSideSort): rank this rider's chunk; the last rider out decides the placement
-      const int chunks = (int)((u.m + kChunk - 1) / kChunk);
-      __shared__ int last_mp;
       update_merge_riding<1, NCH, true>(u, block, W.smp);
-      __syncthreads();  // every thread's device-coherent stores have completed
-      if (threadIdx.x == 0) {
-        const int prev = __hip_atomic_fetch_add(&u.barrier[5], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        last_mp = prev == chunks - 1;
-        if (last_mp) __hip_atomic_store(&u.barrier[5], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // zero for the next launch
-      }
-      __syncthreads();
-      if (!last_mp) return;
-      SortLds<1> none;
-      update_block_body<NCH, PCAP, true, true, true>(u, W.place, none);
+      rider_last_out_places<NCH>(u, W.place);
       return;
     }
     if (stage == kSideAll) {
@@ -1005,11 +1007,10 @@ __device__ __forceinline__ void update_side_work(const UpdateArgs& u, int stage,
         if (c < chunks) update_chunk_sort(u, c, W.sort);
         __syncthreads();  // W.sort is reused; the chunk-sorted pairs written above are read below by other threads
       }
-    }
-    if (stage != kSidePlaceOnly) {  // (kSidePlaceOnly: the hop-0 launch's riders merged already -- kSideSortMerge)
       update_merge_riding<NCH, NCH>(u, 0, W.smp);
       __syncthreads();  // the sorted arrays written above are read below by other threads of this workgroup
     }
+    // kSideAll, kSidePlaceOnly (the previous launch's riders merged already)
     SortLds<1> none;
     update_block_body<NCH, PCAP, true, true>(u, W.place, none);
   }
@@ -2481,11 +2482,11 @@ static int fused_rows_per_wave(int k0) {
   return g > k0 ? k0 : g;
 }
 
-// hop 0 (a: seeds / groups, k, outputs) and hop 1 (k1, out_*1) as one launch; the caller checked can_fuse01
+// hop 0 (a: seeds / groups, k, outputs) and hop 1 (k1, out_*1) as one launch; the caller checked plan_fuse01
 // commit (RING, optional): the previous batch's deferred commit, run by ceil(m / 4) workgroups behind the riders
 template <bool RING>
 static int launch_fused01(LookupArgs a, hipStream_t stream, hipEvent_t ev_start, hipEvent_t ev_stop, const UpdateArgs* side,
-                          int side_stage, unsigned side_blocks, const UpdateArgs* commit = nullptr) {
+                          int side_stage, unsigned side_blocks, int pcap, const UpdateArgs* commit = nullptr) {
   const UpdateArgs u = side ? *side : UpdateArgs{};
   const UpdateArgs c = (RING && commit) ? *commit : UpdateArgs{};
   a.side_blocks = (RING && side) ? side_blocks : 0;
@@ -2502,8 +2503,9 @@ static int launch_fused01(LookupArgs a, hipStream_t stream, hipEvent_t ev_start,
   if (blocks > (1 << 20)) blocks = 1 << 20;
   const dim3 grid((unsigned)blocks + a.side_blocks + a.commit_blocks), block(waves_per_block * kWave);
   const size_t lds = (size_t)waves_per_block * kmax * sizeof(int);
-  // the riders' static LDS sized for what rides (RiderLds): placement of <= 512 entries, of <= 1024, or sort / merge only
-  const int pcap = !(RING && side) ? 1024 : ((side_stage != kSideAll && side_stage != kSideSortMergePlace) ? 0 : (u.m <= 512 ? 512 : 1024));
+  // pcap: the riders' static LDS sized for what rides (RiderLds, RiderPlan.pcap): placement of <= 512 entries, of <= 1024, or
+  // sort / merge only
+  if (!(RING && side)) pcap = kRidePlaceMaxM;  // nothing rides
   if (RING && vec == 4 && pcap == 512 && fused_ts_path()) {
     static long long* ts_buf = nullptr;
     static size_t ts_cap = 0;
@@ -2887,18 +2889,6 @@ static void launch_update_presorted(const UpdateArgs& a, hipStream_t st) {
   if (a.D > 0) hipLaunchKernelGGL(ring_update_feat_kernel<false>, dim3((unsigned)((a.m + 3) / 4)), dim3(256), 0, st, a);
 }
 
-// 1024 < m <= 4096 next to the lookups (side stream): chunk sort, merge (+ pre-gather), placement decisions; nothing here
-// writes ring state.  The commit (ring_update_feat_kernel<true>) follows the lookups on the main stream.
-static void launch_update_mid_front(const UpdateArgs& a, unsigned chunks, hipStream_t st) {
-  hipLaunchKernelGGL(ring_update_chunk_sort_kernel, dim3(chunks), dim3(kChunk), 0, st, a);
-  hipLaunchKernelGGL(ring_update_merge_kernel, dim3(chunks), dim3(kChunk), 0, st, a);
-  int P = 64;
-  while (P < a.m) P <<= 1;
-  constexpr unsigned parts = 8;
-  if (P <= 2048) hipLaunchKernelGGL((ring_update_decide_kernel<2, 2048>), dim3(parts), dim3(1024), 0, st, a);
-  else hipLaunchKernelGGL((ring_update_decide_kernel<4, 4096>), dim3(parts), dim3(1024), 0, st, a);
-}
-
 static void launch_update_block(UpdateArgs& a, int32_t* scratch, hipStream_t st) {
   int P = 64;
   while (P < a.m) P <<= 1;
@@ -3278,8 +3268,7 @@ static SideStream* side_stream_for_current_device() {
     // whole chip busy, and every one of its launches would otherwise queue behind that launch's workgroups
     int prio_lo = 0, prio_hi = 0;
     (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-    static const bool no_prio = getenv("TGMX_SIDE_NO_PRIO") != nullptr;  // A/B knob
-    if (hipStreamCreateWithPriority(&s.stream, hipStreamNonBlocking, no_prio ? prio_lo : prio_hi) != hipSuccess) return nullptr;
+    if (hipStreamCreateWithPriority(&s.stream, hipStreamNonBlocking, prio_hi) != hipSuccess) return nullptr;
     if (hipEventCreateWithFlags(&s.fork, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&s.join, hipEventDisableTiming) != hipSuccess) {
       s.stream = nullptr;
@@ -3388,14 +3377,58 @@ static bool plan_fuse01(const tgmx_recency_step_t* s, long long S0) {
   return true;
 }
 
+// ---- the rider schedule: the table above SideStage, as one pure function of sizes ---------------------------------------------
+struct RiderPlan {
+  int stage[2];        // SideStage riding lookup launch 0 (hop 0, or the fused hop 0 + 1 launch) and launch 1 (hop 1 when not fused)
+  unsigned blocks[2];  // its rider workgroups; 0: nothing rides
+  int pcap;            // fused launch: placement capacity of the riders' LDS (RiderLds)
+  int after;           // AfterLookups: what follows the last lookup
+};
+
+// m: ring entries of the batch (0: no update); S: hop-0 seeds; fused: plan_fuse01; rings: streaming (the static index takes no update)
+static RiderPlan plan_riders(long long m, int n_hops, long long S, bool fused, bool rings) {
+  if (!rings || m <= 0) return {};
+  if (m > kBlockMaxM) return {{}, {}, 0, kAfterLarge};
+  if (n_hops <= 0 || S <= 0 || getenv_no_ride()) return {{}, {}, 0, kAfterBlock};
+  const unsigned chunks = (unsigned)((m + kChunk - 1) / kChunk);
+  if (fused) {
+    if (m <= 512) return {{kSideAll}, {1}, 512, kAfterCommit};
+    if (m <= kRidePlaceMaxM) return {{kSideSortMergePlace}, {chunks}, 1024, kAfterCommit};
+    return {{kSideSortMerge}, {chunks}, 0, kAfterPresorted};
+  }
+  if (n_hops == 1) return {{kSideSort}, {chunks}, 0, kAfterMergePresorted};
+  if (chunks == 1) return {{kSideSortMerge, kSidePlaceOnly}, {1, 1}, 0, kAfterCommit};
+  if (m <= kRidePlaceMaxM) return {{kSideSort, kSideMergePlace}, {chunks, chunks}, 0, kAfterCommit};
+  return {{kSideSort, kSideMerge}, {chunks, chunks}, 0, kAfterPresorted};
+}
+
+// hop-0 seeds of an argument block: the groups' concatenation, or S0
+static long long hop0_seed_count(const tgmx_recency_step_t* s) {
+  if (s->n_groups <= 0) return s->S0;
+  long long S = 0;
+  for (int g = 0; g < s->n_groups && g < TGMX_MAX_SEED_GROUPS; ++g) S += s->grp_n[g];
+  return S;
+}
+
+static long long ring_entries(const tgmx_recency_step_t* s) { return s->n <= 0 ? 0 : (s->directed ? s->n : 2 * s->n); }
+
 extern "C" int tgmx_recency_step_plan(const tgmx_recency_step_t* s) {
   if (!s) return 0;
-  long long S0 = s->S0;
-  if (s->n_groups > 0) {
-    S0 = 0;
-    for (int g = 0; g < s->n_groups && g < TGMX_MAX_SEED_GROUPS; ++g) S0 += s->grp_n[g];
-  }
-  return plan_fuse01(s, S0) ? 1 : 0;
+  const long long S = hop0_seed_count(s);
+  const bool fused = plan_fuse01(s, S);
+  const RiderPlan p = plan_riders(ring_entries(s), s->n_hops, S, fused, s->indptr == nullptr);
+  return (fused ? TGMX_PLAN_FUSED01 : 0) | p.stage[0] << 4 | p.stage[1] << 8 | (int)p.blocks[0] << 12 | (int)p.blocks[1] << 17 |
+         (p.pcap / 512) << 22 | p.after << 24;
+}
+
+// what every lookup launch of a step shares: the index, the status word, the sizes, the event window
+static LookupArgs step_lookup_args(const tgmx_recency_step_t* s) {
+  LookupArgs a{};
+  a.indptr = s->indptr; a.recs = reinterpret_cast<const Rec*>(s->ring); a.write_pos = s->write_pos; a.edge_x = s->ring_x;
+  a.status = s->status; a.D = s->D; a.B = s->B; a.N = s->num_nodes;
+  a.ev_lo = s->ev_lo; a.ev_hi = s->ev_hi;
+  a.x_by_pos = s->indptr && s->csr_x_by_pos;
+  return a;
 }
 
 extern "C" int tgmx_recency_step(const tgmx_recency_step_t* s, tgmx_stream_t stream) {
@@ -3414,9 +3447,8 @@ extern "C" int tgmx_recency_step(const tgmx_recency_step_t* s, tgmx_stream_t str
   // ---- hop-0 seeds: groups are concatenated by the hop-0 lookup itself (or by nothing when there is no hop)
   SeedGroups grp{};
   grp.gen = -1;
-  long long S = s->S0;
+  long long S = hop0_seed_count(s);
   if (s->n_groups > 0) {
-    S = 0;
     const int gen = s->neg_out ? s->neg_group : -1;  // negatives generated in place of seed group neg_group
     TGMX_REQUIRE(gen < s->n_groups, "recency_step: neg_group=%d but %d seed groups", gen, s->n_groups);
     if (gen >= 0) {
@@ -3424,34 +3456,36 @@ extern "C" int tgmx_recency_step(const tgmx_recency_step_t* s, tgmx_stream_t str
       grp.gen = gen; grp.gen_low = s->neg_low; grp.gen_range = (unsigned)((long long)s->neg_high - s->neg_low);
       grp.gen_seed = s->neg_seed; grp.gen_call = s->neg_call; grp.gen_index0 = (unsigned long long)s->neg_index0; grp.gen_out = s->neg_out; grp.gen_out_ts = s->neg_time_out;
     }
+    long long end = 0;
     for (int g = 0; g < s->n_groups; ++g) {
       TGMX_REQUIRE(s->grp_n[g] >= 0 && (s->grp_n[g] == 0 || ((g == gen || s->grp_nid[g]) && s->grp_ts[g])), "recency_step: seed group %d", g);
-      S += s->grp_n[g];
-      grp.nid[g] = s->grp_nid[g]; grp.ts[g] = s->grp_ts[g]; grp.end[g] = S;
+      end += s->grp_n[g];
+      grp.nid[g] = s->grp_nid[g]; grp.ts[g] = s->grp_ts[g]; grp.end[g] = end;
     }
     TGMX_REQUIRE(S == 0 || (s->seed_nid0 && s->seed_ts0), "recency_step: null hop-0 seed output");
     TGMX_REQUIRE(S == 0 || s->n_hops > 0, "recency_step: seed groups need at least one hop");
     grp.out_nid = s->seed_nid0; grp.out_ts = s->seed_ts0; grp.groups = s->n_groups;
   }
 
+  // ---- what rides which lookup launch and what follows the last one (the table above SideStage)
+  const bool fused = plan_fuse01(s, S);
+  const RiderPlan plan = plan_riders(ring_entries(s), s->n_hops, S, fused, !csr);
+
   // ---- deferred commit: does this call defer its own (and run the pending one inside its lookup launch)?  Else whatever is
-  // pending is committed first, and the call runs as without deferral
+  // pending is committed first, and the call runs as without deferral.  (Only the fused launch with a riding placement -- m <= 1024,
+  // kAfterCommit -- can carry and leave a commit.)
   tgmx_defer* dfr = csr ? nullptr : s->defer;
   static const bool defer_on = !(getenv("TGMX_DEFER_COMMIT") && atoi(getenv("TGMX_DEFER_COMMIT")) == 0);  // A/B knob
-  const long long m_all = s->directed ? s->n : 2 * s->n;
-  const bool defer = dfr && defer_on && s->defer_ok && s->n > 0 && m_all <= kRidePlaceMaxM && s->n_hops == 2 && S > 0 && !s->guard_seed_errors &&
-                     s->eid0 >= 0 && dfr->N == s->num_nodes && dfr->B == s->B &&
-                     (long long)s->B * s->num_nodes + s->n < 2147483647LL && plan_fuse01(s, S) && !getenv_no_ride();
+  const bool defer = dfr && defer_on && s->defer_ok && fused && plan.after == kAfterCommit && s->n_hops == 2 && !s->guard_seed_errors &&
+                     s->eid0 >= 0 && dfr->N == s->num_nodes && dfr->B == s->B && (long long)s->B * s->num_nodes + s->n < 2147483647LL;
   if (dfr && dfr->pending && !defer)
     if (const int rf = tgmx_defer_flush(dfr, stream)) return rf;
   if (defer)
     if (const int rb = defer_buffers(dfr, st)) return rb;
 
   // ---- ring update, front half: batches of up to kBlockMaxM entries are sorted by workgroups riding along with the
-  // lookup launches (chunk sort with hop 0, merge with hop 1); only the placement runs after the lookups
+  // lookup launches; at most the placement and the commit run after the lookups
   UpdateArgs u{};
-  unsigned side_chunks = 0;
-  bool ride_place = false;  // m <= 1024: hop 1 carries the merge AND the placement decisions
   const unsigned stamp = defer ? dfr->stamp + 1 : 0u;  // (the stamp of this batch: 1, 2, ...; never 0)
   int32_t* scratch = defer ? dfr->scratch[stamp & 1] : s->scratch;
   if (s->n > 0) {
@@ -3461,30 +3495,19 @@ extern "C" int tgmx_recency_step(const tgmx_recency_step_t* s, tgmx_stream_t str
     u.ts_bound = s->ts_bound;
     u.guard_mask = s->guard_seed_errors ? (TGMX_ST_SEED_RANGE | TGMX_ST_SEED_TIME) : 0;
     u.sorted_ts = s->sorted_ts;
-    if (u.m <= kBlockMaxM && s->n_hops > 0 && S > 0 && !getenv_no_ride()) side_chunks = set_chunk_scratch(u, scratch + kScratchHead);
-    ride_place = side_chunks > 0 && u.m <= kRidePlaceMaxM && s->n_hops >= 2;
+    if (plan.blocks[0] > 0) set_chunk_scratch(u, scratch + kScratchHead);
   }
   if (defer) {
     const int q = (int)(stamp & 1);
     u.dhdr = dfr->hdr[q]; u.drec = dfr->rec[q]; u.dslot = dfr->slot[q]; u.dstamp = stamp;
     if (dfr->pending) { u.phdr = dfr->hdr[q ^ 1]; u.pstamp = dfr->stamp; }
   }
-  // 1024 < m <= 4096 (the replicated update of a 4- / 8-rank global wiki batch): the front half -- sort, merge, placement
-  // decisions -- CAN run on the side stream next to the lookups instead of riders + a placement launch behind them.
-  // Measured on MI355X and rejected: the fork / join dependency between the streams costs more than the placement launch it
-  // hides (wiki, rank 7 of 8: 84.1 vs 60.4 us per step; rank 3 of 4: 70.4 vs 53.2).  Off unless TGMX_SIDE_MID=1 (A/B knob).
-  static const bool no_side_mid = getenv("TGMX_SIDE_MID") == nullptr;
-  SideStream* mid = nullptr;
-  if (side_chunks > 0 && !ride_place && u.m > kRidePlaceMaxM && !no_side_mid && (mid = side_stream_for_current_device()) != nullptr) {
-    (void)hipEventRecord(mid->fork, st);  // the batch's inputs and the previous batch's ring writes are complete
-    (void)hipStreamWaitEvent(mid->stream, mid->fork, 0);
-    launch_update_mid_front(u, side_chunks, mid->stream);
-    (void)hipEventRecord(mid->join, mid->stream);
-    side_chunks = 0;  // no riders in the lookup launches
-  }
+  // (1024 < m <= 4096 with sort, merge and placement decisions on the side stream instead of riders + a placement launch was
+  // measured on MI355X and rejected: the fork / join between the streams costs more than the placement launch it hides -- wiki,
+  // rank 7 of 8: 84.1 vs 60.4 us per step; rank 3 of 4: 70.4 vs 53.2.)
   SideStream* side = nullptr;  // set: the large update's front half runs on the side stream next to the lookups
   bool side_pending = false;   // its launches are enqueued BEHIND the first lookup launch (below)
-  if (s->n > 0 && u.m > kBlockMaxM && s->n_hops > 0 && S > 0 && (side = side_stream_for_current_device()) != nullptr) {
+  if (plan.after == kAfterLarge && s->n_hops > 0 && S > 0 && (side = side_stream_for_current_device()) != nullptr) {
     (void)hipEventRecord(side->fork, st);  // the batch's inputs and the previous batch's ring writes are complete
     (void)hipStreamWaitEvent(side->stream, side->fork, 0);
     side_pending = true;
@@ -3508,38 +3531,30 @@ extern "C" int tgmx_recency_step(const tgmx_recency_step_t* s, tgmx_stream_t str
   const int32_t* cur_n = s->seed_nid0;
   const int64_t* cur_t = s->seed_ts0;
   int h = 0;
-  if (plan_fuse01(s, S)) {
+  if (fused) {
     const int k0 = s->k[0], k1 = s->k[1];
     TGMX_REQUIRE(s->B >= k0 && s->B >= k1, "recency_step: k=[%d, %d] but B=%d", k0, k1, s->B);
     TGMX_REQUIRE(cur_n && cur_t && s->out_nid[0] && s->out_ts[0] && s->out_nid[1] && s->out_ts[1] &&
                      (s->D == 0 || (s->ring_x && (s->out_x[0] || s->out_eid[0]) && (s->out_x[1] || s->out_eid[1]))), "recency_step: null pointer at hop 0 / 1");
-    LookupArgs a{};
+    LookupArgs a = step_lookup_args(s);
     a.grp = grp;
-    a.indptr = s->indptr; a.recs = reinterpret_cast<const Rec*>(s->ring); a.write_pos = s->write_pos; a.edge_x = s->ring_x;
     a.seeds = cur_n; a.qtimes = cur_t; a.out_nid = s->out_nid[0]; a.out_ts = s->out_ts[0]; a.out_x = s->out_x[0];
     a.k1 = k1; a.out_nid1 = s->out_nid[1]; a.out_ts1 = s->out_ts[1]; a.out_x1 = s->out_x[1];
     a.out_valid = s->out_valid[0]; a.out_valid1 = s->out_valid[1];
     a.out_valid_prev = s->out_valid_prev[0]; a.out_valid_prev1 = s->out_valid_prev[1];
     a.out_eid = s->out_eid[0]; a.out_eid1 = s->out_eid[1];
-    a.status = s->status; a.S = S; a.D = s->D; a.k = k0; a.B = s->B; a.N = s->num_nodes; a.allow_pad = 0;
-    a.ev_lo = s->ev_lo; a.ev_hi = s->ev_hi;
-    a.x_by_pos = csr && s->csr_x_by_pos;
+    a.S = S; a.k = k0; a.allow_pad = 0;
     const bool timed = s->timed_hop == 0 || s->timed_hop == 1;
     hipEvent_t e0 = timed ? (hipEvent_t)s->ev_start : nullptr, e1 = timed ? (hipEvent_t)s->ev_stop : nullptr;
-    // riders: m <= 512 -> one workgroup does it all and only the commit follows; 512 < m <= 1024 -> a rider per chunk, the last one
-    // out places (TGMX_THREE_PHASE=0: one workgroup, A/B); else sort | barrier | merge and the placement is its own launch
-    static const bool three_phase_on = !(getenv("TGMX_THREE_PHASE") && atoi(getenv("TGMX_THREE_PHASE")) == 0);
-    const bool three_phase = three_phase_on && ride_place && u.m > 512;
     const bool commit = defer && dfr->pending;  // the previous batch's commit rides this launch
     if (commit) {
       a.phdr = u.phdr; a.pstamp = u.pstamp;
       a.prec = dfr->rec[(stamp & 1) ^ 1]; a.pslot = dfr->slot[(stamp & 1) ^ 1];
       a.pstore = s->D > 0 ? dfr->pend.edge_x : nullptr; a.peid0 = (int)dfr->pend.eid0;
     }
-    const int rc = csr ? launch_fused01<false>(a, st, e0, e1, nullptr, 0, 0)
-                       : launch_fused01<true>(a, st, e0, e1, side_chunks > 0 ? &u : nullptr,
-                                              ride_place ? (three_phase ? kSideSortMergePlace : kSideAll) : kSideSortMerge,
-                                              (ride_place && !three_phase) ? 1u : side_chunks, commit ? &dfr->pend : nullptr);
+    const int rc = csr ? launch_fused01<false>(a, st, e0, e1, nullptr, 0, 0, 0)
+                       : launch_fused01<true>(a, st, e0, e1, plan.blocks[0] > 0 ? &u : nullptr, plan.stage[0], plan.blocks[0], plan.pcap,
+                                              commit ? &dfr->pend : nullptr);
     if (rc) return rc;
     if (const int rs = enqueue_side()) return rs;
     cur_n = s->out_nid[1];
@@ -3552,33 +3567,19 @@ extern "C" int tgmx_recency_step(const tgmx_recency_step_t* s, tgmx_stream_t str
     TGMX_REQUIRE(k > 0 && s->B >= k, "recency_step: hop %d has k=%d, B=%d", h, k, s->B);
     TGMX_REQUIRE(cur_n && cur_t && s->out_nid[h] && s->out_ts[h] && (s->D == 0 || (s->ring_x && (s->out_x[h] || s->out_eid[h]))),
                  "recency_step: null pointer at hop %d", h);
-    LookupArgs a{};
+    LookupArgs a = step_lookup_args(s);
     if (h == 0) a.grp = grp;
-    a.indptr = s->indptr; a.recs = reinterpret_cast<const Rec*>(s->ring); a.write_pos = s->write_pos; a.edge_x = s->ring_x;
     a.seeds = cur_n; a.qtimes = cur_t; a.out_nid = s->out_nid[h]; a.out_ts = s->out_ts[h]; a.out_x = s->out_x[h];
     a.out_valid = s->out_valid[h]; a.out_valid_prev = s->out_valid_prev[h];
     a.out_eid = s->out_eid[h];
-    a.status = s->status; a.S = S; a.D = s->D; a.k = k; a.B = s->B; a.N = s->num_nodes; a.allow_pad = h > 0;
-    a.ev_lo = s->ev_lo; a.ev_hi = s->ev_hi;
+    a.S = S; a.k = k; a.allow_pad = h > 0;
     a.cursor = csr ? reinterpret_cast<long long*>(s->csr_cursor) : nullptr;
-    a.x_by_pos = csr && s->csr_x_by_pos;
     a.leave_room = side != nullptr;
     const bool timed = h == s->timed_hop;
     hipEvent_t e0 = timed ? (hipEvent_t)s->ev_start : nullptr, e1 = timed ? (hipEvent_t)s->ev_stop : nullptr;
-    const bool ride = side_chunks > 0 && h < 2;
-    // m <= 1024, two lookup launches: the merge rides hop 0 with the chunk sorts (its riders meet at a barrier), hop 1's single rider
-    // only decides the placement -- the one workgroup that merged AND placed made hop 1 last 17.7 us at the review shape (TGMX_SPLIT_MERGE=0: A/B)
-    static const bool split_merge_on = !(getenv("TGMX_SPLIT_MERGE") && atoi(getenv("TGMX_SPLIT_MERGE")) == 0);
-    const bool split_merge = split_merge_on && ride_place && s->n_hops >= 2;
-    // round 6: hop 0 carries the chunk sorts only, hop 1 the merge (a rider per chunk) + the placement (the last rider out): the riders no
-    // longer pace the first launch (TGMX_MERGE_LATE=0: sort + barrier + merge in hop 0, placement in hop 1, as in rounds 3-5 -- A/B)
-    static const bool merge_late_on = !(getenv("TGMX_MERGE_LATE") && atoi(getenv("TGMX_MERGE_LATE")) == 0);
-    const bool merge_late = merge_late_on && split_merge && side_chunks > 1;
-    const int stage = h == 0 ? ((split_merge && !merge_late) ? kSideSortMerge : kSideSort)
-                             : (ride_place ? (merge_late ? kSideMergePlace : (split_merge ? kSidePlaceOnly : kSidePlace)) : kSideMerge);
+    const bool ride = h < 2 && plan.blocks[h] > 0;  // (after a fused launch h >= 2: nothing rides)
     const int rc = csr ? launch_lookup<false>(a, st, e0, e1)
-                       : launch_lookup<true>(a, st, e0, e1, ride ? &u : nullptr, stage,
-                                             (h == 1 && ride_place && !merge_late) ? 1u : side_chunks);
+                       : launch_lookup<true>(a, st, e0, e1, ride ? &u : nullptr, ride ? plan.stage[h] : 0, ride ? plan.blocks[h] : 0u);
     if (rc) return rc;
     if (const int rs = enqueue_side()) return rs;
     cur_n = s->out_nid[h];
@@ -3588,29 +3589,24 @@ extern "C" int tgmx_recency_step(const tgmx_recency_step_t* s, tgmx_stream_t str
   if (const int rs = enqueue_side()) return rs;
 
   // ---- ring update (after every lookup, recency.py:161-163)
-  if (s->n > 0) {
-    if (mid) {
-      (void)hipStreamWaitEvent(st, mid->join, 0);
-      hipLaunchKernelGGL(ring_update_feat_kernel<true>, dim3((unsigned)((u.m + 3) / 4)), dim3(256), 0, st, u);
-    } else if (defer) {
-      // deferred: committed by the next deferring call's lookup launch, or by the flush in front of any other call
-      dfr->pend = u;
-      dfr->pending = true;
-      dfr->stamp = stamp;
-      ++dfr->deferred;
-    } else if (ride_place) {
-      hipLaunchKernelGGL(ring_update_feat_kernel<true>, dim3((unsigned)((u.m + 3) / 4)), dim3(256), 0, st, u);
-    } else if (side_chunks > 0) {
-      if (s->n_hops < 2) hipLaunchKernelGGL(ring_update_merge_kernel, dim3(side_chunks), dim3(kChunk), 0, st, u);
-      launch_update_presorted(u, st);
-    } else if (u.m <= kBlockMaxM) {
-      launch_update_block(u, s->scratch + kScratchHead, st);
-    } else if (side) {
-      (void)hipStreamWaitEvent(st, side->join, 0);
-      launch_update_large_back(u, st);
-    } else if (const int rl = launch_update_large(u, s->scratch + kScratchHead, st)) {
-      return rl;
-    }
+  if (defer) {
+    // in place of kAfterCommit: committed by the next deferring call's lookup launch, or by the flush in front of any other call
+    dfr->pend = u;
+    dfr->pending = true;
+    dfr->stamp = stamp;
+    ++dfr->deferred;
+  } else if (plan.after == kAfterCommit) {
+    hipLaunchKernelGGL(ring_update_feat_kernel<true>, dim3((unsigned)((u.m + 3) / 4)), dim3(256), 0, st, u);
+  } else if (plan.after == kAfterPresorted || plan.after == kAfterMergePresorted) {
+    if (plan.after == kAfterMergePresorted) hipLaunchKernelGGL(ring_update_merge_kernel, dim3(plan.blocks[0]), dim3(kChunk), 0, st, u);
+    launch_update_presorted(u, st);
+  } else if (plan.after == kAfterBlock) {
+    launch_update_block(u, s->scratch + kScratchHead, st);
+  } else if (plan.after == kAfterLarge && side) {
+    (void)hipStreamWaitEvent(st, side->join, 0);
+    launch_update_large_back(u, st);
+  } else if (plan.after == kAfterLarge) {
+    if (const int rl = launch_update_large(u, s->scratch + kScratchHead, st)) return rl;
   }
   TGMX_CHECK_LAUNCH("recency_step");
   return TGMX_OK;
