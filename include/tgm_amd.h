@@ -1208,6 +1208,44 @@ typedef struct tgmx_ncn_fwd {
 } tgmx_ncn_fwd_t;
 int tgmx_ncn_forward(const tgmx_ncn_fwd_t* args, tgmx_stream_t stream);
 
+/* ---- EdgeBankPredictor (the reference's tgm/nn/modules/edgebank.py): the edge memory as a device hash table ---- */
+
+/* table: capacity slots of 16 bytes {uint64 key = src << 32 | dst, int64 ts}, open addressing with linear probing from
+ * splitmix64(key) & (capacity - 1); capacity a power of two; an empty slot has key = all ones (and the caller fills a new table so).  stamp
+ * [capacity] int64, zeroed with a new table: the arrival number of the event whose ts the slot holds (only the update reads or writes it).
+ * state: tgmx_edgebank_state_bytes() bytes {int64 window_end, int64 window_size (unlimited mode), float32 window_size (fixed mode), pad};
+ * the window start is window_end - window_size in int64, or (float)window_end - window_size in float32 when fixed.  status: one int32 of
+ * sticky bits: 1 = an id outside [0, 2^31) was offered or queried (it contributes nothing / answers 0), 2 = a probe ran through the whole
+ * table (the caller let it fill: capacity must stay >= 2 x the entries). */
+typedef struct tgmx_edgebank {
+  void* table; int64_t* stamp; int64_t capacity;
+  void* state;
+  int32_t fixed, reserved_;                                     /* fixed: memory_mode == 'fixed' */
+  double pos_prob;                                              /* what a hit answers, cast to the output dtype as torch casts it */
+  int64_t arrivals;                                             /* events offered to tgmx_edgebank_update before this call */
+  int32_t* status;
+} tgmx_edgebank_t;
+size_t tgmx_edgebank_state_bytes(void);
+
+/* One batch of the reference's update(): window_end = max(window_end, max ts); then every event with ts >= the new window start (fixed
+ * mode: both sides rounded to float32) stores its ts under (src, dst), and of several events of one pair the LAST in arrival order (position
+ * in the call, then call order) is the one kept, whatever its ts.  ids / ts int64 where the *_is64 flag is set, else int32.  n <= 1024 is
+ * one workgroup and one launch, more is three launches.  No float atomics, nothing depends on scheduling but the slot positions. */
+int tgmx_edgebank_update(const tgmx_edgebank_t* eb, const void* src, int32_t src_is64, const void* dst, int32_t dst_is64, const void* ts,
+                         int32_t ts_is64, int64_t n, tgmx_stream_t stream);
+
+/* out[i] = pos_prob where the pair is stored (fixed mode: and its int64 ts >= the float32 window start, compared exactly), else 0; one lane
+ * per answer.  neg == NULL: `total` = B pairs (src[i], dst[i]).  Otherwise row b answers (src[b], dst[b]) and then (src[b], neg[b][m]): neg
+ * is [B, M] with neg_off == NULL (total = B (M + 1)), or the rows laid end to end with neg_off [B + 1] their int64 offsets (total = B +
+ * neg_off[B]); row b's answers start at neg_off[b] + b.  out_dtype: 0 int32, 1 int64, 2 float32, 3 float64. */
+int tgmx_edgebank_query(const tgmx_edgebank_t* eb, const void* src, int32_t src_is64, const void* dst, int32_t dst_is64, const void* neg,
+                        int32_t neg_is64, const int64_t* neg_off, int64_t M, int64_t B, int64_t total, void* out, int32_t out_dtype,
+                        tgmx_stream_t stream);
+
+/* Moves the entries of `from` into `to` (a new, empty table of at least twice the capacity); in fixed mode entries whose ts has left the
+ * window (the update's test, against from->state) are dropped, as the reference's _clean_up drops them.  *kept (device) = entries moved. */
+int tgmx_edgebank_rehash(const tgmx_edgebank_t* from, const tgmx_edgebank_t* to, int64_t* kept, tgmx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

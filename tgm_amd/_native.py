@@ -483,6 +483,25 @@ SIGNATURES['tgmx_ncn_adj_build'] = (c_int32, [_P, c_int32, c_int64, c_int64, c_i
 SIGNATURES['tgmx_ncn_cn_emb'] = (c_int32, [_P, c_int64, c_int32, c_int32, _P, _P, _P, c_int32, c_int64, c_int64, _P, _P, _P, _P, c_int64, _P])
 SIGNATURES['tgmx_ncn_forward'] = (c_int32, [ctypes.POINTER(NCNFwd), _P])
 
+
+class EdgeBank(ctypes.Structure):
+    """tgmx_edgebank_t (include/tgm_amd.h)."""
+
+    _fields_ = [
+        ('table', c_void_p), ('stamp', c_void_p), ('capacity', c_int64),
+        ('state', c_void_p),
+        ('fixed', c_int32), ('reserved_', c_int32),
+        ('pos_prob', ctypes.c_double),
+        ('arrivals', c_int64),
+        ('status', c_void_p),
+    ]  # fmt: skip
+
+
+SIGNATURES['tgmx_edgebank_state_bytes'] = (c_size_t, [])
+SIGNATURES['tgmx_edgebank_update'] = (c_int32, [ctypes.POINTER(EdgeBank), _P, c_int32, _P, c_int32, _P, c_int32, c_int64, _P])
+SIGNATURES['tgmx_edgebank_query'] = (c_int32, [ctypes.POINTER(EdgeBank), _P, c_int32, _P, c_int32, _P, c_int32, _P, c_int64, c_int64, c_int64, _P, c_int32, _P])
+SIGNATURES['tgmx_edgebank_rehash'] = (c_int32, [ctypes.POINTER(EdgeBank), ctypes.POINTER(EdgeBank), _P, _P])
+
 _lib: Optional[ctypes.CDLL] = None
 
 
