@@ -1246,6 +1246,47 @@ int tgmx_edgebank_query(const tgmx_edgebank_t* eb, const void* src, int32_t src_
  * window (the update's test, against from->state) are dropped, as the reference's _clean_up drops them.  *kept (device) = entries moved. */
 int tgmx_edgebank_rehash(const tgmx_edgebank_t* from, const tgmx_edgebank_t* to, int64_t* kept, tgmx_stream_t stream);
 
+/* ---- tCoMemPredictor (the reference's tgm/nn/modules/t_comem.py): recent-event rings, popularity and pair counts on the device ---- */
+
+/* ring: [num_nodes, k] entries of 8 bytes {float32 ts, int32 dst}, the k most recent events with the node as source; the caller fills a new
+ * ring with {-inf, -1}.  pos, len, popularity: [num_nodes] int32, zeroed: where the node's next event goes, how many entries are filled
+ * (<= k), how often the node was a destination.  table: the pair counts, slots as tgmx_edgebank_t's with key = min(s, d) << 32 | max(s, d)
+ * and value = the count (a self-loop counts 2: the reference increments [s][d] and [d][s]); filled {all ones, 0} when new.  state:
+ * tgmx_tcomem_state_bytes() bytes {int64 end = the largest timestamp seen, float32 size = the window size, pad}; the window is
+ * [f32(f32(end) - size), f32(end)].  status: one int32 of sticky bits: 1 = an id outside [0, 2^31), 2 = a probe ran through the whole table
+ * (capacity must stay >= 2 x the pairs), 4 = a source >= num_nodes, 8 = an update's destination >= num_nodes.  A flagged event contributes
+ * nothing, a flagged query answers 0. */
+typedef struct tgmx_tcomem {
+  void* ring; int32_t *pos, *len, *popularity;
+  void* table; int64_t capacity;
+  void* state;
+  int64_t num_nodes; int32_t k, reserved_;
+  double co_occurrence_weight;
+  int32_t* status;
+} tgmx_tcomem_t;
+size_t tgmx_tcomem_state_bytes(void);
+
+/* One batch of the reference's update(), in event order: end = max(end, max ts); per event the pair's count += 1 (2 for a self-loop),
+ * popularity[dst] += 1, and the event {f32(ts), dst} goes to ring[src][pos], pos advancing modulo k and len saturating at k, whatever the
+ * timestamp.  ids / ts int64 where the *_is64 flag is set, else int32.  One workgroup and one launch per 1024 events, in arrival order.
+ * Integer atomics only; nothing depends on scheduling but the slot positions in the table. */
+int tgmx_tcomem_update(const tgmx_tcomem_t* tc, const void* src, int32_t src_is64, const void* dst, int32_t dst_is64, const void* ts,
+                       int32_t ts_is64, int64_t n, tgmx_stream_t stream);
+
+/* out (float32) = base(src) + the co-occurrence term.  base(s) = sum over ring entries i < len[s] with start <= ts <= f32(end) of
+ * exp(-(f32(end) - ts) / size) * sigmoid(popularity[dst]) in float32, the same bits for a source wherever it appears.  With c the pair's
+ * count and t = co_occurrence_weight * (c / (1 + c)) in double, query_dtype (the dtype of the ids the reference would have been handed:
+ * 0 int32, 1 int64, 2 float32, 3 float64) decides the term as the reference's zeros_like(query_src) does: 0 / 1 add nothing, 2 adds
+ * (float)t in float32, 3 adds t in double and rounds the sum.  Rows as in tgmx_edgebank_query, one wave per row: neg == NULL: `total` = B
+ * pairs; else row b answers (src[b], dst[b]) and then (src[b], neg[b][m]), neg [B, M] (total = B (M + 1)) or ragged through neg_off [B + 1]
+ * (total = B + neg_off[B]; row b's answers start at neg_off[b] + b). */
+int tgmx_tcomem_query(const tgmx_tcomem_t* tc, const void* src, int32_t src_is64, const void* dst, int32_t dst_is64, const void* neg,
+                      int32_t neg_is64, const int64_t* neg_off, int64_t M, int64_t B, int64_t total, float* out, int32_t query_dtype,
+                      tgmx_stream_t stream);
+
+/* Moves the pair counts of `from` into `to` (a new, empty table of at least twice the capacity).  *kept (device) = pairs moved. */
+int tgmx_tcomem_rehash(const tgmx_tcomem_t* from, const tgmx_tcomem_t* to, int64_t* kept, tgmx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

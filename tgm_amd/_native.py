@@ -502,6 +502,25 @@ SIGNATURES['tgmx_edgebank_update'] = (c_int32, [ctypes.POINTER(EdgeBank), _P, c_
 SIGNATURES['tgmx_edgebank_query'] = (c_int32, [ctypes.POINTER(EdgeBank), _P, c_int32, _P, c_int32, _P, c_int32, _P, c_int64, c_int64, c_int64, _P, c_int32, _P])
 SIGNATURES['tgmx_edgebank_rehash'] = (c_int32, [ctypes.POINTER(EdgeBank), ctypes.POINTER(EdgeBank), _P, _P])
 
+
+class TCoMem(ctypes.Structure):
+    """tgmx_tcomem_t (include/tgm_amd.h)."""
+
+    _fields_ = [
+        ('ring', c_void_p), ('pos', c_void_p), ('len', c_void_p), ('popularity', c_void_p),
+        ('table', c_void_p), ('capacity', c_int64),
+        ('state', c_void_p),
+        ('num_nodes', c_int64), ('k', c_int32), ('reserved_', c_int32),
+        ('co_occurrence_weight', ctypes.c_double),
+        ('status', c_void_p),
+    ]  # fmt: skip
+
+
+SIGNATURES['tgmx_tcomem_state_bytes'] = (c_size_t, [])
+SIGNATURES['tgmx_tcomem_update'] = (c_int32, [ctypes.POINTER(TCoMem), _P, c_int32, _P, c_int32, _P, c_int32, c_int64, _P])
+SIGNATURES['tgmx_tcomem_query'] = (c_int32, [ctypes.POINTER(TCoMem), _P, c_int32, _P, c_int32, _P, c_int32, _P, c_int64, c_int64, c_int64, _P, c_int32, _P])
+SIGNATURES['tgmx_tcomem_rehash'] = (c_int32, [ctypes.POINTER(TCoMem), ctypes.POINTER(TCoMem), _P, _P])
+
 _lib: Optional[ctypes.CDLL] = None
 
 

@@ -1,7 +1,7 @@
 // EdgeBankPredictor (the reference's tgm/nn/modules/edgebank.py), for gfx950: the edge memory as a device hash table, the batch update, the
 // batched queries (flat, and one source against its destination and its negatives) and the rehash into a larger table.
 //
-// Table: open addressing, linear probing, capacity a power of two.  A slot is 16 bytes {uint64 key = src << 32 | dst, int64 ts}, so a probe is
+// Table (pairtable.h): open addressing, linear probing, capacity a power of two.  A slot is 16 bytes {uint64 key = src << 32 | dst, int64 ts}, so a probe is
 // one 16-byte load; the empty key is all ones (ids lie in [0, 2^31), so no pair packs to it).  A key is written once, by a 64-bit
 // compare-and-swap, and never changes or leaves until a rehash: a probe that meets an empty slot has seen every slot the key could be in.
 //
@@ -16,36 +16,21 @@
 // positions may differ with the order in which colliding keys claim).
 //
 // Every probe loop is a for over at most `capacity` probes; one that runs out sets kOverflow in the status word and gives up.
-#include "common.h"
+#include "pairtable.h"
 
 namespace tgmx {
 
-constexpr unsigned long long kEbEmpty = ~0ull;
 constexpr int kEbBadId = 1, kEbOverflow = 2;  // status bits
 constexpr int kEbBlockMax = 1024;             // events the one-workgroup update takes
-constexpr int kEbThreads = 256;
 
-struct EbSlot {
-  unsigned long long key;
-  long long ts;
-};
 struct alignas(16) EbState {  // tgmx_edgebank_state_bytes()
   long long end;              // window_end
   long long size_i;           // window size, unlimited mode (int64 arithmetic)
   float size_f;               // window size, fixed mode (float32 arithmetic, as the reference's 0-dim tensors)
   int pad_[3];
 };
-static_assert(sizeof(EbState) == 32 && sizeof(EbSlot) == 16, "edgebank layouts");
+static_assert(sizeof(EbState) == 32, "edgebank layouts");
 
-__device__ __forceinline__ unsigned long long eb_hash(unsigned long long x) {  // the splitmix64 finaliser
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-  return x ^ (x >> 31);
-}
-__device__ __forceinline__ long long eb_ld(const void* p, int is64, long long i) {
-  return is64 ? (long long)reinterpret_cast<const int64_t*>(p)[i] : (long long)reinterpret_cast<const int32_t*>(p)[i];
-}
-__device__ __forceinline__ bool eb_id_ok(long long s, long long d) { return s >= 0 && s < (1ll << 31) && d >= 0 && d < (1ll << 31); }
 __device__ __forceinline__ unsigned long long eb_key(long long s, long long d) { return ((unsigned long long)s << 32) | (unsigned long long)d; }
 
 // the insertion test `ts >= window_start`: float32 on both sides in fixed mode (the reference compares a Python int with a 0-dim float32
@@ -56,33 +41,6 @@ __device__ __forceinline__ bool eb_in_window(long long ts, long long end, const 
 // the query's test: the stored int64 against the float32 start taken exactly (Python compares an int with a float exactly; |ts| < 2^53)
 __device__ __forceinline__ bool eb_hit(long long ts, long long end, const EbState& s, int fixed) {
   return !fixed || (double)ts >= (double)((float)end - s.size_f);
-}
-
-// slot of `key`, claimed if absent; -1 when `cap` probes found neither the key nor room
-__device__ __forceinline__ long long eb_claim(EbSlot* __restrict__ table, long long cap, unsigned long long key) {
-  unsigned long long* keys = reinterpret_cast<unsigned long long*>(table);
-  long long i = (long long)(eb_hash(key) & (unsigned long long)(cap - 1));
-  for (long long p = 0; p < cap; ++p) {
-    unsigned long long cur = __hip_atomic_load(&keys[2 * i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (cur == kEbEmpty) cur = atomicCAS(&keys[2 * i], kEbEmpty, key);  // returns what was there: empty (now mine), mine, or another's
-    if (cur == kEbEmpty || cur == key) return i;
-    i = (i + 1) & (cap - 1);
-  }
-  return -1;
-}
-// slot of `key`, or -1 (absent: an empty slot ends the probe)
-__device__ __forceinline__ long long eb_find(const EbSlot* __restrict__ table, long long cap, unsigned long long key, long long* ts_out) {
-  long long i = (long long)(eb_hash(key) & (unsigned long long)(cap - 1));
-  for (long long p = 0; p < cap; ++p) {
-    const ulonglong2 s = reinterpret_cast<const ulonglong2*>(table)[i];  // one 16-byte load
-    if (s.x == key) {
-      *ts_out = (long long)s.y;
-      return i;
-    }
-    if (s.x == kEbEmpty) return -1;
-    i = (i + 1) & (cap - 1);
-  }
-  return -1;
 }
 
 struct EbUpdateArgs {
@@ -116,7 +74,7 @@ __device__ __forceinline__ long long eb_stamp(const EbUpdateArgs& a, unsigned lo
 }
 // phase 3: the stamp is read past the L1 (the atomics ran in L2; a line this CU cached before them would be stale)
 __device__ __forceinline__ void eb_write(const EbUpdateArgs& a, long long slot, long long g, long long t) {
-  if (slot >= 0 && __hip_atomic_load(&a.stamp[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == g) a.table[slot].ts = t;
+  if (slot >= 0 && __hip_atomic_load(&a.stamp[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == g) a.table[slot].val = t;
 }
 
 // n <= kEbBlockMax events, one workgroup, one event per thread
@@ -262,36 +220,12 @@ struct EbRehashArgs {
   unsigned long long* kept;
 };
 
-// keys of the old table are distinct, so each claims an empty slot of the new one and is its only writer
+// fixed mode drops what has left the window (the reference's _clean_up: the insertion test, float32 on both sides)
 __global__ __launch_bounds__(kEbThreads) void eb_rehash_kernel(EbRehashArgs a) {
   const EbState st = *a.state;
-  const long long step = (long long)gridDim.x * blockDim.x;
-  const long long trips = (a.from_cap + step - 1) / step;  // the wave's bound: every lane takes every trip (the ballot below)
-  for (long long r = 0; r < trips; ++r) {
-    const long long i = r * step + (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    bool keep = false;
-    if (i < a.from_cap) {
-      const ulonglong2 s = reinterpret_cast<const ulonglong2*>(a.from)[i];
-      // fixed mode drops what has left the window (the reference's _clean_up: the insertion test, float32 on both sides)
-      if (s.x != kEbEmpty && eb_in_window((long long)s.y, st.end, st, a.fixed)) {
-        const long long slot = eb_claim(a.to, a.to_cap, s.x);
-        if (slot >= 0) {
-          a.to[slot].ts = (long long)s.y;
-          keep = true;
-        } else {
-          atomicOr(a.status, kEbOverflow);
-        }
-      }
-    }
-    const unsigned long long kept = __ballot(keep);
-    if (lane_id() == 0 && kept) atomicAdd(a.kept, (unsigned long long)__popcll(kept));
-  }
+  eb_move_slots(a.from, a.from_cap, a.to, a.to_cap, a.status, kEbOverflow, a.kept, [&](long long ts) { return eb_in_window(ts, st.end, st, a.fixed); });
 }
 
-static unsigned eb_grid(long long items) {
-  const long long blocks = (items + kEbThreads - 1) / kEbThreads;
-  return (unsigned)(blocks < 1 ? 1 : (blocks > 8192 ? 8192 : blocks));
-}
 static bool eb_valid(const tgmx_edgebank_t* eb) {
   return eb && eb->table && eb->stamp && eb->state && eb->status && eb->capacity >= 2 && eb->capacity < (1ll << 40) &&
          (eb->capacity & (eb->capacity - 1)) == 0;

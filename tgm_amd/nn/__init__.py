@@ -6,6 +6,8 @@ from .dygformer import DyGFormer, NeighborCooccurrenceEncoder, TransformerEncode
 from .graphmixer import GraphMixerEncoder
 from .mlp_mixer import FeedForwardNet, MLPMixer
 from .ncn import NCNPredictor
+from .poptrack import PopTrackPredictor
+from .tcomem import tCoMemPredictor
 from .tgat import TGAT, MergeLayer
 from .tgcn import TGCN, GCNConv
 from .tgn import GraphAttentionEmbedding, IdentityMessage, LastAggregator, MeanAggregator, TGNMemory, TGNStep, TransformerConv, sampled_edge_list
@@ -15,6 +17,6 @@ from . import decoder, encoder, modules  # noqa: E402,F401  (the reference's imp
 
 __all__ = [
     'DyGFormer', 'EdgeBankPredictor', 'EncoderModule', 'FeedForwardNet', 'GCNConv', 'GraphAttentionEmbedding', 'GraphMixerEncoder', 'IdentityMessage', 'LastAggregator',
-    'MLPMixer', 'MeanAggregator', 'MergeLayer', 'NCNPredictor', 'NeighborCooccurrenceEncoder', 'RandomProjectionModule', 'TGAT', 'TGCN',
-    'TGNMemory', 'TGNStep', 'TPNet', 'TemporalAttention', 'Time2Vec', 'TransformerConv', 'TransformerEncoder', 'invalidate_parameter_caches', 'sampled_edge_list',
+    'MLPMixer', 'MeanAggregator', 'MergeLayer', 'NCNPredictor', 'NeighborCooccurrenceEncoder', 'PopTrackPredictor', 'RandomProjectionModule', 'TGAT', 'TGCN',
+    'TGNMemory', 'TGNStep', 'TPNet', 'TemporalAttention', 'Time2Vec', 'TransformerConv', 'TransformerEncoder', 'invalidate_parameter_caches', 'sampled_edge_list', 'tCoMemPredictor',
 ]  # fmt: skip
