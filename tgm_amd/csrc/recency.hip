@@ -16,7 +16,7 @@
 //
 // File map (one translation unit: the lookup launches carry pieces of the ring update, so both live here):
 //   UpdateArgs, keys, the single-workgroup sort / placement body (update_block_body)
-//   riders: update_chunk_sort, update_merge_riding, rider_barrier, update_side_work -- the state-independent half of
+//   riders: update_chunk_sort, update_merge_riding, rider_barrier, update_sort_lds, update_side_work -- the state-independent half of
 //     the ring update as workgroup-sized pieces that ride inside the lookup launches; which piece rides
 //     which launch is one table: the comment above SideStage, plan_riders on the host
 //   lookup pieces (fetch_seed ... lookup_seed) and the kernels built from them: recency_lookup_kernel (one hop),
@@ -379,12 +379,23 @@ __device__ __forceinline__ T ld_agent(const T* p) {
   return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// what the placement needs of sorted positions tid * E .. tid * E + E - 1, held in registers by a caller that sorted in LDS
+// (update_sort_lds): entry index, node (-1 invalid), absolute write_pos, record
+template <int E>
+struct SortedFeed {
+  int pay[E], node[E], w[E];
+  Rec rec[E];
+};
+
 // DEFER: decide everything, write nothing to the rings -- winner[p] = the ring row position p finally owns (-1 none),
 // target[p] = the write_pos increment position p commits (0 none); `ring_update_commit_kernel` applies them.
 // COH: the presorted arrays were written by OTHER workgroups of this launch (riders): read them device-coherently
-template <int E, int MAXM, bool PRESORTED, bool DEFER, bool COH = false>
+// REGS: the presorted values come from `feed` instead of the scratch, and the scratch arrays the commit reads (sorted_j,
+// sorted_node, sorted_rec) are written here, beside winner and target
+template <int E, int MAXM, bool PRESORTED, bool DEFER, bool COH = false, bool REGS = false>
 __device__ __forceinline__ void update_block_body(const UpdateArgs& a, PlaceLds<MAXM>& L, SortLds<PRESORTED ? 1 : MAXM>& S,
-                                                  int part = 0, int parts = 1) {
+                                                  int part = 0, int parts = 1, const SortedFeed<E>* feed = nullptr) {
+  static_assert(!REGS || (PRESORTED && DEFER && !COH), "a register feed is a presorted, deferring placement of one workgroup");
   constexpr int H = 2 * MAXM;
   constexpr int HBITS = MAXM == 512 ? 10 : (MAXM == 1024 ? 11 : (MAXM == 2048 ? 12 : 13));
   static_assert((1 << HBITS) == H, "hash size");
@@ -416,7 +427,11 @@ __device__ __forceinline__ void update_block_body(const UpdateArgs& a, PlaceLds<
       pay[r] = p;
       node[r] = -1;
       w[r] = 0;
-      if (p < m) {
+      if constexpr (REGS) {
+        pay[r] = feed->pay[r];
+        node[r] = feed->node[r];
+        w[r] = feed->w[r];
+      } else if (p < m) {
         pay[r] = COH ? ld_agent(&a.sorted_j[p]) : a.sorted_j[p];
         node[r] = COH ? ld_agent(&a.sorted_node[p]) : a.sorted_node[p];
         w[r] = COH ? ld_agent(&a.target[p]) : a.target[p];
@@ -548,10 +563,14 @@ __device__ __forceinline__ void update_block_body(const UpdateArgs& a, PlaceLds<
         if constexpr (DEFER) {
           // the commit kernel reads sorted_rec[p] itself; a deferred commit also publishes the record for the next launch's lookups
           if (a.drec) {
-            const long long* src = reinterpret_cast<const long long*>(&a.sorted_rec[p]);
-            long long* dst = reinterpret_cast<long long*>(&a.drec[tgt[r]]);
-            dst[0] = COH ? ld_agent(&src[0]) : src[0];
-            dst[1] = COH ? ld_agent(&src[1]) : src[1];
+            if constexpr (REGS) {
+              a.drec[tgt[r]] = feed->rec[r];
+            } else {
+              const long long* src = reinterpret_cast<const long long*>(&a.sorted_rec[p]);
+              long long* dst = reinterpret_cast<long long*>(&a.drec[tgt[r]]);
+              dst[0] = COH ? ld_agent(&src[0]) : src[0];
+              dst[1] = COH ? ld_agent(&src[1]) : src[1];
+            }
             a.dslot[tgt[r]] = (int32_t)a.dstamp;
           }
         } else if constexpr (PRESORTED) {
@@ -581,6 +600,11 @@ __device__ __forceinline__ void update_block_body(const UpdateArgs& a, PlaceLds<
     a.winner[p] = win;
     if constexpr (DEFER) a.target[p] = kept;
     if constexpr (!PRESORTED) a.sorted_j[p] = pay[r];
+    if constexpr (REGS) {
+      a.sorted_j[p] = pay[r];
+      a.sorted_node[p] = node[r];
+      a.sorted_rec[p] = feed->rec[r];
+    }
   }
 }
 
@@ -726,8 +750,8 @@ struct SampleLds {
 };
 
 // NE entries per thread (entry `tid` of chunks c0 .. c0 + NE - 1), each searched in up to NC chunks; NE * NC
-// searches advance together.  <1, 16>: one workgroup per chunk, any m <= 4096.  <4, 4>: ONE workgroup merges a whole
-// batch of m <= 1024 entries (and goes on to place it, see below).
+// searches advance together.  <1, 16>: one workgroup per chunk, any m <= 4096; <1, NCH>: the riders that go on to place a
+// batch of NCH chunks.  (A batch of m <= 512 entries in one workgroup does not come here: update_sort_lds.)
 template <int NE, int NC, bool COH = false>  // COH: the placement follows in ANOTHER workgroup of this launch
 __device__ __forceinline__ void update_merge_riding(const UpdateArgs& a, int c0, SampleLds& W) {
   const int m = (int)a.m;
@@ -856,7 +880,9 @@ __device__ __forceinline__ void update_merge_riding(const UpdateArgs& a, int c0,
 //   kSideMerge           workgroup c ranks chunk c's entries among all chunks (the sorts ran in the previous launch)
 //   kSideSortMerge       both, with the riders' barrier between them (they are the launch's first <= 16 workgroups: resident together)
 //   kSidePlaceOnly       ONE workgroup decides the placement of a batch the previous launch's riders sorted and merged
-//   kSideAll             ONE workgroup does all of it: chunk sorts one after the other, merge, placement decisions
+//   kSideAll             ONE workgroup does all of it in one pass through LDS (update_sort_lds): the batch is read once, sorted and
+//                        rank-merged in LDS, and the placement decisions are fed from registers; global memory sees the entries'
+//                        loads, one round for their nodes' write_pos, and the final stores
 //   kSideSortMergePlace  kSideSortMerge, then the last rider out decides the placement
 //   kSideMergePlace      kSideMerge, then the last rider out decides the placement: the update's chain is spread over BOTH lookup
 //                        launches and the launch boundary is the barrier
@@ -940,6 +966,161 @@ __device__ __forceinline__ void commit_block(const UpdateArgs& c, unsigned cb) {
   if (p < c.m) commit_position(c, p);
 }
 
+// ---- kSideAll: a whole batch of m <= 512 entries in ONE workgroup, sorted without a global round trip ------------------------
+// The lookups around a rider keep the memory pipeline full, so every DEPENDENT global read costs it microseconds, and as the
+// fused launch's one rider it ends with the last lookup.  Here the batch is read once (src / dst / ts of two entries per thread,
+// then write_pos / the pending header of their nodes while the sort runs), and everything up to the placement's final stores
+// stays in registers and LDS: the two 256-entry chunk sorts, a rank merge of the two sorted halves by binary search in LDS, and
+// the hand-over of every sorted position's entry to the thread that places it.  The buffers are dead before the placement's
+// hash tables are initialised (RiderLds is a union).
+constexpr int kAllMaxM = 512;
+struct AllLds {
+  union {
+    struct {  // the chunk-sorted halves for the rank merge; the head is the sort network's exchange buffer before that
+      long long key[kAllMaxM];
+      int pay[kAllMaxM];
+    } srt;
+    struct {  // by entry index: what the batch's entries read; j: entry index by sorted position
+      long long ts[kAllMaxM];
+      int node[kAllMaxM], nbr[kAllMaxM], w[kAllMaxM], j[kAllMaxM];
+    } ent;
+  };
+  long long red[kChunk / kWave], red2[kChunk / kWave];
+};
+
+template <int E>
+__device__ __forceinline__ void update_sort_lds(const UpdateArgs& a, AllLds& W, SortedFeed<E>& f) {
+  constexpr int NQ = kAllMaxM / kChunk;
+  static_assert(NQ == 2, "the rank merge below is between two sorted halves");
+  static_assert(E * kChunk >= kAllMaxM, "every sorted position has a thread");
+  const int m = (int)a.m;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int chunks = (m + kChunk - 1) / kChunk;
+
+  // the batch, once: entries tid and 256 + tid, then the state of their nodes (in flight while the sort runs)
+  int node[NQ], nbr[NQ], w[NQ];
+  long long t[NQ], i[NQ];
+  bool act[NQ], valid[NQ];
+  long long mx = -0x7fffffffffffffffLL, mn = 0x7fffffffffffffffLL;
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) {
+    const int j = q * kChunk + tid;
+    act[q] = j < m;
+    node[q] = nbr[q] = -1;
+    t[q] = i[q] = 0;
+    if (act[q]) {
+      update_entry(a, j, node[q], nbr[q], t[q], i[q]);
+      mx = t[q] > mx ? t[q] : mx;
+      mn = t[q] < mn ? t[q] : mn;
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) {
+    valid[q] = act[q] && node[q] >= 0 && node[q] < a.N && nbr[q] >= 0 && nbr[q] < a.N;
+    if (act[q] && !valid[q]) atomicOr(a.status, TGMX_ST_EDGE_RANGE);
+    // write_pos only moves after the lookups -- or, with a deferred commit in this launch, as its header says
+    w[q] = valid[q] ? logical_wp(a.write_pos, a.phdr, a.pstamp, node[q]) : 0;
+  }
+  for (int off = 32; off > 0; off >>= 1) {
+    const long long o = __shfl_xor(mx, off), o2 = __shfl_xor(mn, off);
+    mx = o > mx ? o : mx;
+    mn = o2 < mn ? o2 : mn;
+  }
+  if (lane == 0) {
+    W.red[wave] = mx;
+    W.red2[wave] = mn;
+  }
+  __syncthreads();
+  mx = W.red[0];
+  mn = W.red2[0];
+  for (int wv = 1; wv < kChunk / kWave; ++wv) {
+    mx = W.red[wv] > mx ? W.red[wv] : mx;
+    mn = W.red2[wv] < mn ? W.red2[wv] : mn;
+  }
+  const long long span = mx + 1;
+  const bool packed = can_pack(a.key_wrap32, mn, mx);
+
+  // the two chunk sorts (update_chunk_sort's keys and tie order); padding sorts to each chunk's end
+  long long key[NQ];
+  int pay[NQ];
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) {
+    const int j = q * kChunk + tid;
+    key[q] = 0x7fffffffffffffffLL;
+    pay[q] = j;
+    if (act[q]) {
+      key[q] = update_key(node[q], t[q], span, a.key_wrap32);
+      if (packed) key[q] = packed_key(key[q], j);
+    }
+    if (q < chunks) {
+      if (packed) bitonic_sort_one<true>(key[q], pay[q], W.srt.key, W.srt.pay, tid, kChunk);
+      else bitonic_sort_one<false>(key[q], pay[q], W.srt.key, W.srt.pay, tid, kChunk);
+    }
+  }
+  // sorted position of the pair this thread holds of chunk q: its place in the chunk + the pairs of the other chunk before it
+  // (pairs are unique, so the ranks are a permutation)
+  int rank[NQ];
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) rank[q] = tid;
+  if (chunks > 1) {
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+      W.srt.key[q * kChunk + tid] = key[q];
+      W.srt.pay[q * kChunk + tid] = pay[q];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+      const long long* ok = W.srt.key + (1 - q) * kChunk;
+      const int* op = W.srt.pay + (1 - q) * kChunk;
+      int lo = 0, hi = kChunk;
+#pragma unroll 1
+      for (int step = 0; step < 9; ++step) {  // 2^9 > kChunk
+        if (lo < hi) {
+          const int mid = (lo + hi) >> 1;
+          if (pair_after(key[q], pay[q], ok[mid], op[mid])) lo = mid + 1;
+          else hi = mid;
+        }
+      }
+      rank[q] += lo;
+    }
+  }
+  __syncthreads();  // W.srt is dead, W.ent takes its place
+
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) {
+    const int j = q * kChunk + tid;
+    if (act[q]) {
+      W.ent.ts[j] = t[q];
+      W.ent.node[j] = valid[q] ? node[q] : -1;
+      W.ent.nbr[j] = nbr[q];
+      W.ent.w[j] = w[q];  // the ABSOLUTE write_pos (the placement takes it modulo B; a deferred commit's header needs all of it)
+      W.ent.j[rank[q]] = pay[q];  // (position tid of a chunk is real exactly when entry tid of that chunk is)
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int r = 0; r < E; ++r) {
+    const int p = tid * E + r;
+    f.pay[r] = p;
+    f.node[r] = -1;
+    f.w[r] = 0;
+    f.rec[r].nbr = -1;
+    f.rec[r].eid = -1;
+    f.rec[r].ts = 0;
+    if (p < m) {
+      const int j = W.ent.j[p];
+      f.pay[r] = j;
+      f.node[r] = W.ent.node[j];
+      f.w[r] = W.ent.w[j];
+      f.rec[r].nbr = W.ent.nbr[j];
+      f.rec[r].eid = a.eid0 >= 0 ? (int)(a.eid0 + (j >= a.n ? j - a.n : j)) : -1;
+      f.rec[r].ts = W.ent.ts[j];
+    }
+  }
+  __syncthreads();  // W.ent is dead: the placement's tables take its place
+}
+
 // PCAP: capacity of the riding placement (entries); 0 = this launch's riders only sort / merge.  The union is static LDS of EVERY
 // workgroup of the launch, rider or not: 24.9 KB at 1024 entries caps a lookup launch at 6 workgroups per CU, 12.6 KB at 512
 // (the single-rank wiki batch: m = 400) at 12, 6.2 KB without the placement tables at 25.
@@ -947,8 +1128,10 @@ template <int PCAP>
 union RiderLds {
   ChunkSortLds sort;
   SampleLds smp;
+  AllLds all;
   PlaceLds<PCAP> place;
 };
+static_assert(sizeof(RiderLds<512>) == sizeof(PlaceLds<512>), "the one-pass rider's LDS fits under the placement tables");
 template <>
 union RiderLds<0> {
   ChunkSortLds sort;
@@ -1000,18 +1183,14 @@ __device__ __forceinline__ void update_side_work(const UpdateArgs& u, int stage,
       rider_last_out_places<NCH>(u, W.place);
       return;
     }
-    if (stage == kSideAll) {
-      const int chunks = (int)((u.m + kChunk - 1) / kChunk);
-#pragma unroll 1
-      for (int c = 0; c < NCH; ++c) {
-        if (c < chunks) update_chunk_sort(u, c, W.sort);
-        __syncthreads();  // W.sort is reused; the chunk-sorted pairs written above are read below by other threads
-      }
-      update_merge_riding<NCH, NCH>(u, 0, W.smp);
-      __syncthreads();  // the sorted arrays written above are read below by other threads of this workgroup
-    }
-    // kSideAll, kSidePlaceOnly (the previous launch's riders merged already)
     SortLds<1> none;
+    if (stage == kSideAll) {  // (plan_riders: m <= 512 = kAllMaxM)
+      SortedFeed<NCH> feed;
+      update_sort_lds<NCH>(u, W.all, feed);
+      update_block_body<NCH, PCAP, true, true, false, true>(u, W.place, none, 0, 1, &feed);
+      return;
+    }
+    // kSidePlaceOnly (the previous launch's riders merged already)
     update_block_body<NCH, PCAP, true, true>(u, W.place, none);
   }
 }
