@@ -1287,6 +1287,51 @@ int tgmx_tcomem_query(const tgmx_tcomem_t* tc, const void* src, int32_t src_is64
 /* Moves the pair counts of `from` into `to` (a new, empty table of at least twice the capacity).  *kept (device) = pairs moved. */
 int tgmx_tcomem_rehash(const tgmx_tcomem_t* from, const tgmx_tcomem_t* to, int64_t* kept, tgmx_stream_t stream);
 
+/* ---- CTAN (the reference's tgm/nn/encoder/ctan.py): memory update, wide-head attention, the encoder's inference forward ---- */
+
+/* CTANMemory.update_state (ctan.py:128-147) with LastAggregator: over the positions p in [0, 2B) of cat[src, pos_dst] (time t[p mod B]),
+ * a node's memory row becomes row p* of cat[src_emb, pos_dst_emb], p* = the LOWEST p among the node's positions with the largest
+ * float32(t) (the reference's argmax over float scores), and its last_update the exact int64 maximum of its times -- plain overwrites, no
+ * maximum against the old state.  src_emb has rows_src >= B rows, [*, M]; row p >= rows_src is pos_dst_emb's row p - rows_src (the caller
+ * checks that the two hold 2B rows).  ids int64 where the *_is64 flag is set, else int32.  scratch_key [num_nodes] 8-byte words, all
+ * ZERO, and scratch_tmax [num_nodes] int64, all INT64_MIN, on entry; both are left so (the caller keeps them between calls).  Two
+ * launches, integer atomic maxima only: the same bits on every run.  An id outside [0, num_nodes) is skipped and sets bit 1 of *status. */
+int tgmx_ctan_memory_update(const void* src, int32_t src_is64, const void* dst, int32_t dst_is64, const int64_t* t, int64_t B,
+                            const float* src_emb, const float* dst_emb, int64_t rows_src, int32_t M, int64_t num_nodes, float* memory,
+                            int64_t* last_update, void* scratch_key, int64_t* scratch_tmax, int32_t* status, tgmx_stream_t stream);
+
+/* The attention of TransformerConv(heads = 1, root_weight = False) (third-party definition, PyG 2.6.1) with AntiSymmetricConv's update as
+ * its epilogue.  Arguments as tgmx_tconv_attend's with H = 1; `order` must hold every segment in ascending edge id (tgmx_segment_sort),
+ * src[e] in [0, U).  With phi_i = sum_j softmax_j(q_i.(k_j + e_ij) scale) (v_j + e_ij), 0 for a target without incoming edges:
+ *   mode 0: h4 += phi;   mode 1: x <- x + epsilon tanh(h4 + phi);   mode 2: out = tanh(x + epsilon tanh(h4 + phi)),
+ * every one of the U rows included.  C <= 256: one wave covers a row (a lane owns ceil(C / 64) consecutive columns), edges in blocks of
+ * four requested ahead, long segments over four waves merged in wave order -- deterministic.  Wider: tgmx_tconv_attend's walk, then
+ * the epilogue as a launch of its own. */
+int tgmx_ctan_attend(const float* q, const float* k, const float* v, const float* eproj, const int64_t* order, const int64_t* src,
+                     const int64_t* seg_lo, const int64_t* seg_hi, int64_t U, int32_t C, float scale, float* h4, float* x, float* out,
+                     float epsilon, int32_t mode, tgmx_stream_t stream);
+
+/* CTAN.forward (ctan.py:53-79; AntiSymmetricConv and TransformerConv from their PyG 2.6.1 definitions) as ONE call, inference only:
+ *   x = node_x W_x^T + b_x;  once: edge_attr[e] = [msg[e] | cos(rel_e tw + tb)], rel_e = (float(|last_update[src[e]] - t[e]|) - mean_delta_t)
+ *   / std_delta_t in float32, eproj = edge_attr W_edge^T, the edges grouped by tgt (tgmx_segment_sort);  num_iters times: qkvs = x W4^T + b4
+ *   (W4 = [W_query, W_key, W_value, A], A = W - W^T - gamma I; b4 = [b_query, b_key, b_value, bias]: one batched GEMM), then
+ *   tgmx_ctan_attend in mode 1 (mode 2 on the last iteration, into out).
+ * Every buffer is the caller's.  src / tgt out of [0, U) are clamped and raise TGMX_ST_EDGE_RANGE in *status. */
+typedef struct tgmx_ctan_fwd {
+  const float* node_x; int64_t U; int32_t in_ch, M;    /* [U, in_ch], in_ch = M + node_dim */
+  const int64_t* last_update;                          /* [U] */
+  const int64_t* src; const int64_t* tgt; const int64_t* t; const float* msg; int64_t E; int32_t D, T;
+  const float* tw; const float* tb;                    /* [T], [T] */
+  const float* W_x; const float* b_x;                  /* [M, in_ch], [M] */
+  const float* W4; const float* b4; const float* W_edge; /* [4, M, M], [4, M], [M, D + T] */
+  int32_t num_iters; float epsilon, mean_delta_t, std_delta_t;
+  float* edge_attr; float* eproj; float* x; float* qkvs; /* [E, D + T], [E, M], [U, M], [4, U, M] */
+  int64_t* src_ok; int64_t* order; int64_t* seg_lo; int64_t* seg_hi; /* [E], [E], [U], [U] */
+  void* sort_ws; size_t sort_ws_bytes; int32_t* status;
+  float* out;                                          /* [U, M] */
+} tgmx_ctan_fwd_t;
+int tgmx_ctan_forward(const tgmx_ctan_fwd_t* args, tgmx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

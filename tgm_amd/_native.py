@@ -521,6 +521,26 @@ SIGNATURES['tgmx_tcomem_update'] = (c_int32, [ctypes.POINTER(TCoMem), _P, c_int3
 SIGNATURES['tgmx_tcomem_query'] = (c_int32, [ctypes.POINTER(TCoMem), _P, c_int32, _P, c_int32, _P, c_int32, _P, c_int64, c_int64, c_int64, _P, c_int32, _P])
 SIGNATURES['tgmx_tcomem_rehash'] = (c_int32, [ctypes.POINTER(TCoMem), ctypes.POINTER(TCoMem), _P, _P])
 
+
+class CtanFwd(ctypes.Structure):
+    """tgmx_ctan_fwd_t (include/tgm_amd.h)."""
+
+    _fields_ = [
+        ('node_x', c_void_p), ('U', c_int64), ('in_ch', c_int32), ('M', c_int32), ('last_update', c_void_p),
+        ('src', c_void_p), ('tgt', c_void_p), ('t', c_void_p), ('msg', c_void_p), ('E', c_int64), ('D', c_int32), ('T', c_int32),
+        ('tw', c_void_p), ('tb', c_void_p), ('W_x', c_void_p), ('b_x', c_void_p), ('W4', c_void_p), ('b4', c_void_p), ('W_edge', c_void_p),
+        ('num_iters', c_int32), ('epsilon', ctypes.c_float), ('mean_delta_t', ctypes.c_float), ('std_delta_t', ctypes.c_float),
+        ('edge_attr', c_void_p), ('eproj', c_void_p), ('x', c_void_p), ('qkvs', c_void_p),
+        ('src_ok', c_void_p), ('order', c_void_p), ('seg_lo', c_void_p), ('seg_hi', c_void_p),
+        ('sort_ws', c_void_p), ('sort_ws_bytes', c_size_t), ('status', c_void_p),
+        ('out', c_void_p),
+    ]  # fmt: skip
+
+
+SIGNATURES['tgmx_ctan_memory_update'] = (c_int32, [_P, c_int32, _P, c_int32, _P, c_int64, _P, _P, c_int64, c_int32, c_int64, _P, _P, _P, _P, _P, _P])
+SIGNATURES['tgmx_ctan_attend'] = (c_int32, [_P, _P, _P, _P, _P, _P, _P, _P, c_int64, c_int32, ctypes.c_float, _P, _P, _P, ctypes.c_float, c_int32, _P])
+SIGNATURES['tgmx_ctan_forward'] = (c_int32, [ctypes.POINTER(CtanFwd), _P])
+
 _lib: Optional[ctypes.CDLL] = None
 
 

@@ -41,6 +41,7 @@ extern "C" size_t tgmx_abi_sizeof(int32_t which) {
     case 19: return sizeof(tgmx_ncn_fwd_t);
     case 20: return sizeof(tgmx_edgebank_t);
     case 21: return sizeof(tgmx_tcomem_t);
+    case 22: return sizeof(tgmx_ctan_fwd_t);
     default: return 0;
   }
 }

@@ -1,6 +1,7 @@
 from ._paramver import invalidate_parameter_caches
 from .attention import TemporalAttention
 from .base import EncoderModule
+from .ctan import CTAN, CTANMemory
 from .edgebank import EdgeBankPredictor
 from .dygformer import DyGFormer, NeighborCooccurrenceEncoder, TransformerEncoder
 from .graphmixer import GraphMixerEncoder
@@ -16,7 +17,7 @@ from .tpnet import RandomProjectionModule, TPNet
 from . import decoder, encoder, modules  # noqa: E402,F401  (the reference's import paths: tgm.nn.encoder.tgn, tgm.nn.modules.attention, ...)
 
 __all__ = [
-    'DyGFormer', 'EdgeBankPredictor', 'EncoderModule', 'FeedForwardNet', 'GCNConv', 'GraphAttentionEmbedding', 'GraphMixerEncoder', 'IdentityMessage', 'LastAggregator',
+    'CTAN', 'CTANMemory', 'DyGFormer', 'EdgeBankPredictor', 'EncoderModule', 'FeedForwardNet', 'GCNConv', 'GraphAttentionEmbedding', 'GraphMixerEncoder', 'IdentityMessage', 'LastAggregator',
     'MLPMixer', 'MeanAggregator', 'MergeLayer', 'NCNPredictor', 'NeighborCooccurrenceEncoder', 'PopTrackPredictor', 'RandomProjectionModule', 'TGAT', 'TGCN',
     'TGNMemory', 'TGNStep', 'TPNet', 'TemporalAttention', 'Time2Vec', 'TransformerConv', 'TransformerEncoder', 'invalidate_parameter_caches', 'sampled_edge_list', 'tCoMemPredictor',
 ]  # fmt: skip
