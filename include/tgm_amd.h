@@ -510,7 +510,8 @@ int tgmx_tgat_attn_reduce(const float* qf, const float* nbrf, int32_t d, const f
                           const float* tw, const float* tb, const float* nbr_time_feat,
                           const uint8_t* mask, int32_t T, int32_t H, int32_t k, int64_t R,
                           float scale, int32_t head_stride /* floats between heads in qf / zbar rows, 0 = C */,
-                          float* zbar, float* attn_probs /* optional [R,H,k]: softmax weights BEFORE dropout, for backward */,
+                          float* zbar, float* attn_probs /* optional [R,H,k]: softmax weights BEFORE dropout, for backward;
+                                                             a row WITHOUT a valid slot stores its uniform weights negated (-1/k) */,
                           const tgmx_dropout_t* drop /* NULL = off; element (r, h, s) of [R, H, k], attention.py:119 */,
                           tgmx_stream_t stream);
 
@@ -676,7 +677,11 @@ int tgmx_ln_backward(const float* dout, int64_t ldd, const float* y, int64_t ldy
 
 /* Backward of tgmx_tgat_attn_reduce (needs the saved attention weights): given dzbar [R,H,Cs] ->
  * dqf [R,H,Cs], dnbr [R,k,d] (accumulated, may be NULL) and per-row partials dtime_rows [R, 2T] of the
- * Time2Vec weight | bias gradients (column-sum them).  k * H <= 64. */
+ * Time2Vec weight | bias gradients (column-sum them).  k * H <= 64.
+ * probs [R,H,k] as tgmx_tgat_attn_reduce saved them: weights >= 0, a masked slot exactly 0.  A row whose weights are NEGATIVE
+ * (the forward writes -1/k) had no valid slot: every score was masked_fill'ed (attention.py:117), so nothing flows back through
+ * the scores -- ds = 0, dqf = 0 -- and only the value path remains: dz[s] = sum_h |probs[h,s]| * mask[h,s] * dzbar[h].
+ * Columns [C, head_stride) of dqf are unspecified. */
 int tgmx_tgat_attn_backward(const float* qf, const float* probs, const float* dzbar, const float* nbrf,
                             int32_t d, const float* ex, int32_t D, const int64_t* seed_t,
                             const int64_t* nbr_t, const float* tw, const float* tb, int32_t T, int32_t H,

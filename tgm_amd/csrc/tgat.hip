@@ -1720,8 +1720,13 @@ __global__ __launch_bounds__(256) void tgat_attn_reduce_kernel(const AttnArgs a)
   }
   __builtin_amdgcn_wave_barrier();
 
-  if (a.probs)
-    for (int e = lane; e < H * k; e += kWave) a.probs[r * (long long)H * k + e] = s_A[e];
+  if (a.probs) {
+    // a row without a valid slot saves its (uniform) weights NEGATED: the backward's marker that nothing flows through the scores
+    // (masked_fill on every slot, attention.py:117; include/tgm_amd.h: tgmx_tgat_attn_backward)
+    bool none = true;
+    for (int s = 0; s < k; ++s) none = none && s_valid[s] == 0.f;
+    for (int e = lane; e < H * k; e += kWave) a.probs[r * (long long)H * k + e] = none ? -s_A[e] : s_A[e];
+  }
   if (a.drop.thresh) {
     for (int e = lane; e < H * k; e += kWave) s_A[e] *= dropout_scale(a.drop, (unsigned long long)(a.drop_row0 + r) * (H * k) + e);
     __builtin_amdgcn_wave_barrier();
@@ -1835,14 +1840,32 @@ __global__ __launch_bounds__(256) void tgat_attn_reduce_reg_kernel(const AttnArg
   // time delta.  The uniform average of k identical vectors is that vector: no scores, no softmax, ONE slot read instead
   // of k.  (Differs from summing k products by (1/k) in the last bit or two: ~1e-7 relative.)  Applies to id-masked
   // rows only; an explicit mask tensor takes the general path.
+  // With dropout on, the k slots of such a row of a layer ABOVE the leaves are k different rows of the layer below, each with its own
+  // dropout masks: equal inputs, different values.  The slots are then compared first (k loads in flight together, still no score and
+  // no softmax) and a row whose slots differ takes the general path.  Without dropout equal inputs give equal rows: no comparison.
   const bool e_on = lane < D4;
   {
     const unsigned kmask = k >= 32 ? 0xffffffffu : ((1u << k) - 1u);
     const bool none = ((unsigned)__ballot(my_ok) & kmask) == 0 && !a.mask;
     const float dt0 = lane_bcast(my_dt, 0);
-    if (none && __all(lane >= k || my_dt == dt0)) {
+    bool one_entry = none && __all(lane >= k || my_dt == dt0);
+    if (one_entry && a.drop.thresh) {
+      bool same = true;
+      for (int s2 = 1; s2 < k; ++s2) {
+        if (NBV) {
+          if (lane < d4) {
+            const float4 u = reinterpret_cast<const float4*>(nrow(0))[lane], v = reinterpret_cast<const float4*>(nrow(s2))[lane];
+            same = same && u.x == v.x && u.y == v.y && u.z == v.z && u.w == v.w;
+          }
+        } else if (lane < d) {
+          same = same && nrow(0)[lane] == nrow(s2)[lane];
+        }
+      }
+      one_entry = __all(same);
+    }
+    if (one_entry) {
       const float A = 1.0f / (float)k;  // softmax of k equal scores
-      if (a.probs && lane < H * k) a.probs[r * (long long)H * k + lane] = A;
+      if (a.probs && lane < H * k) a.probs[r * (long long)H * k + lane] = -A;  // negated: the backward's marker of a row without a valid slot
       float wh[H];
 #pragma unroll
       for (int h = 0; h < H; ++h) {
@@ -2029,7 +2052,7 @@ __global__ __launch_bounds__(256) void tgat_attn_reduce_reg_kernel(const AttnArg
     float ev = live ? expf(sc - mx) : 0.f;
     const float sum = butterfly_sum<H>(ev);
     float A = ev / sum;
-    if (a.probs && live) a.probs[r * (long long)H * k + (lane - js * H) * k + js] = A;
+    if (a.probs && live) a.probs[r * (long long)H * k + (lane - js * H) * k + js] = okm ? A : -A;  // (no valid slot: saved negated, the backward's marker)
     if (a.drop.thresh && live) A *= dropout_scale(a.drop, (unsigned long long)(a.drop_row0 + r) * (H * k) + (lane - js * H) * k + js);
 
     // ---- zbar[h] = sum_s A[h][s] z[s], from registers ----

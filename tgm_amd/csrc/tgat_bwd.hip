@@ -368,12 +368,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void t
     if (lv_eid) s_eid[s] = lv_eid[r * k + s];
   }
   int span;
+  bool no_valid;  // the forward's marker: the weights of a row without a valid slot are saved NEGATED (uniform, -1/k)
   {
     const int js0 = lane / H, jh0 = lane - js0 * H;
     const float A0 = js0 < k ? a.probs[r * (long long)H * k + jh0 * k + js0] : 0.f;
     const unsigned long long amask = __ballot(A0 != 0.f);
     const int first = amask ? (__ffsll((long long)amask) - 1) / H : 0;
     span = k - first;
+    no_valid = __any(A0 < 0.f);
   }
   __builtin_amdgcn_wave_barrier();
   // feature c of slot sl: a strided block of the row's own slots, or (edge features by id) row eid[sl] of the resident store --
@@ -482,11 +484,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void t
     // zbar used A' = A * mk (dropout on the softmax output, attention.py:119): dA = dA' * mk, and the slot gradients below take A'
     const float mk = live ? dropout_scale(a.drop, (unsigned long long)(a.drop_row0 + r) * (H * k) + jh * k + js) : 0.f;
     const float dA = ((NV2 > 0 && lane >= 32) ? Q[0] : P[0]) * mk;
-    const float A = live ? a.probs[r * (long long)H * k + jh * k + js] : 0.f;
+    const float A = live ? fabsf(a.probs[r * (long long)H * k + jh * k + js]) : 0.f;
     float dot = A * dA;
 #pragma unroll
     for (int o = H; o < 64; o <<= 1) dot += __shfl_xor(dot, o);
-    const float ds = A * (dA - dot);  // softmax backward; masked slots have A == 0
+    // softmax backward; masked slots have A == 0.  A row without a valid slot: every score was masked_fill'ed (attention.py:117),
+    // nothing flows back through them -- ds = 0, only the value path A' dzbar remains
+    const float ds = no_valid ? 0.f : A * (dA - dot);
     if (live) {
       s_A[jh * k + js] = A * mk;
       s_ds[jh * k + js] = ds;
@@ -648,7 +652,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NBV ? 1 : 2,
   }
   const int js = lane / H, jh = lane - js * H;  // lane j = slot * H + head
   const bool live = js < k;
-  const float A = live ? a.probs[r * (long long)H * k + jh * k + js] : 0.f;
+  const float A_saved = live ? a.probs[r * (long long)H * k + jh * k + js] : 0.f;
+  const float A = fabsf(A_saved);  // (saved negated for a row without a valid slot: the forward's marker, see no_valid below)
 #pragma unroll
   for (int h = 0; h < H; ++h) {
     const float* qh = q + h * Cs;
@@ -676,6 +681,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NBV ? 1 : 2,
   // the slots that carry gradient: from the first one with A != 0 in some head to the end (see the kernel above)
   const unsigned long long amask = __ballot(A != 0.f);
   const int span = amask ? k - (__ffsll((long long)amask) - 1) / H : k;
+  const bool no_valid = __any(A_saved < 0.f);  // every score was masked_fill'ed (attention.py:117): nothing flows back through them
   // the cosine's reduction path, once per row: a sufficient test first, the exact one only if it fails (tgat.hip: row_args_small)
   bool row_small;
   {
@@ -752,7 +758,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NBV ? 1 : 2,
     // ---- softmax backward in the lanes (slot, head); zbar used A' = A * mk (dropout on the softmax output, attention.py:119) ----
     const float dA = (live && js >= s0) ? sc * mk : 0.f;
     const float dot = lanes::butterfly_sum<H>(A * dA);
-    const float ds = A * (dA - dot);  // a masked slot has A == 0
+    const float ds = no_valid ? 0.f : A * (dA - dot);  // a masked slot has A == 0; a row without a valid slot keeps the value path only
     const float Ap = A * mk;
 
     // ---- pass 2, from registers: dqf[h] = scale * sum_s ds[h][s] z[s];  dz[s] = sum_h A' dzbar[h] + scale * ds * qf[h] ----
