@@ -56,7 +56,7 @@ int tgmx_version(void);
 /* sizeof of the argument structs as this library was compiled (a binding checks its own mirror against it):
  * 0 tgmx_adj_t, 1 tgmx_recency_step_t, 2 tgmx_tgat_layer_t, 3 tgmx_tgat_model_t, 4 tgmx_tgat_hop_t, 5 tgmx_tgat_layout_t,
  * 6 tgmx_pipeline_t, 7 tgmx_pipeline_out_t, 8 tgmx_dropout_t, 9 tgmx_tgn_memory_fwd_t, 10 tgmx_tconv_fwd_t, 11 tgmx_pipeline_post_t,
- * 12 tgmx_tgn_step_t */
+ * 12 tgmx_tgn_step_t, ..., 22 tgmx_ctan_fwd_t, 24 tgmx_gclstm_fwd_t (23 is reserved and answers 0: tests/test_ctan_cpu.py pins it) */
 size_t tgmx_abi_sizeof(int32_t which);
 const char* tgmx_last_error(void);
 
@@ -1336,6 +1336,59 @@ typedef struct tgmx_ctan_fwd {
   float* out;                                          /* [U, M] */
 } tgmx_ctan_fwd_t;
 int tgmx_ctan_forward(const tgmx_ctan_fwd_t* args, tgmx_stream_t stream);
+
+/* ---- ChebConv / GCLSTM (the reference's tgm/nn/encoder/gclstm.py; ChebConv from its published PyG definition): the scaled Laplacian of a
+ * snapshot as a CSR by destination, a gather SpMM over it, and the cell's inference forward as one call ---- */
+
+#define TGMX_CHEB_NORM_NONE 0
+#define TGMX_CHEB_NORM_SYM 1
+#define TGMX_CHEB_NORM_RW 2
+
+/* Bytes of workspace tgmx_cheb_laplacian needs for E edges over N nodes (0: sizes out of range). */
+size_t tgmx_cheb_workspace_bytes(int64_t E, int64_t N);
+
+/* L_hat = 2 L / lambda_max - I of the graph (src[e] -> dst[e], weight w[e] or 1) as rows BY DESTINATION: indptr [N + 1], cols [E] (the
+ * sources, ascending within a row, duplicates kept in edge order), vals [E], and the diagonal diag [N].  Self loops are dropped; the degree
+ * is taken over the SOURCE index; normalization NONE: m_e = -w, d_i = deg_i;  SYM: m_e = -deg[src]^-1/2 w deg[dst]^-1/2, d_i = 1;
+ * RW: m_e = -w / deg[src], d_i = 1 (an infinite factor counts as 0);  vals = 2 m_e / lambda_max (infinite -> 0), diag = 2 d_i / lambda_max - 1.
+ * lambda_max is read from lambda_ptr (device, one float) when that is non-NULL.  ids int64 where idx64 is set, else int32.
+ * One stable radix sort by (dst, src) carrying the edge position, row pointers by binary search; weighted degrees are summed in a fixed
+ * order over a second stable sort by source (integer counts without weights): no float atomics, the same bits on every run.
+ * An edge with an endpoint outside [0, N) is skipped and counted in *skipped (device, accumulating; may be NULL); E = 0 is valid. */
+int tgmx_cheb_laplacian(const void* src, const void* dst, int32_t idx64, const float* w, int64_t E, int64_t N, int32_t normalization,
+                        float lambda_max, const float* lambda_ptr, int32_t* indptr, int32_t* cols, float* vals, float* diag,
+                        void* workspace, size_t workspace_bytes, int32_t* skipped, tgmx_stream_t stream);
+
+/* out[i, :C] = alpha (sum_{j in row i} vals[j] t[cols[j], :C] + diag[i] t[i, :C]) + beta prev[i, :C] over row-major float32 operands with
+ * leading dimensions ldt / ldp / ldo (column slices of a wider operand are fine; out must not overlap t).  prev is not read when beta = 0.
+ * The steps of the Chebyshev recurrence are (alpha, beta) = (1, 0) and (2, -1).  Gather form: a wave per destination row, four source
+ * rows requested ahead, float4 lanes when C % 4 = 0 and every pointer / leading dimension is 16-byte aligned; a row of more than 64
+ * entries is split over the four waves of its workgroup and the partial sums are added in wave order.  nnz: an upper bound on the entries
+ * (the E the Laplacian was built from).  With scratch (tgmx_cheb_propagate_scratch_floats(nnz, C) floats, 16-byte aligned; 0 floats: not
+ * needed) a row of more than 2048 entries leaves that launch: a second one sums it chunk by chunk of 1024 entries, a workgroup per chunk,
+ * and a third adds the chunk sums in ascending order; without scratch such a row stays with its one workgroup (same values up to the order
+ * of the sum, slower).  No atomics: reproducible bit for bit. */
+size_t tgmx_cheb_propagate_scratch_floats(int64_t nnz, int32_t C);
+int tgmx_cheb_propagate(const int32_t* indptr, const int32_t* cols, const float* vals, const float* diag, int64_t N, int32_t C,
+                        const float* t, int64_t ldt, const float* prev, int64_t ldp, float alpha, float beta, float* out, int64_t ldo,
+                        int64_t nnz, float* scratch, size_t scratch_floats, tgmx_stream_t stream);
+
+/* GCLSTM.forward (gclstm.py:97-107, 165-227) as ONE call, inference only: the Laplacian once (not at all for K = 1, where the cell does
+ * not read the graph), op = [x | Tx_0 | ... | Tx_{K-1}] with Tx_0 = H by K - 1 propagations, pre = op W^T + b with the four gates'
+ * weights stacked (rows of gate g in i, f, c, o order: [W_g^T | lins_g,0 | ... | lins_g,K-1], b = b_g + conv_g.bias), then
+ * I, F, O = sigmoid, T = tanh, C_out = F C + I T, H_out = O tanh(C_out).  Every buffer is the caller's. */
+typedef struct tgmx_gclstm_fwd {
+  const float* x; int64_t N; int32_t in_ch, C, K, normalization;  /* [N, in_ch] */
+  const void* src; const void* dst; const float* edge_w; int64_t E; int32_t idx64; float lambda_max; const float* lambda_ptr;
+  const float* W; const float* b; int64_t ldw;         /* [4C, ldw >= in_ch + K C], [4C] */
+  const float* H; const float* Cprev;                  /* [N, C] each */
+  int32_t* indptr; int32_t* cols; float* vals; float* diag; /* [N + 1], [E], [E], [N] */
+  void* lap_ws; size_t lap_ws_bytes; int32_t* skipped;
+  float* prop_ws; size_t prop_ws_floats;               /* tgmx_cheb_propagate_scratch_floats(E, C) floats, or NULL */
+  float* op; int64_t ldop; float* pre;                 /* [N, ldop >= in_ch + K C], [N, 4C] */
+  float* H_out; float* C_out;                          /* [N, C] each */
+} tgmx_gclstm_fwd_t;
+int tgmx_gclstm_forward(const tgmx_gclstm_fwd_t* args, tgmx_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -541,6 +541,31 @@ SIGNATURES['tgmx_ctan_memory_update'] = (c_int32, [_P, c_int32, _P, c_int32, _P,
 SIGNATURES['tgmx_ctan_attend'] = (c_int32, [_P, _P, _P, _P, _P, _P, _P, _P, c_int64, c_int32, ctypes.c_float, _P, _P, _P, ctypes.c_float, c_int32, _P])
 SIGNATURES['tgmx_ctan_forward'] = (c_int32, [ctypes.POINTER(CtanFwd), _P])
 
+CHEB_NORM = {None: 0, 'sym': 1, 'rw': 2}  # TGMX_CHEB_NORM_*
+
+
+class GclstmFwd(ctypes.Structure):
+    """tgmx_gclstm_fwd_t (include/tgm_amd.h)."""
+
+    _fields_ = [
+        ('x', c_void_p), ('N', c_int64), ('in_ch', c_int32), ('C', c_int32), ('K', c_int32), ('normalization', c_int32),
+        ('src', c_void_p), ('dst', c_void_p), ('edge_w', c_void_p), ('E', c_int64), ('idx64', c_int32), ('lambda_max', ctypes.c_float),
+        ('lambda_ptr', c_void_p),
+        ('W', c_void_p), ('b', c_void_p), ('ldw', c_int64),
+        ('H', c_void_p), ('Cprev', c_void_p),
+        ('indptr', c_void_p), ('cols', c_void_p), ('vals', c_void_p), ('diag', c_void_p),
+        ('lap_ws', c_void_p), ('lap_ws_bytes', c_size_t), ('skipped', c_void_p), ('prop_ws', c_void_p), ('prop_ws_floats', c_size_t),
+        ('op', c_void_p), ('ldop', c_int64), ('pre', c_void_p),
+        ('H_out', c_void_p), ('C_out', c_void_p),
+    ]  # fmt: skip
+
+
+SIGNATURES['tgmx_cheb_workspace_bytes'] = (c_size_t, [c_int64, c_int64])
+SIGNATURES['tgmx_cheb_laplacian'] = (c_int32, [_P, _P, c_int32, _P, c_int64, c_int64, c_int32, ctypes.c_float, _P, _P, _P, _P, _P, _P, c_size_t, _P, _P])
+SIGNATURES['tgmx_cheb_propagate_scratch_floats'] = (c_size_t, [c_int64, c_int32])
+SIGNATURES['tgmx_cheb_propagate'] = (c_int32, [_P, _P, _P, _P, c_int64, c_int32, _P, c_int64, _P, c_int64, ctypes.c_float, ctypes.c_float, _P, c_int64, c_int64, _P, c_size_t, _P])
+SIGNATURES['tgmx_gclstm_forward'] = (c_int32, [ctypes.POINTER(GclstmFwd), _P])
+
 _lib: Optional[ctypes.CDLL] = None
 
 

@@ -42,6 +42,7 @@ extern "C" size_t tgmx_abi_sizeof(int32_t which) {
     case 20: return sizeof(tgmx_edgebank_t);
     case 21: return sizeof(tgmx_tcomem_t);
     case 22: return sizeof(tgmx_ctan_fwd_t);
+    case 24: return sizeof(tgmx_gclstm_fwd_t);  // (23 stays 0: an existing test pins it as the first unused index)
     default: return 0;
   }
 }

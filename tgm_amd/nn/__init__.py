@@ -3,6 +3,7 @@ from .attention import TemporalAttention
 from .base import EncoderModule
 from .ctan import CTAN, CTANMemory
 from .edgebank import EdgeBankPredictor
+from .gclstm import GCLSTM, ChebConv
 from .dygformer import DyGFormer, NeighborCooccurrenceEncoder, TransformerEncoder
 from .graphmixer import GraphMixerEncoder
 from .mlp_mixer import FeedForwardNet, MLPMixer
@@ -17,7 +18,7 @@ from .tpnet import RandomProjectionModule, TPNet
 from . import decoder, encoder, modules  # noqa: E402,F401  (the reference's import paths: tgm.nn.encoder.tgn, tgm.nn.modules.attention, ...)
 
 __all__ = [
-    'CTAN', 'CTANMemory', 'DyGFormer', 'EdgeBankPredictor', 'EncoderModule', 'FeedForwardNet', 'GCNConv', 'GraphAttentionEmbedding', 'GraphMixerEncoder', 'IdentityMessage', 'LastAggregator',
+    'CTAN', 'CTANMemory', 'ChebConv', 'DyGFormer', 'EdgeBankPredictor', 'EncoderModule', 'FeedForwardNet', 'GCLSTM', 'GCNConv', 'GraphAttentionEmbedding', 'GraphMixerEncoder', 'IdentityMessage', 'LastAggregator',
     'MLPMixer', 'MeanAggregator', 'MergeLayer', 'NCNPredictor', 'NeighborCooccurrenceEncoder', 'PopTrackPredictor', 'RandomProjectionModule', 'TGAT', 'TGCN',
     'TGNMemory', 'TGNStep', 'TPNet', 'TemporalAttention', 'Time2Vec', 'TransformerConv', 'TransformerEncoder', 'invalidate_parameter_caches', 'sampled_edge_list', 'tCoMemPredictor',
 ]  # fmt: skip
