@@ -56,7 +56,8 @@ int tgmx_version(void);
 /* sizeof of the argument structs as this library was compiled (a binding checks its own mirror against it):
  * 0 tgmx_adj_t, 1 tgmx_recency_step_t, 2 tgmx_tgat_layer_t, 3 tgmx_tgat_model_t, 4 tgmx_tgat_hop_t, 5 tgmx_tgat_layout_t,
  * 6 tgmx_pipeline_t, 7 tgmx_pipeline_out_t, 8 tgmx_dropout_t, 9 tgmx_tgn_memory_fwd_t, 10 tgmx_tconv_fwd_t, 11 tgmx_pipeline_post_t,
- * 12 tgmx_tgn_step_t, ..., 22 tgmx_ctan_fwd_t, 24 tgmx_gclstm_fwd_t (23 is reserved and answers 0: tests/test_ctan_cpu.py pins it) */
+ * 12 tgmx_tgn_step_t, ..., 22 tgmx_ctan_fwd_t, 24 tgmx_gclstm_fwd_t, 26 tgmx_roland_fwd_t (23 and 25 are reserved and answer 0: tests/test_ctan_cpu.py and
+ * tests/test_gclstm_cpu.py pin them) */
 size_t tgmx_abi_sizeof(int32_t which);
 const char* tgmx_last_error(void);
 
@@ -1389,6 +1390,69 @@ typedef struct tgmx_gclstm_fwd {
   float* H_out; float* C_out;                          /* [N, C] each */
 } tgmx_gclstm_fwd_t;
 int tgmx_gclstm_forward(const tgmx_gclstm_fwd_t* args, tgmx_stream_t stream);
+
+/* ---- GCNConv above the dense cap / ROLAND (the reference's tgm/nn/encoder/roland.py; GCNConv from its published PyG definition): GCN's
+ * normalised adjacency as a CSR by destination, the gather SpMM over it with a fused epilogue, and ROLAND's forward as one call ---- */
+
+/* Bytes of workspace tgmx_gcn_norm_csr needs for E edges over N nodes (0: sizes out of range). */
+size_t tgmx_gcn_workspace_bytes(int64_t E, int64_t N);
+
+/* The sparse twin of tgmx_gcn_norm_dense: D^-1/2 (A + I) D^-1/2 of the graph (src[e] -> dst[e], weight w[e] or 1) as rows BY DESTINATION:
+ * indptr [N + 1], cols [E] (the sources, ascending within a row, duplicates kept in edge order), vals [E], and the diagonal diag [N].
+ * gcn_norm with add_remaining_self_loops: the degree is taken over the DESTINATION index and includes the loop weight; a node's loop
+ * weight is `fill` unless it has an explicit self loop, then that loop's weight (of several, the one at the highest edge position);
+ * explicit loops are folded into diag; repeated edges each count; deg = 0 gives the factor 0.  add_self_loops = 0: loops are ordinary
+ * entries and diag is 0.  ids int64 where idx64 is set, else int32, read as they are.
+ * One stable radix sort by (dst, src) carrying the edge position, row pointers by binary search; unweighted degrees are the rows' lengths,
+ * weighted ones are summed per row in CSR order by one wave: no float atomics, the same bits on every run.
+ * An edge with an endpoint outside [0, N) is skipped and counted in *skipped (device, accumulating; may be NULL); E = 0 issues no sort. */
+int tgmx_gcn_norm_csr(const void* src, const void* dst, int32_t idx64, const float* w, int64_t E, int64_t N, float fill,
+                      int32_t add_self_loops, int32_t* indptr, int32_t* cols, float* vals, float* diag, void* workspace,
+                      size_t workspace_bytes, int32_t* skipped, tgmx_stream_t stream);
+
+#define TGMX_GCN_EPI_NONE 0  /* out = s,  s = diag[i] t[i] + sum_j vals[j] t[cols[j]] + bias */
+#define TGMX_GCN_EPI_RELU 1  /* out = relu(s) */
+#define TGMX_GCN_EPI_TAU 2   /* out = tau prev[i] + (1 - tau) relu(s) */
+
+/* out[i, :C] = epi(diag[i] t[i, :C] + sum_{j in row i} vals[j] t[cols[j], :C] + bias[:C]) over row-major float32 operands with leading
+ * dimensions (column slices of a wider operand are fine; out must not overlap t).  bias may be NULL.  TGMX_GCN_EPI_TAU reads prev
+ * [N, ldp] and tau: from tau_ptr (device, one float: a learnable tau is never read back) when that is non-NULL, else the argument; with
+ * prev_copy [N, ldc] non-NULL it also stores prev[i, :C] there (the caller's state copied on the way).  The gather, the scratch and the
+ * launches are those of tgmx_cheb_propagate (scratch: tgmx_cheb_propagate_scratch_floats(nnz, C) floats); the epilogue runs wherever a
+ * row finishes.  No atomics: reproducible bit for bit. */
+int tgmx_gcn_propagate(const int32_t* indptr, const int32_t* cols, const float* vals, const float* diag, int64_t N, int32_t C,
+                       const float* t, int64_t ldt, const float* bias, int32_t epilogue, const float* prev, int64_t ldp, float tau,
+                       const float* tau_ptr, float* prev_copy, int64_t ldc, float* out, int64_t ldo, int64_t nnz, float* scratch,
+                       size_t scratch_floats, tgmx_stream_t stream);
+
+#define TGMX_ROLAND_TAU 0  /* 'moving', 'learnable', None: H_l = tau prev_l + (1 - tau) relu(conv_l(.)) */
+#define TGMX_ROLAND_MLP 1  /* H_l = mlp_l([relu(conv_l(.)) | prev_l]) */
+#define TGMX_ROLAND_GRU 2  /* H_l = GRUCell_l(relu(conv_l(.)), prev_l) */
+
+/* ROLAND.forward (roland.py:86-151) as ONE call (its outputs are detached in the reference, so this is the whole model whenever dropout
+ * is inactive): the normalisation once, then per layer l = 0, 1 the GEMM xw = h_in W_l^T (h_in = x, then out[0]) and a propagation with
+ * conv_l.bias and the update as its epilogue.  TAU: the propagation writes out[l] (prev[l] [N, ldp]; prev_copy[l] [N, C] or NULL).
+ * MLP / GRU: it writes relu(.) into the left column slice of op[l] [N, 2C], whose right slice the caller has filled with prev_l;
+ * MLP: out[l] = op[l] mlp_w[l]^T + mlp_b[l];  GRU: gi = op[l][:, :C] w_ih[l]^T + b_ih[l], gh = op[l][:, C:] w_hh[l]^T + b_hh[l] (two plain
+ * GEMMs), then r = sigmoid(gi_r + gh_r), z = sigmoid(gi_z + gh_z), n = tanh(gi_n + r gh_n), out[l] = (1 - z) n + z prev_l.
+ * Every buffer is the caller's; nothing is read back. */
+typedef struct tgmx_roland_fwd {
+  const float* x; int64_t N; int32_t in_ch, C, update, add_self_loops;  /* [N, in_ch] */
+  const void* src; const void* dst; int64_t E; int32_t idx64; float fill;
+  const float* conv_w[2]; int64_t ldw[2]; const float* conv_b[2];      /* [C, ldw[0] >= in_ch], [C, ldw[1] >= C]; [C] */
+  float tau; const float* tau_ptr;                                     /* TAU */
+  const float* prev[2]; int64_t ldp; float* prev_copy[2];              /* TAU */
+  const float* mlp_w[2]; const float* mlp_b[2];                        /* MLP: [C, 2C], [C] */
+  const float* w_ih[2]; const float* w_hh[2]; const float* b_ih[2]; const float* b_hh[2]; /* GRU: [3C, C], [3C] */
+  int32_t* indptr; int32_t* cols; float* vals; float* diag;            /* [N + 1], [E], [E], [N] */
+  void* norm_ws; size_t norm_ws_bytes; int32_t* skipped;
+  float* prop_ws; size_t prop_ws_floats;                               /* tgmx_cheb_propagate_scratch_floats(E, C) floats, or NULL */
+  float* xw;                                                           /* [N, C] */
+  float* op[2];                                                        /* MLP, GRU: [N, 2C] */
+  float* gi; float* gh;                                                /* GRU: [N, 3C] each */
+  float* out[2];                                                       /* [N, C] each */
+} tgmx_roland_fwd_t;
+int tgmx_roland_forward(const tgmx_roland_fwd_t* args, tgmx_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -566,6 +566,33 @@ SIGNATURES['tgmx_cheb_propagate_scratch_floats'] = (c_size_t, [c_int64, c_int32]
 SIGNATURES['tgmx_cheb_propagate'] = (c_int32, [_P, _P, _P, _P, c_int64, c_int32, _P, c_int64, _P, c_int64, ctypes.c_float, ctypes.c_float, _P, c_int64, c_int64, _P, c_size_t, _P])
 SIGNATURES['tgmx_gclstm_forward'] = (c_int32, [ctypes.POINTER(GclstmFwd), _P])
 
+GCN_EPI = {'none': 0, 'relu': 1, 'tau': 2}  # TGMX_GCN_EPI_*
+ROLAND_UPDATE = {'moving': 0, 'learnable': 0, None: 0, 'mlp': 1, 'gru': 2}  # TGMX_ROLAND_*
+
+
+class RolandFwd(ctypes.Structure):
+    """tgmx_roland_fwd_t (include/tgm_amd.h)."""
+
+    _fields_ = [
+        ('x', c_void_p), ('N', c_int64), ('in_ch', c_int32), ('C', c_int32), ('update', c_int32), ('add_self_loops', c_int32),
+        ('src', c_void_p), ('dst', c_void_p), ('E', c_int64), ('idx64', c_int32), ('fill', ctypes.c_float),
+        ('conv_w', c_void_p * 2), ('ldw', c_int64 * 2), ('conv_b', c_void_p * 2),
+        ('tau', ctypes.c_float), ('tau_ptr', c_void_p),
+        ('prev', c_void_p * 2), ('ldp', c_int64), ('prev_copy', c_void_p * 2),
+        ('mlp_w', c_void_p * 2), ('mlp_b', c_void_p * 2),
+        ('w_ih', c_void_p * 2), ('w_hh', c_void_p * 2), ('b_ih', c_void_p * 2), ('b_hh', c_void_p * 2),
+        ('indptr', c_void_p), ('cols', c_void_p), ('vals', c_void_p), ('diag', c_void_p),
+        ('norm_ws', c_void_p), ('norm_ws_bytes', c_size_t), ('skipped', c_void_p), ('prop_ws', c_void_p), ('prop_ws_floats', c_size_t),
+        ('xw', c_void_p), ('op', c_void_p * 2), ('gi', c_void_p), ('gh', c_void_p),
+        ('out', c_void_p * 2),
+    ]  # fmt: skip
+
+
+SIGNATURES['tgmx_gcn_workspace_bytes'] = (c_size_t, [c_int64, c_int64])
+SIGNATURES['tgmx_gcn_norm_csr'] = (c_int32, [_P, _P, c_int32, _P, c_int64, c_int64, ctypes.c_float, c_int32, _P, _P, _P, _P, _P, c_size_t, _P, _P])
+SIGNATURES['tgmx_gcn_propagate'] = (c_int32, [_P, _P, _P, _P, c_int64, c_int32, _P, c_int64, _P, c_int32, _P, c_int64, ctypes.c_float, _P, _P, c_int64, _P, c_int64, c_int64, _P, c_size_t, _P])
+SIGNATURES['tgmx_roland_forward'] = (c_int32, [ctypes.POINTER(RolandFwd), _P])
+
 _lib: Optional[ctypes.CDLL] = None
 
 

@@ -9,40 +9,22 @@
 // on the order of arrival); with weights a second stable sort by source groups the positions and one wave per node sums its group in a
 // fixed order.  Nothing here adds floats with atomics: two runs give the same bits.
 //
-// Propagate: out = alpha (L_hat t) + beta prev, gather form.  A workgroup of four waves owns four destination rows; a wave walks its row's
+// Propagate: out = alpha (L_hat t) + beta prev, gather form (the kernels live in spmm.h, shared with gcn.hip).  A workgroup of four waves owns four destination rows; a wave walks its row's
 // entries four at a time (four source rows requested before the first is used), the lanes spread over the channels.  A row of more than
-// kChebLongRow entries is cut into four contiguous pieces, one per wave, and the partial sums meet in LDS in wave order.  A row of more than
-// kChebVeryLong entries (a hub: the most popular page of a wiki-shaped day has 21 000) would still keep one workgroup busy long after the
-// others have left, so the caller's scratch takes it out of that launch: a second launch cuts the ENTRY array into chunks of kChebChunk, a
+// kSpmmLongRow entries is cut into four contiguous pieces, one per wave, and the partial sums meet in LDS in wave order.  A row of more than
+// kSpmmVeryLong entries (a hub: the most popular page of a wiki-shaped day has 21 000) would still keep one workgroup busy long after the
+// others have left, so the caller's scratch takes it out of that launch: a second launch cuts the ENTRY array into chunks of kSpmmChunk, a
 // workgroup per chunk sums the part of the (at most two) very long rows its chunk holds, and a third adds a row's chunk sums in ascending
 // chunk order.  Every order is fixed by the CSR alone.
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include "common.h"
+#include "spmm.h"
 
 namespace tgmx {
 
-constexpr int kChebThreads = 256;
-constexpr int kChebWaves = kChebThreads / kWave;
-constexpr int kChebLongRow = 64;   // entries; longer rows are split over the workgroup's waves
-constexpr int kChebChPerLane = 4;  // channels a lane covers per pass: 256 channels a pass
-constexpr int kChebChunk = 1024;   // entries of the CSR one workgroup of the chunk launch covers
-constexpr int kChebVeryLong = 2 * kChebChunk;  // rows longer than this go through the chunk launch: a chunk then meets at most two of them
-
-__device__ __forceinline__ long long cheb_idx(const void* p, int is64, long long i) {
-  return is64 ? (long long)reinterpret_cast<const int64_t*>(p)[i] : (long long)reinterpret_cast<const int32_t*>(p)[i];
-}
-
-static int cheb_col_bits(long long N) {
-  int cb = 1;
-  while ((1ll << cb) < N) ++cb;
-  return cb;
-}
-
-static unsigned cheb_grid(long long items, int per_block, long long cap) {
-  long long blocks = (items + per_block - 1) / per_block;
-  return (unsigned)(blocks < 1 ? 1 : (blocks > cap ? cap : blocks));
-}
+constexpr int kChebThreads = kSpmmThreads;
+constexpr int kChebWaves = kSpmmWaves;
 
 // ---- Laplacian --------------------------------------------------------------------------------------------------------------------------
 // keys by destination (and by source when the degrees are weighted); cnt: the unweighted degree as an integer count
@@ -51,7 +33,7 @@ __global__ __launch_bounds__(256) void cheb_keys_kernel(const void* __restrict__
                                                         unsigned* __restrict__ ks, int* __restrict__ cnt, int* __restrict__ skipped) {
   const long long step = (long long)gridDim.x * blockDim.x;
   for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < E; e += step) {
-    const long long s = cheb_idx(src, is64, e), d = cheb_idx(dst, is64, e);
+    const long long s = spmm_idx(src, is64, e), d = spmm_idx(dst, is64, e);
     const bool in = s >= 0 && s < N && d >= 0 && d < N;
     const bool ok = in && s != d;
     if (!in && skipped) atomicAdd(skipped, 1);
@@ -182,211 +164,23 @@ static int cheb_layout(long long E, long long N, ChebLayout& w) {
 }
 
 // ---- propagate ----------------------------------------------------------------------------------------------------------------------------
-// a lane's channels of one pass: VEC: the float4 at c0 + 4 lane;  else c0 + lane + 64 q, q < 4
-template <bool VEC>
-__device__ __forceinline__ void cheb_load(const float* __restrict__ row, int c0, int C, int lane, float x[kChebChPerLane]) {
-  if (VEC) {
-    const int c = c0 + lane * 4;
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (c < C) v = *reinterpret_cast<const float4*>(row + c);
-    x[0] = v.x; x[1] = v.y; x[2] = v.z; x[3] = v.w;
-  } else {
-#pragma unroll
-    for (int q = 0; q < kChebChPerLane; ++q) {
-      const int c = c0 + lane + q * kWave;
-      x[q] = c < C ? row[c] : 0.f;
-    }
-  }
-}
-template <bool VEC>
-__device__ __forceinline__ void cheb_store(float* __restrict__ row, int c0, int C, int lane, const float x[kChebChPerLane]) {
-  if (VEC) {
-    const int c = c0 + lane * 4;
-    if (c < C) *reinterpret_cast<float4*>(row + c) = make_float4(x[0], x[1], x[2], x[3]);
-  } else {
-#pragma unroll
-    for (int q = 0; q < kChebChPerLane; ++q) {
-      const int c = c0 + lane + q * kWave;
-      if (c < C) row[c] = x[q];
-    }
-  }
-}
-
-// acc += sum over the entries [lo, hi) in ascending order, four source rows requested ahead
-template <bool VEC>
-__device__ __forceinline__ void cheb_accumulate(const int32_t* __restrict__ cols, const float* __restrict__ vals, int lo, int hi,
-                                                const float* __restrict__ t, long long ldt, int c0, int C, int lane, float acc[kChebChPerLane]) {
-  int j = lo;
-  for (; j + 4 <= hi; j += 4) {
-    float x[4][kChebChPerLane], v[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      v[u] = vals[j + u];
-      cheb_load<VEC>(t + (long long)cols[j + u] * ldt, c0, C, lane, x[u]);
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u)
-#pragma unroll
-      for (int q = 0; q < kChebChPerLane; ++q) acc[q] = __fmaf_rn(v[u], x[u][q], acc[q]);
-  }
-  for (; j < hi; ++j) {
-    float x[kChebChPerLane];
-    const float v = vals[j];
-    cheb_load<VEC>(t + (long long)cols[j] * ldt, c0, C, lane, x);
-#pragma unroll
-    for (int q = 0; q < kChebChPerLane; ++q) acc[q] = __fmaf_rn(v, x[q], acc[q]);
-  }
-}
-
-struct ChebProp {
-  const int32_t* indptr;
-  const int32_t* cols;
-  const float* vals;
-  const float* diag;
-  long long N;
-  int C;
-  const float* t;
-  long long ldt;
+// the epilogue of the Chebyshev recurrence over the shared gather SpMM (spmm.h): out = alpha (L_hat t) + beta prev
+struct ChebEpi {
   const float* prev;
   long long ldp;
   float alpha, beta;
-  float* out;
-  long long ldo;
-  int very_long;   // rows longer than this are left to the chunk launches
-  float* scratch;  // [chunks, 2, C]: the chunk launches' partial sums
+  template <bool VEC>
+  __device__ __forceinline__ void apply(long long i, int c0, int C, int lane, float o[kSpmmChPerLane]) const {
+#pragma unroll
+    for (int q = 0; q < kSpmmChPerLane; ++q) o[q] = alpha * o[q];
+    if (beta != 0.f) {
+      float p[kSpmmChPerLane];
+      spmm_load<VEC>(prev + i * ldp, c0, C, lane, p);
+#pragma unroll
+      for (int q = 0; q < kSpmmChPerLane; ++q) o[q] = __fmaf_rn(beta, p[q], o[q]);
+    }
+  }
 };
-
-// out row i of one channel pass from the gathered sum acc
-template <bool VEC>
-__device__ __forceinline__ void cheb_finish(const ChebProp& a, long long i, int c0, int lane, float acc[kChebChPerLane]) {
-  float self[kChebChPerLane], o[kChebChPerLane];
-  cheb_load<VEC>(a.t + i * a.ldt, c0, a.C, lane, self);
-  const float d = a.diag[i];
-#pragma unroll
-  for (int q = 0; q < kChebChPerLane; ++q) o[q] = a.alpha * __fmaf_rn(d, self[q], acc[q]);
-  if (a.beta != 0.f) {
-    float p[kChebChPerLane];
-    cheb_load<VEC>(a.prev + i * a.ldp, c0, a.C, lane, p);
-#pragma unroll
-    for (int q = 0; q < kChebChPerLane; ++q) o[q] = __fmaf_rn(a.beta, p[q], o[q]);
-  }
-  cheb_store<VEC>(a.out + i * a.ldo, c0, a.C, lane, o);
-}
-
-// the sum over the entries [lo, hi) by the four waves of a workgroup, a contiguous quarter each, the partial sums added in wave order: the
-// total in wave 0's acc.  Called by every thread of the workgroup with the same bounds (two barriers).
-template <bool VEC>
-__device__ __forceinline__ void cheb_block_sum(const ChebProp& a, int lo, int hi, int c0, int lane, int wave,
-                                               float (*part)[kChebChPerLane][kWave], float acc[kChebChPerLane]) {
-  const int piece = (hi - lo + kChebWaves - 1) / kChebWaves;
-  const int mylo = min(lo + wave * piece, hi), myhi = min(mylo + piece, hi);
-#pragma unroll
-  for (int q = 0; q < kChebChPerLane; ++q) acc[q] = 0.f;
-  cheb_accumulate<VEC>(a.cols, a.vals, mylo, myhi, a.t, a.ldt, c0, a.C, lane, acc);
-#pragma unroll
-  for (int q = 0; q < kChebChPerLane; ++q) part[wave][q][lane] = acc[q];
-  __syncthreads();
-  if (wave == 0) {
-#pragma unroll
-    for (int q = 0; q < kChebChPerLane; ++q) {
-      float s = part[0][q][lane];
-#pragma unroll
-      for (int w = 1; w < kChebWaves; ++w) s += part[w][q][lane];
-      acc[q] = s;
-    }
-  }
-  __syncthreads();
-}
-
-template <bool VEC>
-__global__ __launch_bounds__(kChebThreads) void cheb_propagate_kernel(ChebProp a) {
-  __shared__ float part[kChebWaves][kChebChPerLane][kWave];
-  const int lane = lane_id(), wave = threadIdx.x / kWave;
-  const long long row0 = (long long)blockIdx.x * kChebWaves;
-  // short rows: one wave each
-  {
-    const long long i = row0 + wave;
-    if (i < a.N) {
-      const int lo = a.indptr[i], hi = a.indptr[i + 1];
-      if (hi - lo <= kChebLongRow) {
-        for (int c0 = 0; c0 < a.C; c0 += kWave * kChebChPerLane) {
-          float acc[kChebChPerLane] = {0.f, 0.f, 0.f, 0.f};
-          cheb_accumulate<VEC>(a.cols, a.vals, lo, hi, a.t, a.ldt, c0, a.C, lane, acc);
-          cheb_finish<VEC>(a, i, c0, lane, acc);
-        }
-      }
-    }
-  }
-  // long rows: the four waves take a contiguous quarter each (every thread of the workgroup sees the same lengths: the barriers are uniform)
-  for (int r = 0; r < kChebWaves; ++r) {
-    const long long i = row0 + r;
-    if (i >= a.N) break;
-    const int lo = a.indptr[i], hi = a.indptr[i + 1];
-    if (hi - lo <= kChebLongRow || hi - lo > a.very_long) continue;
-    for (int c0 = 0; c0 < a.C; c0 += kWave * kChebChPerLane) {
-      float acc[kChebChPerLane];
-      cheb_block_sum<VEC>(a, lo, hi, c0, lane, wave, part, acc);
-      if (wave == 0) cheb_finish<VEC>(a, i, c0, lane, acc);
-    }
-  }
-}
-
-// the row that holds entry e < indptr[N]
-__device__ __forceinline__ int cheb_row_of(const int32_t* __restrict__ indptr, int N, int e) {
-  int lo = 0, hi = N;
-  while (lo < hi) {
-    const int mid = (int)(((long long)lo + hi) >> 1);
-    if (indptr[mid + 1] <= e) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
-}
-
-// chunk b of the entry array: the partial sums of the very long rows that hold its first entry (slot 0) and its last entry (slot 1)
-template <bool VEC>
-__global__ __launch_bounds__(kChebThreads) void cheb_chunk_kernel(ChebProp a) {
-  __shared__ float part[kChebWaves][kChebChPerLane][kWave];
-  const int lane = lane_id(), wave = threadIdx.x / kWave;
-  const int N = (int)a.N, nnz = a.indptr[N];
-  const long long e0l = (long long)blockIdx.x * kChebChunk;
-  if (e0l >= nnz) return;
-  const int e0 = (int)e0l, e1 = (int)(e0l + kChebChunk < nnz ? e0l + kChebChunk : nnz);
-  const int rA = cheb_row_of(a.indptr, N, e0), rB = cheb_row_of(a.indptr, N, e1 - 1);
-  for (int slot = 0; slot < 2; ++slot) {
-    const int r = slot ? rB : rA;
-    if (slot && rB == rA) break;
-    const int lo = a.indptr[r], hi = a.indptr[r + 1];
-    if (hi - lo <= a.very_long) continue;
-    const int slo = lo > e0 ? lo : e0, shi = hi < e1 ? hi : e1;
-    float* __restrict__ dst = a.scratch + ((long long)blockIdx.x * 2 + slot) * a.C;
-    for (int c0 = 0; c0 < a.C; c0 += kWave * kChebChPerLane) {
-      float acc[kChebChPerLane];
-      cheb_block_sum<VEC>(a, slo, shi, c0, lane, wave, part, acc);
-      if (wave == 0) cheb_store<VEC>(dst, c0, a.C, lane, acc);
-    }
-  }
-}
-
-// a very long row: its chunks' partial sums in ascending chunk order, then the row's epilogue; one wave per row
-template <bool VEC>
-__global__ __launch_bounds__(kChebThreads) void cheb_join_kernel(ChebProp a) {
-  const int lane = lane_id();
-  const long long i = (long long)blockIdx.x * kChebWaves + threadIdx.x / kWave;
-  if (i >= a.N) return;
-  const int lo = a.indptr[i], hi = a.indptr[i + 1];
-  if (hi - lo <= a.very_long) return;
-  for (int c0 = 0; c0 < a.C; c0 += kWave * kChebChPerLane) {
-    float acc[kChebChPerLane] = {0.f, 0.f, 0.f, 0.f};
-    for (int b = lo / kChebChunk; b <= (hi - 1) / kChebChunk; ++b) {
-      const int slot = b * kChebChunk >= lo ? 0 : 1;  // the row holds the chunk's first entry, or it starts inside the chunk and holds its last
-      float x[kChebChPerLane];
-      cheb_load<VEC>(a.scratch + ((long long)b * 2 + slot) * a.C, c0, a.C, lane, x);
-#pragma unroll
-      for (int q = 0; q < kChebChPerLane; ++q) acc[q] += x[q];
-    }
-    cheb_finish<VEC>(a, i, c0, lane, acc);
-  }
-}
 
 // ---- the cell -------------------------------------------------------------------------------------------------------------------------------
 // op[i, :in] = x[i], op[i, in : in + C] = H[i] (Tx_0), the padding columns [width, ldop) zero
@@ -455,14 +249,14 @@ extern "C" int tgmx_cheb_laplacian(const void* src, const void* dst, int32_t idx
   auto* ps_out = reinterpret_cast<unsigned*>(base + l.ps_out);
   int* cnt = reinterpret_cast<int*>(base + l.cnt);
   float* dis = reinterpret_cast<float*>(base + l.dis);
-  const int cb = cheb_col_bits(N);
+  const int cb = spmm_col_bits(N);
   const bool weighted = w != nullptr && E > 0;
   if (!weighted && hipMemsetAsync(cnt, 0, (size_t)N * sizeof(int), st) != hipSuccess) {
     set_error("cheb_laplacian: clearing the degree counts failed");
     return TGMX_E_LAUNCH;
   }
   if (E > 0) {  // (a zero-length sort is not issued)
-    hipLaunchKernelGGL(cheb_keys_kernel, dim3(cheb_grid(E, 256, 4096)), dim3(256), 0, st, src, dst, idx64, (long long)E, (long long)N, cb, kd_in,
+    hipLaunchKernelGGL(cheb_keys_kernel, dim3(spmm_grid(E, 256, 4096)), dim3(256), 0, st, src, dst, idx64, (long long)E, (long long)N, cb, kd_in,
                        pos_in, weighted ? ks_in : nullptr, cnt, skipped);
     TGMX_CHECK_LAUNCH("cheb_laplacian(keys)");
     size_t tb = l.temp_bytes;
@@ -482,19 +276,16 @@ extern "C" int tgmx_cheb_laplacian(const void* src, const void* dst, int32_t idx
       return TGMX_E_LAUNCH;
     }
   }
-  hipLaunchKernelGGL(cheb_degree_kernel, dim3(cheb_grid(N, kChebWaves, 4096)), dim3(kChebThreads), 0, st, weighted ? ks_out : nullptr, ps_out, w, cnt,
+  hipLaunchKernelGGL(cheb_degree_kernel, dim3(spmm_grid(N, kChebWaves, 4096)), dim3(kChebThreads), 0, st, weighted ? ks_out : nullptr, ps_out, w, cnt,
                      (long long)E, (long long)N, normalization, lambda_max, lambda_ptr, dis, diag);
   TGMX_CHECK_LAUNCH("cheb_laplacian(degree)");
-  hipLaunchKernelGGL(cheb_rows_kernel, dim3(cheb_grid(E > N + 1 ? E : N + 1, 256, 4096)), dim3(256), 0, st, kd_out, pos_out, w, dis, (long long)E,
+  hipLaunchKernelGGL(cheb_rows_kernel, dim3(spmm_grid(E > N + 1 ? E : N + 1, 256, 4096)), dim3(256), 0, st, kd_out, pos_out, w, dis, (long long)E,
                      (long long)N, cb, normalization, lambda_max, lambda_ptr, indptr, cols, vals);
   TGMX_CHECK_LAUNCH("cheb_laplacian(rows)");
   return TGMX_OK;
 }
 
-extern "C" size_t tgmx_cheb_propagate_scratch_floats(int64_t nnz, int32_t C) {
-  if (nnz <= kChebVeryLong || C <= 0) return 0;  // no row can be very long
-  return (size_t)((nnz + kChebChunk - 1) / kChebChunk) * 2 * (size_t)C;
-}
+extern "C" size_t tgmx_cheb_propagate_scratch_floats(int64_t nnz, int32_t C) { return spmm_scratch_floats(nnz, C); }
 
 extern "C" int tgmx_cheb_propagate(const int32_t* indptr, const int32_t* cols, const float* vals, const float* diag, int64_t N, int32_t C,
                                    const float* t, int64_t ldt, const float* prev, int64_t ldp, float alpha, float beta, float* out, int64_t ldo,
@@ -503,32 +294,10 @@ extern "C" int tgmx_cheb_propagate(const int32_t* indptr, const int32_t* cols, c
                "cheb_propagate: bad sizes N=%lld C=%d nnz=%lld", (long long)N, C, (long long)nnz);
   if (N == 0) return TGMX_OK;
   TGMX_REQUIRE(indptr && diag && t && out && (beta == 0.f || prev), "cheb_propagate: null pointer");
-  // very long rows leave the first launch only when the caller brought the scratch for their chunk sums
-  const size_t need = tgmx_cheb_propagate_scratch_floats(nnz, C);
-  const bool chunks = need > 0 && scratch != nullptr;
-  if (chunks && scratch_floats < need) {
-    set_error("cheb_propagate: scratch too small (%zu floats, %zu needed)", scratch_floats, need);
-    return TGMX_E_INVALID;
-  }
-  ChebProp a{indptr, cols, vals, diag, (long long)N, C, t, (long long)ldt, prev, (long long)ldp, alpha, beta, out, (long long)ldo,
-             chunks ? kChebVeryLong : 0x7fffffff, chunks ? scratch : nullptr};
-  auto vec_ok = [](const float* p, long long ld) { return ((uintptr_t)p & 15) == 0 && ld % 4 == 0; };
-  const bool vec = C % 4 == 0 && vec_ok(t, ldt) && vec_ok(out, ldo) && (beta == 0.f || vec_ok(prev, ldp)) && (!chunks || vec_ok(scratch, 4));
-  hipStream_t st = (hipStream_t)stream;
-  const dim3 grid((unsigned)((N + kChebWaves - 1) / kChebWaves)), block(kChebThreads);
-  if (vec) hipLaunchKernelGGL(cheb_propagate_kernel<true>, grid, block, 0, st, a);
-  else hipLaunchKernelGGL(cheb_propagate_kernel<false>, grid, block, 0, st, a);
-  TGMX_CHECK_LAUNCH("cheb_propagate");
-  if (chunks) {
-    const dim3 cgrid((unsigned)((nnz + kChebChunk - 1) / kChebChunk));
-    if (vec) hipLaunchKernelGGL(cheb_chunk_kernel<true>, cgrid, block, 0, st, a);
-    else hipLaunchKernelGGL(cheb_chunk_kernel<false>, cgrid, block, 0, st, a);
-    TGMX_CHECK_LAUNCH("cheb_propagate(chunks)");
-    if (vec) hipLaunchKernelGGL(cheb_join_kernel<true>, grid, block, 0, st, a);
-    else hipLaunchKernelGGL(cheb_join_kernel<false>, grid, block, 0, st, a);
-    TGMX_CHECK_LAUNCH("cheb_propagate(join)");
-  }
-  return TGMX_OK;
+  SpmmArgs<ChebEpi> a{indptr, cols, vals, diag, (long long)N, C, t, (long long)ldt, out, (long long)ldo, 0, nullptr,
+                      ChebEpi{prev, (long long)ldp, alpha, beta}};
+  const bool vec = spmm_vec_ok(t, ldt) && spmm_vec_ok(out, ldo) && (beta == 0.f || spmm_vec_ok(prev, ldp));
+  return spmm_run(a, nnz, scratch, scratch_floats, vec, "cheb_propagate", (hipStream_t)stream);
 }
 
 extern "C" int tgmx_gclstm_forward(const tgmx_gclstm_fwd_t* a, tgmx_stream_t stream) {
@@ -545,7 +314,7 @@ extern "C" int tgmx_gclstm_forward(const tgmx_gclstm_fwd_t* a, tgmx_stream_t str
                                          a->cols, a->vals, a->diag, a->lap_ws, a->lap_ws_bytes, a->skipped, stream)))
     return rc;
   const long long fill = in + C + (a->ldop - width);
-  hipLaunchKernelGGL(gclstm_operand_kernel, dim3(cheb_grid(N * fill, 256, 16384)), dim3(256), 0, st, a->x, in, a->H, C, (int)width, (long long)N,
+  hipLaunchKernelGGL(gclstm_operand_kernel, dim3(spmm_grid(N * fill, 256, 16384)), dim3(256), 0, st, a->x, in, a->H, C, (int)width, (long long)N,
                      a->op, (long long)a->ldop);
   TGMX_CHECK_LAUNCH("gclstm_forward(operand)");
   for (int k = 1; k < K; ++k) {  // Tx_1 = L_hat Tx_0;  Tx_k = 2 L_hat Tx_{k-1} - Tx_{k-2}
@@ -555,7 +324,7 @@ extern "C" int tgmx_gclstm_forward(const tgmx_gclstm_fwd_t* a, tgmx_stream_t str
       return rc;
   }
   if ((rc = tgmx_sgemm_nt(a->op, a->ldop, a->W, a->ldw, a->pre, 4 * C, N, 4 * C, (int32_t)width, a->b, 0, 1, 0, 0, 0, stream))) return rc;
-  hipLaunchKernelGGL(gclstm_gates_kernel, dim3(cheb_grid(N * C, 256, 16384)), dim3(256), 0, st, a->pre, a->Cprev, C, (long long)N, a->H_out, a->C_out);
+  hipLaunchKernelGGL(gclstm_gates_kernel, dim3(spmm_grid(N * C, 256, 16384)), dim3(256), 0, st, a->pre, a->Cprev, C, (long long)N, a->H_out, a->C_out);
   TGMX_CHECK_LAUNCH("gclstm_forward(gates)");
   return TGMX_OK;
 }

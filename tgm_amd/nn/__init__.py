@@ -9,6 +9,7 @@ from .graphmixer import GraphMixerEncoder
 from .mlp_mixer import FeedForwardNet, MLPMixer
 from .ncn import NCNPredictor
 from .poptrack import PopTrackPredictor
+from .roland import ROLAND
 from .tcomem import tCoMemPredictor
 from .tgat import TGAT, MergeLayer
 from .tgcn import TGCN, GCNConv
@@ -19,6 +20,6 @@ from . import decoder, encoder, modules  # noqa: E402,F401  (the reference's imp
 
 __all__ = [
     'CTAN', 'CTANMemory', 'ChebConv', 'DyGFormer', 'EdgeBankPredictor', 'EncoderModule', 'FeedForwardNet', 'GCLSTM', 'GCNConv', 'GraphAttentionEmbedding', 'GraphMixerEncoder', 'IdentityMessage', 'LastAggregator',
-    'MLPMixer', 'MeanAggregator', 'MergeLayer', 'NCNPredictor', 'NeighborCooccurrenceEncoder', 'PopTrackPredictor', 'RandomProjectionModule', 'TGAT', 'TGCN',
+    'MLPMixer', 'MeanAggregator', 'MergeLayer', 'NCNPredictor', 'NeighborCooccurrenceEncoder', 'PopTrackPredictor', 'ROLAND', 'RandomProjectionModule', 'TGAT', 'TGCN',
     'TGNMemory', 'TGNStep', 'TPNet', 'TemporalAttention', 'Time2Vec', 'TransformerConv', 'TransformerEncoder', 'invalidate_parameter_caches', 'sampled_edge_list', 'tCoMemPredictor',
 ]  # fmt: skip

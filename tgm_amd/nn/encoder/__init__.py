@@ -3,16 +3,17 @@
 them.  The submodule names resolve to the modules that hold the implementations -- nothing is defined here."""
 import sys
 
-from .. import ctan, dygformer, gclstm, tgat, tgcn, tgn, tpnet
+from .. import ctan, dygformer, gclstm, roland, tgat, tgcn, tgn, tpnet
 from ..ctan import CTAN, CTANMemory
 from ..dygformer import DyGFormer
 from ..gclstm import GCLSTM
+from ..roland import ROLAND
 from ..tgat import TGAT
 from ..tgcn import TGCN
 from ..tpnet import RandomProjectionModule, TPNet
 from ..tgn import GraphAttentionEmbedding, IdentityMessage, LastAggregator, MeanAggregator, TGNMemory
 
-for _m in (ctan, dygformer, gclstm, tgat, tgcn, tgn, tpnet):
+for _m in (ctan, dygformer, gclstm, roland, tgat, tgcn, tgn, tpnet):
     sys.modules[f'{__name__}.{_m.__name__.rsplit(".", 1)[1]}'] = _m
 
-__all__ = ['CTAN', 'CTANMemory', 'DyGFormer', 'GCLSTM', 'GraphAttentionEmbedding', 'IdentityMessage', 'LastAggregator', 'MeanAggregator', 'RandomProjectionModule', 'TGAT', 'TGCN', 'TGNMemory', 'TPNet']
+__all__ = ['CTAN', 'CTANMemory', 'DyGFormer', 'GCLSTM', 'GraphAttentionEmbedding', 'IdentityMessage', 'LastAggregator', 'MeanAggregator', 'ROLAND', 'RandomProjectionModule', 'TGAT', 'TGCN', 'TGNMemory', 'TPNet']

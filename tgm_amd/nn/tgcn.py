@@ -13,7 +13,7 @@ from __future__ import annotations
 import ctypes
 import math
 import os
-from typing import Optional
+from typing import List, Optional, Tuple, Union
 
 import torch
 import torch.nn as nn
@@ -23,12 +23,16 @@ from .. import _native
 from . import _ops
 from ._fwd_plumbing import carve_scratch, up4
 from ._paramver import TransientCaches
+from .gclstm import _edge_weight, _endpoints, _Skipped
 
 _MAX_DENSE_NODES = 16384  # A_hat is dense: 16384^2 floats = 1 GiB
 
 
-class GCNConv(nn.Module):
-    """x' = D^-1/2 (A + I) D^-1/2 x W^T + b  (PyG parameter layout: ``lin.weight`` [out, in], ``bias`` [out])."""
+class GCNConv(_Skipped, nn.Module):
+    """x' = D^-1/2 (A + I) D^-1/2 x W^T + b  (PyG parameter layout: ``lin.weight`` [out, in], ``bias`` [out]).
+
+    Up to ``_MAX_DENSE_NODES`` nodes the adjacency is dense and the propagation a GEMM; above, without gradients, it is a CSR by
+    destination and a gather SpMM (``tgmx_gcn_norm_csr`` + ``tgmx_gcn_propagate``; ``check()`` reports edges skipped there)."""
 
     def __init__(self, in_channels: int, out_channels: int, improved: bool = False, cached: bool = False, add_self_loops: bool = True) -> None:
         super().__init__()
@@ -36,11 +40,22 @@ class GCNConv(nn.Module):
         self.improved, self.cached, self.add_self_loops = improved, cached, add_self_loops
         self.lin = nn.Linear(in_channels, out_channels, bias=False)
         self.bias = nn.Parameter(torch.zeros(out_channels))
-        bound = math.sqrt(6.0 / (in_channels + out_channels))  # glorot
+        self.reset_parameters()
+
+    def reset_parameters(self) -> None:
+        bound = math.sqrt(6.0 / (self.in_channels + self.out_channels))  # glorot
         nn.init.uniform_(self.lin.weight, -bound, bound)
+        nn.init.zeros_(self.bias)
 
     def forward(self, x: Tensor, edge_index: Tensor, edge_weight: Optional[Tensor] = None) -> Tensor:
         x = _ops._f32c(x, 'x')
+        if x.shape[0] > _MAX_DENSE_NODES and not (
+            torch.is_grad_enabled() and (x.requires_grad or self.lin.weight.requires_grad or self.bias.requires_grad)
+        ):
+            xw = torch.empty((x.shape[0], self.out_channels), dtype=torch.float32, device=x.device)
+            _ops.sgemm_nt(x, self.lin.weight.detach(), xw)
+            csr = gcn_norm_csr(edge_index, edge_weight, x.shape[0], 2.0 if self.improved else 1.0, self.add_self_loops, self._skipped(x.device))
+            return gcn_propagate(csr, xw, torch.empty_like(xw), bias=self.bias.detach())
         A = normalized_adjacency(edge_index, edge_weight, x.shape[0], 2.0 if self.improved else 1.0, self.add_self_loops)
         if torch.is_grad_enabled() and (x.requires_grad or self.lin.weight.requires_grad or self.bias.requires_grad):
             from ._tgcn_train import AdjMatmulFn
@@ -72,6 +87,83 @@ def normalized_adjacency(edge_index: Tensor, edge_weight: Optional[Tensor], N: i
         'tgmx_gcn_norm_dense',
     )  # fmt: skip
     return A[:, :N]
+
+
+def gcn_norm_csr(edge_index: Tensor, edge_weight: Optional[Tensor], N: int, fill: float, add_self_loops: bool, skipped: Optional[Tensor] = None,
+                 bufs: Optional[List[Tensor]] = None) -> Tuple[Tensor, Tensor, Tensor, Tensor]:  # fmt: skip
+    """(indptr, cols, vals, diag) of ``tgmx_gcn_norm_csr``: D^-1/2 (A + I) D^-1/2 as a CSR by destination, any number of nodes;
+    ``bufs``: the caller's five regions (indptr, cols, vals, diag, workspace)."""
+    lib = _native.load()
+    src, dst = _endpoints(edge_index)
+    E, dev = src.numel(), src.device
+    w = _edge_weight(edge_weight, E)
+    nbytes = lib.tgmx_gcn_workspace_bytes(E, N)
+    if nbytes == 0:
+        raise ValueError(f'GCNConv: {E} edges over {N} nodes are out of range')
+    if bufs is None:
+        bufs = [torch.empty(n, dtype=torch.int32, device=dev) for n in (N + 1, max(E, 1), max(E, 1))]
+        bufs += [torch.empty(N, dtype=torch.float32, device=dev), torch.empty((nbytes + 3) // 4, dtype=torch.int32, device=dev)]
+    indptr, cols, vals, diag, ws = bufs
+    _native.check(
+        lib.tgmx_gcn_norm_csr(src.data_ptr(), dst.data_ptr(), 1 if src.dtype == torch.int64 else 0, _native.ptr(w), E, N, float(fill),
+                              1 if add_self_loops else 0, indptr.data_ptr(), cols.data_ptr(), vals.data_ptr(), diag.data_ptr(), ws.data_ptr(),
+                              ws.numel() * 4, _native.ptr(skipped), _native.stream_ptr()),
+        'tgmx_gcn_norm_csr',
+    )  # fmt: skip
+    return indptr, cols, vals.view(torch.float32), diag
+
+
+def gcn_propagate(csr: Tuple[Tensor, Tensor, Tensor, Tensor], t: Tensor, out: Tensor, bias: Optional[Tensor] = None, epilogue: str = 'none',
+                  prev: Optional[Tensor] = None, tau: Union[float, Tensor] = 0.0, prev_copy: Optional[Tensor] = None,
+                  scratch: Optional[Tensor] = None, E: Optional[int] = None) -> Tensor:  # fmt: skip
+    """out = epi(A_hat t + bias) over 2-D row-major float32 views (column slices of a wider operand are fine); ``epilogue``: ``'none'``,
+    ``'relu'`` or ``'tau'`` (``tau prev + (1 - tau) relu(.)``, ``tau`` a float or a one-element float32 tensor on the device, which is
+    not read back).  ``E``: the edge count the CSR was built from when ``cols`` is longer."""
+    indptr, cols, vals, diag = csr
+    tau_t = tau if isinstance(tau, Tensor) else None
+    _native.check(
+        _native.load().tgmx_gcn_propagate(indptr.data_ptr(), cols.data_ptr(), vals.data_ptr(), diag.data_ptr(), t.shape[0], t.shape[1], t.data_ptr(),
+                                          t.stride(0), _native.ptr(bias), _native.GCN_EPI[epilogue], _native.ptr(prev),
+                                          0 if prev is None else prev.stride(0), 0.0 if tau_t is not None else float(tau), _native.ptr(tau_t),
+                                          _native.ptr(prev_copy), 0 if prev_copy is None else prev_copy.stride(0), out.data_ptr(), out.stride(0),
+                                          cols.numel() if E is None else E, _native.ptr(scratch), 0 if scratch is None else scratch.numel(),
+                                          _native.stream_ptr()),
+        'tgmx_gcn_propagate',
+    )  # fmt: skip
+    return out
+
+
+def composed_gcn_conv(conv: GCNConv, x: Tensor, edge_index: Tensor, skipped: Optional[Tensor] = None) -> Tensor:
+    """``conv`` (no edge weights) composed from torch ops, device-agnostic and without a data-dependent shape: an edge that is dropped
+    (an endpoint out of range; a self loop, which moves to the diagonal) keeps its slot with weight 0."""
+    N, E = x.shape[0], edge_index.shape[1]
+    src, dst = edge_index[0].long(), edge_index[1].long()
+    inside = (src >= 0) & (src < N) & (dst >= 0) & (dst < N)
+    if skipped is not None:
+        skipped += (~inside).sum().to(skipped.dtype)
+    src, dst = src.clamp(0, max(N - 1, 0)), dst.clamp(0, max(N - 1, 0))
+    loop = inside & (src == dst) if conv.add_self_loops else torch.zeros_like(inside)
+    w = (inside & ~loop).to(x.dtype)
+    # unweighted: an explicit self loop weighs 1 whichever of a node's loops is taken; a node without one gets the fill value
+    lw = torch.zeros(N, dtype=x.dtype, device=x.device)
+    if conv.add_self_loops:
+        has = torch.zeros(N, dtype=x.dtype, device=x.device).index_add_(0, dst, loop.to(x.dtype)) > 0
+        lw = torch.where(has, torch.ones_like(lw), torch.full_like(lw, 2.0 if conv.improved else 1.0))
+    xw = conv.lin(x)
+    if not E:
+        dinv = lw.pow(-0.5)
+        dinv = dinv.masked_fill(dinv == float('inf'), 0)
+        return (dinv * lw * dinv).unsqueeze(1) * xw + conv.bias
+    # no float atomics here either (a seeded call repeats bit for bit): the edges in a stable order by destination, one sum per segment
+    dst, order = torch.sort(dst, stable=True)
+    src, w = src[order], w[order]
+    lengths = torch.zeros(N, dtype=torch.int64, device=x.device).index_add_(0, dst, torch.ones_like(dst))
+    deg = lw + torch.segment_reduce(w, 'sum', lengths=lengths, unsafe=True)
+    dinv = deg.pow(-0.5)
+    dinv = dinv.masked_fill(dinv == float('inf'), 0)
+    msg = (dinv[src] * w * dinv[dst]).unsqueeze(1) * xw[src]
+    out = (dinv * lw * dinv).unsqueeze(1) * xw + torch.segment_reduce(msg, 'sum', lengths=lengths, axis=0, unsafe=True)
+    return out + conv.bias
 
 
 class TGCN(TransientCaches, nn.Module):
