@@ -1454,6 +1454,37 @@ typedef struct tgmx_roland_fwd {
 } tgmx_roland_fwd_t;
 int tgmx_roland_forward(const tgmx_roland_fwd_t* args, tgmx_stream_t stream);
 
+/* ---- HistoricalNegativeEdgeSamplerHook (the reference's tgm/hooks/negatives/sampler.py:68-238): per-source history on the device ---- */
+
+/* A source's past destinations, in arrival order, as a chain of segments in `pool` (int32 words): segment k holds ranks
+ * [4 (2^k - 1), 4 (2^(k+1) - 1)) in 1 + 4 2^k words, word 0 the pool offset of segment k - 1 (-1 for k = 0).  cnt [num_nodes]: past events
+ * per source (zeroed when new); tail [num_nodes]: offset of the source's newest segment (whatever where cnt is 0).  state: two int32,
+ * {pool_top, status}, zeroed when new: segments are handed out by atomicAdd on pool_top and never move, so offsets survive the caller
+ * copying the pool into a larger one.  A stream of `count` events over num_nodes ids needs at most
+ * (9 count + 11 min(count, num_nodes)) / 4 + 1 words (csrc/histneg.hip derives it); the caller sizes pool_cap from that before a call.
+ * status, sticky bits: 1 = a source id outside [0, num_nodes) was offered (it draws -1 and joins no history), 2 = the pool was too small
+ * for a group (its events were dropped from the chains) or a chain led outside it.  memory: the reference's [2, mem_cap] int32 log of
+ * (src, dst) in arrival order, `count` events in it before this call. */
+typedef struct tgmx_histneg {
+  int32_t* cnt; int32_t* tail; int64_t num_nodes;
+  int32_t* pool; int64_t pool_cap;
+  int32_t* state;
+  int32_t* memory; int64_t mem_cap; int64_t count;
+  uint64_t seed, call;                                          /* the draw's generator: counter_u32(seed, call, source id) */
+} tgmx_histneg_t;
+size_t tgmx_histneg_workspace_bytes(int64_t B, int64_t num_nodes);
+
+/* One batch of the hook, on `stream`: (a) one lane per position i draws neg[i] = history[umulhi32(counter_u32(seed, call, src[i]), n)] from
+ * the n = cnt[src[i]] destinations stored BEFORE this batch (-1 where n = 0 or the id is out of range), valid[i] = neg[i] != -1,
+ * neg_time[i] = time[i], and logs (src[i], dst[i]) at memory[:, count + i]; (b) a stable radix sort of (source, position) groups the batch,
+ * one lane per group allocates and links the segments the group needs and advances cnt / tail, then every event stores its destination
+ * at rank cnt_before + (its place in the group), so same-source events keep batch order.  neg / valid NULL together: no draw (the first
+ * batch); time / neg_time NULL together: no copy.  ids int64 where the *_is64 flag is set, else int32.  Four launches while the sort is
+ * one (B within rocPRIM's single-block limit); nothing is read back. */
+int tgmx_histneg_step(const tgmx_histneg_t* h, const void* src, int32_t src_is64, const void* dst, int32_t dst_is64, const int64_t* time,
+                      int64_t B, int32_t* neg, int64_t* neg_time, uint8_t* valid, void* workspace, size_t workspace_bytes,
+                      tgmx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

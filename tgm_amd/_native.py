@@ -593,6 +593,21 @@ SIGNATURES['tgmx_gcn_norm_csr'] = (c_int32, [_P, _P, c_int32, _P, c_int64, c_int
 SIGNATURES['tgmx_gcn_propagate'] = (c_int32, [_P, _P, _P, _P, c_int64, c_int32, _P, c_int64, _P, c_int32, _P, c_int64, ctypes.c_float, _P, _P, c_int64, _P, c_int64, c_int64, _P, c_size_t, _P])
 SIGNATURES['tgmx_roland_forward'] = (c_int32, [ctypes.POINTER(RolandFwd), _P])
 
+class HistNeg(ctypes.Structure):
+    """tgmx_histneg_t (include/tgm_amd.h)."""
+
+    _fields_ = [
+        ('cnt', c_void_p), ('tail', c_void_p), ('num_nodes', c_int64),
+        ('pool', c_void_p), ('pool_cap', c_int64),
+        ('state', c_void_p),
+        ('memory', c_void_p), ('mem_cap', c_int64), ('count', c_int64),
+        ('seed', ctypes.c_uint64), ('call', ctypes.c_uint64),
+    ]  # fmt: skip
+
+
+SIGNATURES['tgmx_histneg_workspace_bytes'] = (c_size_t, [c_int64, c_int64])
+SIGNATURES['tgmx_histneg_step'] = (c_int32, [ctypes.POINTER(HistNeg), _P, c_int32, _P, c_int32, _P, c_int64, _P, _P, _P, _P, c_size_t, _P])
+
 _lib: Optional[ctypes.CDLL] = None
 
 

@@ -2,7 +2,7 @@ from .base import BaseDGHook, DGHook, SeedableHook, StatefulHook, StatelessHook
 from .dedup import DeduplicationHook
 from .edge_list import SampledEdgeListHook
 from .hook_manager import HookManager
-from .negatives import RandomNegativeEdgeSamplerHook
+from .negatives import HistoricalNegativeEdgeSamplerHook, RandomNegativeEdgeSamplerHook
 from .recency import RecencyNeighborHook
 from .uniform import NeighborSamplerHook
 from .time_gap import TimeGapNeighborHook
@@ -13,6 +13,7 @@ __all__ = [
     'BaseDGHook',
     'DGHook',
     'DeduplicationHook',
+    'HistoricalNegativeEdgeSamplerHook',
     'HookManager',
     'NeighborSamplerHook',
     'RandomNegativeEdgeSamplerHook',
