@@ -56,7 +56,7 @@ int tgmx_version(void);
 /* sizeof of the argument structs as this library was compiled (a binding checks its own mirror against it):
  * 0 tgmx_adj_t, 1 tgmx_recency_step_t, 2 tgmx_tgat_layer_t, 3 tgmx_tgat_model_t, 4 tgmx_tgat_hop_t, 5 tgmx_tgat_layout_t,
  * 6 tgmx_pipeline_t, 7 tgmx_pipeline_out_t, 8 tgmx_dropout_t, 9 tgmx_tgn_memory_fwd_t, 10 tgmx_tconv_fwd_t, 11 tgmx_pipeline_post_t,
- * 12 tgmx_tgn_step_t, ..., 22 tgmx_ctan_fwd_t, 24 tgmx_gclstm_fwd_t, 26 tgmx_roland_fwd_t (23 and 25 are reserved and answer 0: tests/test_ctan_cpu.py and
+ * 12 tgmx_tgn_step_t, ..., 22 tgmx_ctan_fwd_t, 24 tgmx_gclstm_fwd_t, 26 tgmx_roland_fwd_t, 27 tgmx_decoder_fwd_t (23 and 25 are reserved and answer 0: tests/test_ctan_cpu.py and
  * tests/test_gclstm_cpu.py pin them) */
 size_t tgmx_abi_sizeof(int32_t which);
 const char* tgmx_last_error(void);
@@ -1484,6 +1484,78 @@ size_t tgmx_histneg_workspace_bytes(int64_t B, int64_t num_nodes);
 int tgmx_histneg_step(const tgmx_histneg_t* h, const void* src, int32_t src_is64, const void* dst, int32_t dst_is64, const int64_t* time,
                       int64_t B, int32_t* neg, int64_t* neg_time, uint8_t* valid, void* workspace, size_t workspace_bytes,
                       tgmx_stream_t stream);
+
+/* ---- the decoders (the reference's tgm/nn/decoder/{link,node,graph}proppred.py, tgm/nn/modules/aggregation.py): an MLP head over merged
+ * pairs of embedding rows, over rows, or over one pooled row.  Every entry sums in one fixed order: a call is reproducible bit for bit. ---- */
+
+#define TGMX_DECODER_ACT_NONE 0
+#define TGMX_DECODER_ACT_RELU 1
+
+/* C[R, N] = act(A1[ia] Wa^T + A2[ib] Wb^T + bias): row r of the first operand is A1[ia[r], :K1] (ia NULL: row r), likewise the second;
+ * A2 = NULL is the one-operand case.  Wa [N, ldwa >= K1], Wb [N, ldwb >= K2], bias [N] or NULL.  Exact-fp32 MFMA (16x16x4), the rows
+ * gathered into LDS through the indices; the K loop runs through the first operand and then the second in 64-wide chunks, ascending (inside a
+ * chunk four interleaved sets of 4-wide k-steps, folded pairwise).  n1 / n2: rows of A1 /
+ * A2.  An index outside [0, n) is not dereferenced: row r of C is NaN and *bad (device, accumulating; may be NULL) counts it. */
+int tgmx_decoder_pair_gemm(const float* A1, int64_t lda1, int64_t n1, const int32_t* ia, const float* A2, int64_t lda2, int64_t n2,
+                           const int32_t* ib, const float* Wa, int64_t ldwa, int32_t K1, const float* Wb, int64_t ldwb, int32_t K2,
+                           const float* bias, int32_t act, float* C, int64_t ldc, int64_t R, int32_t N, int32_t* bad, tgmx_stream_t stream);
+
+/* The table form's per-pair stage over P [NP, ldp >= 2H] (P = z [Wa ; Wb]^T + [bias | 0]): h = act(P[a, :H] + P[c, H:2H]) for
+ *   M >= 0: B queries; query b pairs a = ia[b] with c = ib[b] (candidate 0) and with its candidates neg[b M + j - 1] (off NULL: M each) or
+ *           neg[off[b] + j - 1] (off [B + 1], int64; max_candidates: the longest list, a host number); pair j of query b is output row
+ *           b (M + 1) + j, or off[b] + b + j.  A workgroup loads the query's half row once and reuses it for its candidates;
+ *   M = -1: B flat pairs, a = ia[r], c = ib[r], output row r.
+ * out_dim in 1..16: out[row, :out_dim] = h w_last^T + b_last (w_last [out_dim, H]);  out_dim = 0: out[row, :H] = h (leading dimension ldo).
+ * Lanes span H and fold by a fixed butterfly; for H < 64 several pairs share a wave.  ids int64 where idx64 is set, else int32.  An index
+ * outside [0, NP) is not dereferenced: the pair's outputs are NaN and *bad counts it.  TGMX_E_UNSUPPORTED for H > 512 or out_dim > 16. */
+int tgmx_decoder_score(const float* P, int64_t ldp, int64_t NP, int32_t H, const void* ia, const void* ib, const void* neg, int32_t idx64,
+                       const int64_t* off, int64_t M, int64_t max_candidates, int64_t B, int32_t act, const float* w_last, const float* b_last,
+                       int32_t out_dim, float* out, int64_t ldo, int32_t* bad, tgmx_stream_t stream);
+
+/* out[r, :out_dim] = x[r, :K] W^T + b as row dots, out_dim <= 16 (W [out_dim, K] contiguous); TGMX_E_UNSUPPORTED beyond that (a wider last
+ * layer is a tgmx_sgemm_nt). */
+int tgmx_decoder_tail(const float* x, int64_t ldx, int64_t R, int32_t K, const float* W, const float* b, int32_t out_dim, float* out,
+                      tgmx_stream_t stream);
+
+/* out[:D] = the column sum (mean != 0: the column mean, sum / N) of x [N, D].  Chunks of 128 rows, then the chunks, each level
+ * in four interleaved chains folded pairwise, in double, rounded to float32 once: the order depends on N alone, no atomics.  scratch: tgmx_pool_rows_scratch_floats(N, D) floats, 8-byte aligned (0 for N <= 128).
+ * TGMX_E_UNSUPPORTED for D > 1536. */
+size_t tgmx_pool_rows_scratch_floats(int64_t N, int32_t D);
+int tgmx_pool_rows(const float* x, int64_t ldx, int64_t N, int32_t D, int32_t mean, float* scratch, size_t scratch_floats, float* out,
+                   tgmx_stream_t stream);
+
+#define TGMX_DECODER_MAX_LAYERS 8
+#define TGMX_DECODER_ROWS 0   /* the layers over a1 [R, D] (NodePredictor), or over its pooled row (GraphPredictor) */
+#define TGMX_DECODER_PAIR 1   /* merge = tgmx_decoder_pair_gemm into h[1] [R, H], then the layers */
+#define TGMX_DECODER_TABLE 2  /* merge = P = a1 wa^T + mbias (wa [2H, ldwa] stacked, mbias [2H]) and tgmx_decoder_score, then the layers */
+#define TGMX_DECODER_POOL_NONE 0
+#define TGMX_DECODER_POOL_MEAN 1
+#define TGMX_DECODER_POOL_SUM 2
+
+typedef struct tgmx_decoder_layer {
+  const float* w; const float* b; int32_t in, out;    /* Linear: [out, in], [out] */
+} tgmx_decoder_layer_t;
+
+/* One row x [layers[0].in] through num_layers Linears (relu between, none after the last) into out [layers[last].out]: one workgroup, the
+ * row in LDS, each dot accumulated in double and rounded once.  TGMX_E_UNSUPPORTED for a layer wider than 4096. */
+int tgmx_decoder_row_mlp(const float* x, const tgmx_decoder_layer_t* layers, int32_t num_layers, float* out, tgmx_stream_t stream);
+
+/* A whole head as ONE call.  layers: the Linears after the merge stage, relu between them and none after the last (ConcatMerge: the first
+ * Linear of the model IS the merge stage, with merge_act = relu; LearnableSumMerge: the merge stage is lin_src / lin_dst with merge_act =
+ * none and every Linear of the model is a layer).  A last layer of at most 16 outputs is tgmx_decoder_tail -- in the table form with one
+ * layer it rides tgmx_decoder_score -- the others are tgmx_sgemm_nt flipping between h[0] and h[1] ([R, widest hidden layer] each); for R = 1 the
+ * layers are one tgmx_decoder_row_mlp.
+ * PAIR: ia / ib are int32 (or NULL).  TABLE: ia, ib, neg, off, M, max_candidates, B as in tgmx_decoder_score; R: output rows in all.
+ * Every buffer is the caller's; nothing is read back. */
+typedef struct tgmx_decoder_fwd {
+  int32_t form, merge_act, pool, num_layers;
+  const float* a1; int64_t lda1, n1; const float* a2; int64_t lda2, n2;
+  const void* ia; const void* ib; const void* neg; const int64_t* off; int32_t idx64, reserved_; int64_t M, max_candidates, B, R;
+  const float* wa; int64_t ldwa; const float* wb; int64_t ldwb; const float* mbias; int32_t D, H;
+  tgmx_decoder_layer_t layers[TGMX_DECODER_MAX_LAYERS];
+  float* P; float* h[2]; float* pooled; float* pool_ws; size_t pool_ws_floats; int32_t* bad; float* out;
+} tgmx_decoder_fwd_t;
+int tgmx_decoder_forward(const tgmx_decoder_fwd_t* args, tgmx_stream_t stream);
 
 #ifdef __cplusplus
 }

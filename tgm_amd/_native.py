@@ -608,6 +608,46 @@ class HistNeg(ctypes.Structure):
 SIGNATURES['tgmx_histneg_workspace_bytes'] = (c_size_t, [c_int64, c_int64])
 SIGNATURES['tgmx_histneg_step'] = (c_int32, [ctypes.POINTER(HistNeg), _P, c_int32, _P, c_int32, _P, c_int64, _P, _P, _P, _P, c_size_t, _P])
 
+
+DECODER_MAX_LAYERS = 8  # TGMX_DECODER_MAX_LAYERS
+DECODER_MAX_TAIL = 16  # widest last layer the row-dot kernels take
+DECODER_MAX_H = 512  # widest half row of tgmx_decoder_score
+DECODER_ROW_MLP_MAX = 4096  # widest layer of tgmx_decoder_row_mlp
+DECODER_FORM = {'rows': 0, 'pair': 1, 'table': 2}  # TGMX_DECODER_*
+DECODER_POOL = {None: 0, 'mean': 1, 'sum': 2}  # TGMX_DECODER_POOL_*
+
+
+class DecoderLayer(ctypes.Structure):
+    """tgmx_decoder_layer_t (include/tgm_amd.h)."""
+
+    _fields_ = [('w', c_void_p), ('b', c_void_p), ('in_', c_int32), ('out', c_int32)]
+
+
+class DecoderFwd(ctypes.Structure):
+    """tgmx_decoder_fwd_t (include/tgm_amd.h)."""
+
+    _fields_ = [
+        ('form', c_int32), ('merge_act', c_int32), ('pool', c_int32), ('num_layers', c_int32),
+        ('a1', c_void_p), ('lda1', c_int64), ('n1', c_int64), ('a2', c_void_p), ('lda2', c_int64), ('n2', c_int64),
+        ('ia', c_void_p), ('ib', c_void_p), ('neg', c_void_p), ('off', c_void_p), ('idx64', c_int32), ('reserved_', c_int32),
+        ('M', c_int64), ('max_candidates', c_int64), ('B', c_int64), ('R', c_int64),
+        ('wa', c_void_p), ('ldwa', c_int64), ('wb', c_void_p), ('ldwb', c_int64), ('mbias', c_void_p), ('D', c_int32), ('H', c_int32),
+        ('layers', DecoderLayer * DECODER_MAX_LAYERS),
+        ('P', c_void_p), ('h', c_void_p * 2), ('pooled', c_void_p), ('pool_ws', c_void_p), ('pool_ws_floats', c_size_t), ('bad', c_void_p),
+        ('out', c_void_p),
+    ]  # fmt: skip
+
+
+SIGNATURES['tgmx_decoder_pair_gemm'] = (c_int32, [_P, c_int64, c_int64, _P, _P, c_int64, c_int64, _P, _P, c_int64, c_int32, _P, c_int64, c_int32, _P, c_int32,
+                                                  _P, c_int64, c_int64, c_int32, _P, _P])
+SIGNATURES['tgmx_decoder_score'] = (c_int32, [_P, c_int64, c_int64, c_int32, _P, _P, _P, c_int32, _P, c_int64, c_int64, c_int64, c_int32, _P, _P, c_int32,
+                                              _P, c_int64, _P, _P])
+SIGNATURES['tgmx_decoder_tail'] = (c_int32, [_P, c_int64, c_int64, c_int32, _P, _P, c_int32, _P, _P])
+SIGNATURES['tgmx_pool_rows_scratch_floats'] = (c_size_t, [c_int64, c_int32])
+SIGNATURES['tgmx_pool_rows'] = (c_int32, [_P, c_int64, c_int64, c_int32, c_int32, _P, c_size_t, _P, _P])
+SIGNATURES['tgmx_decoder_row_mlp'] = (c_int32, [_P, ctypes.POINTER(DecoderLayer), c_int32, _P, _P])
+SIGNATURES['tgmx_decoder_forward'] = (c_int32, [ctypes.POINTER(DecoderFwd), _P])
+
 _lib: Optional[ctypes.CDLL] = None
 
 

@@ -2,7 +2,7 @@
 
 The names and meanings are the reference's (tgm/exceptions.py:1-47), so callers' ``except`` clauses keep working
 unchanged; ``NativeLibraryError`` is ours.  The classes are built from one table (name, what it means) instead of
-nine two-line class statements.
+ten two-line class statements.
 """
 from typing import Dict, Type
 
@@ -13,6 +13,7 @@ class TGMError(Exception):
 
 _MEANINGS = (
     ('BadHookProtocolError', 'The object handed to HookManager is not a DGHook.'),
+    ('BadAggregatorProtocolError', 'The merge / pooling object handed to a decoder is not an Aggregator.'),
     ('BadEncoderProtocolError', 'The module handed to HookManager.validate_requirement is not an EncoderModule.'),
     ('UnresolvableHookDependenciesError', 'requires/produces of the registered hooks admit no execution order.'),
     ('InvalidNodeIDError', 'A node id collides with PADDED_NODE_ID or overflows int32.'),

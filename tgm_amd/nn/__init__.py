@@ -4,6 +4,9 @@ from .base import EncoderModule
 from .ctan import CTAN, CTANMemory
 from .edgebank import EdgeBankPredictor
 from .gclstm import GCLSTM, ChebConv
+from .graphproppred import GraphPredictor
+from .linkproppred import LinkPredictor
+from .nodeproppred import NodePredictor
 from .dygformer import DyGFormer, NeighborCooccurrenceEncoder, TransformerEncoder
 from .graphmixer import GraphMixerEncoder
 from .mlp_mixer import FeedForwardNet, MLPMixer
@@ -19,7 +22,7 @@ from .tpnet import RandomProjectionModule, TPNet
 from . import decoder, encoder, modules  # noqa: E402,F401  (the reference's import paths: tgm.nn.encoder.tgn, tgm.nn.modules.attention, ...)
 
 __all__ = [
-    'CTAN', 'CTANMemory', 'ChebConv', 'DyGFormer', 'EdgeBankPredictor', 'EncoderModule', 'FeedForwardNet', 'GCLSTM', 'GCNConv', 'GraphAttentionEmbedding', 'GraphMixerEncoder', 'IdentityMessage', 'LastAggregator',
-    'MLPMixer', 'MeanAggregator', 'MergeLayer', 'NCNPredictor', 'NeighborCooccurrenceEncoder', 'PopTrackPredictor', 'ROLAND', 'RandomProjectionModule', 'TGAT', 'TGCN',
+    'CTAN', 'CTANMemory', 'ChebConv', 'DyGFormer', 'EdgeBankPredictor', 'EncoderModule', 'FeedForwardNet', 'GCLSTM', 'GCNConv', 'GraphAttentionEmbedding', 'GraphMixerEncoder', 'GraphPredictor', 'IdentityMessage', 'LastAggregator', 'LinkPredictor',
+    'MLPMixer', 'MeanAggregator', 'MergeLayer', 'NCNPredictor', 'NeighborCooccurrenceEncoder', 'NodePredictor', 'PopTrackPredictor', 'ROLAND', 'RandomProjectionModule', 'TGAT', 'TGCN',
     'TGNMemory', 'TGNStep', 'TPNet', 'TemporalAttention', 'Time2Vec', 'TransformerConv', 'TransformerEncoder', 'invalidate_parameter_caches', 'sampled_edge_list', 'tCoMemPredictor',
 ]  # fmt: skip
