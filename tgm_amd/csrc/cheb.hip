@@ -3,22 +3,13 @@
 // reference (torch_geometric); it is implemented from its published definition (get_laplacian, then 2 L / lambda_max - I): parity unpinned
 // upstream.
 //
-// Laplacian: the E edges become keys (dst << cb | src), cb = bits of N, carrying their edge position through ONE stable radix sort
-// (rocPRIM); a self loop or an edge with an endpoint outside [0, N) gets a key behind every row.  Row pointers are a binary search per node
-// (no scan, no atomics).  The degree is taken over the SOURCE index: without weights it is an integer count (integer atomics do not depend
-// on the order of arrival); with weights a second stable sort by source groups the positions and one wave per node sums its group in a
-// fixed order.  Nothing here adds floats with atomics: two runs give the same bits.
+// Laplacian: the builder of edge_csr.h with keys (dst << cb | src).  Dropped: a self loop, and an edge with an endpoint outside [0, N).  The
+// degree is taken over the SOURCE index: without weights it is an integer count (integer atomics do not depend on the order of arrival); with
+// weights a second stable sort by source groups the positions and one wave per node sums its group in a fixed order.
 //
-// Propagate: out = alpha (L_hat t) + beta prev, gather form (the kernels live in spmm.h, shared with gcn.hip).  A workgroup of four waves owns four destination rows; a wave walks its row's
-// entries four at a time (four source rows requested before the first is used), the lanes spread over the channels.  A row of more than
-// kSpmmLongRow entries is cut into four contiguous pieces, one per wave, and the partial sums meet in LDS in wave order.  A row of more than
-// kSpmmVeryLong entries (a hub: the most popular page of a wiki-shaped day has 21 000) would still keep one workgroup busy long after the
-// others have left, so the caller's scratch takes it out of that launch: a second launch cuts the ENTRY array into chunks of kSpmmChunk, a
-// workgroup per chunk sums the part of the (at most two) very long rows its chunk holds, and a third adds a row's chunk sums in ascending
-// chunk order.  Every order is fixed by the CSR alone.
-#include <rocprim/device/device_radix_sort.hpp>
-
+// Propagate: out = alpha (L_hat t) + beta prev, the gather kernels of spmm.h (shared with gcn.hip) with ChebEpi as their epilogue.
 #include "common.h"
+#include "edge_csr.h"
 #include "spmm.h"
 
 namespace tgmx {
@@ -33,11 +24,11 @@ __global__ __launch_bounds__(256) void cheb_keys_kernel(const void* __restrict__
                                                         unsigned* __restrict__ ks, int* __restrict__ cnt, int* __restrict__ skipped) {
   const long long step = (long long)gridDim.x * blockDim.x;
   for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < E; e += step) {
-    const long long s = spmm_idx(src, is64, e), d = spmm_idx(dst, is64, e);
+    const long long s = ld_idx(src, is64, e), d = ld_idx(dst, is64, e);
     const bool in = s >= 0 && s < N && d >= 0 && d < N;
     const bool ok = in && s != d;
     if (!in && skipped) atomicAdd(skipped, 1);
-    kd[e] = ok ? ((unsigned long long)d << cb) | (unsigned long long)s : 1ull << (2 * cb);  // sorts behind every row
+    kd[e] = key_of(ok, d, s, cb);
     pos[e] = (unsigned)e;
     if (ks) ks[e] = ok ? (unsigned)s : (unsigned)N;
     else if (ok) atomicAdd(&cnt[s], 1);
@@ -57,19 +48,8 @@ __global__ __launch_bounds__(kChebThreads) void cheb_degree_kernel(const unsigne
   for (long long i = (long long)blockIdx.x * kChebWaves + threadIdx.x / kWave; i < N; i += nwaves) {
     float deg;
     if (ks_sorted) {
-      long long lo = 0, hi = E;
-      while (lo < hi) {
-        const long long mid = (lo + hi) >> 1;
-        if ((long long)ks_sorted[mid] < i) lo = mid + 1;
-        else hi = mid;
-      }
-      long long end = lo;
-      hi = E;
-      while (end < hi) {
-        const long long mid = (end + hi) >> 1;
-        if ((long long)ks_sorted[mid] <= i) end = mid + 1;
-        else hi = mid;
-      }
+      const long long lo = key_lower_bound(ks_sorted, E, (unsigned)i);  // the node's group of the source-sorted keys: [lo, end)
+      const long long end = lo + key_lower_bound(ks_sorted + lo, E - lo, (unsigned)i + 1);
       float part = 0.f;
       for (long long j = lo + lane; j < end; j += kWave) part += w[ps_sorted[j]];
 #pragma unroll
@@ -98,68 +78,56 @@ __global__ __launch_bounds__(kChebThreads) void cheb_degree_kernel(const unsigne
   }
 }
 
-__global__ __launch_bounds__(256) void cheb_rows_kernel(const unsigned long long* __restrict__ sorted, const unsigned* __restrict__ pos_sorted,
-                                                        const float* __restrict__ w, const float* __restrict__ dis, long long E, long long N, int cb,
-                                                        int norm, float lambda_max, const float* __restrict__ lambda_ptr,
-                                                        int32_t* __restrict__ indptr, int32_t* __restrict__ cols, float* __restrict__ vals) {
-  const long long step = (long long)gridDim.x * blockDim.x;
-  const long long total = E > N + 1 ? E : N + 1;
-  const float lmax = lambda_ptr ? lambda_ptr[0] : lambda_max;
-  const unsigned long long behind = 1ull << (2 * cb);
-  for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += step) {
-    if (t < E) {
-      const unsigned long long key = sorted[t];
-      if (key < behind) {
-        const long long s = (long long)(key & ((1ull << cb) - 1)), d = (long long)(key >> cb);
-        const float we = w ? w[pos_sorted[t]] : 1.f;
-        float m;
-        if (norm == TGMX_CHEB_NORM_SYM) m = dis[s] * we * dis[d];
-        else if (norm == TGMX_CHEB_NORM_RW) m = dis[s] * we;
-        else m = we;
-        float v = (2.0f * -m) / lmax;
-        if (isinf(v)) v = 0.f;
-        cols[t] = (int32_t)s;
-        vals[t] = v;
-      }
-    }
-    if (t <= N) {
-      const unsigned long long want = (unsigned long long)t << cb;
-      long long lo = 0, hi = E;
-      while (lo < hi) {
-        const long long mid = (lo + hi) >> 1;
-        if (sorted[mid] < want) lo = mid + 1;
-        else hi = mid;
-      }
-      indptr[t] = (int32_t)lo;
-    }
+// entry t of the Laplacian, from source s to destination d: -w_e scaled by the normalisation's degree factors, then 2 / lambda_max
+struct ChebEntry {
+  const unsigned* pos_sorted;
+  const float* w;
+  const float* dis;
+  int norm;
+  float lambda_max;
+  const float* lambda_ptr;
+  float* vals;
+  __device__ __forceinline__ void operator()(long long t, long long s, long long d) const {
+    const float lmax = lambda_ptr ? lambda_ptr[0] : lambda_max;
+    const float we = w ? w[pos_sorted[t]] : 1.f;
+    float m;
+    if (norm == TGMX_CHEB_NORM_SYM) m = dis[s] * we * dis[d];
+    else if (norm == TGMX_CHEB_NORM_RW) m = dis[s] * we;
+    else m = we;
+    float v = (2.0f * -m) / lmax;
+    if (isinf(v)) v = 0.f;
+    vals[t] = v;
   }
-}
-
-struct ChebLayout {
-  size_t kd_in, kd_out, pos_in, pos_out, ks_in, ks_out, ps_out, cnt, dis, temp, temp_bytes, total;
 };
-static int cheb_layout(long long E, long long N, ChebLayout& w) {
-  auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+
+struct ChebWorkspace {
+  unsigned long long *kd_in, *kd_out;
+  unsigned *pos_in, *pos_out, *ks_in, *ks_out, *ps_out;
+  int* cnt;
+  float* dis;
+  char* temp;
+  size_t temp_bytes, total;
+};
+static int cheb_carve(void* workspace, long long E, long long N, ChebWorkspace& w) {
+  WorkspaceCarver c(workspace);
   const size_t n = (size_t)(E > 0 ? E : 1);
-  size_t off = 0;
-  w.kd_in = off; off = up(off + n * 8);
-  w.kd_out = off; off = up(off + n * 8);
-  w.pos_in = off; off = up(off + n * 4);
-  w.pos_out = off; off = up(off + n * 4);
-  w.ks_in = off; off = up(off + n * 4);
-  w.ks_out = off; off = up(off + n * 4);
-  w.ps_out = off; off = up(off + n * 4);
-  w.cnt = off; off = up(off + (size_t)N * 4);
-  w.dis = off; off = up(off + (size_t)N * 4);
-  size_t tb64 = 0, tb32 = 0;
-  if (rocprim::radix_sort_pairs(nullptr, tb64, (const unsigned long long*)nullptr, (unsigned long long*)nullptr, (const unsigned*)nullptr,
-                                (unsigned*)nullptr, n, 0u, 64u) != hipSuccess)
-    return TGMX_E_LAUNCH;
+  w.kd_in = c.take<unsigned long long>(n);
+  w.kd_out = c.take<unsigned long long>(n);
+  w.pos_in = c.take<unsigned>(n);
+  w.pos_out = c.take<unsigned>(n);
+  w.ks_in = c.take<unsigned>(n);
+  w.ks_out = c.take<unsigned>(n);
+  w.ps_out = c.take<unsigned>(n);
+  w.cnt = c.take<int>((size_t)N);
+  w.dis = c.take<float>((size_t)N);
+  size_t tb32 = 0;  // the sort by source: 32-bit keys
+  if (sort_keys_pos_temp_bytes(n, w.temp_bytes) != hipSuccess) return TGMX_E_LAUNCH;
   if (rocprim::radix_sort_pairs(nullptr, tb32, (const unsigned*)nullptr, (unsigned*)nullptr, (const unsigned*)nullptr, (unsigned*)nullptr, n, 0u,
                                 32u) != hipSuccess)
     return TGMX_E_LAUNCH;
-  w.temp = off; w.temp_bytes = tb64 > tb32 ? tb64 : tb32; off = up(off + w.temp_bytes);
-  w.total = off + 256;
+  if (tb32 > w.temp_bytes) w.temp_bytes = tb32;
+  w.temp = c.take<char>(w.temp_bytes);
+  w.total = c.total();
   return TGMX_OK;
 }
 
@@ -222,9 +190,9 @@ __global__ __launch_bounds__(256) void gclstm_gates_kernel(const float* __restri
 using namespace tgmx;
 
 extern "C" size_t tgmx_cheb_workspace_bytes(int64_t E, int64_t N) {
-  ChebLayout w;
+  ChebWorkspace w;
   if (E < 0 || E >= (1ll << 31) || N <= 0 || N >= (1ll << 31)) return 0;
-  return cheb_layout(E, N, w) == TGMX_OK ? w.total : 0;
+  return cheb_carve(nullptr, E, N, w) == TGMX_OK ? w.total : 0;
 }
 
 extern "C" int tgmx_cheb_laplacian(const void* src, const void* dst, int32_t idx64, const float* w, int64_t E, int64_t N, int32_t normalization,
@@ -234,53 +202,40 @@ extern "C" int tgmx_cheb_laplacian(const void* src, const void* dst, int32_t idx
   TGMX_REQUIRE(normalization >= TGMX_CHEB_NORM_NONE && normalization <= TGMX_CHEB_NORM_RW, "cheb_laplacian: unknown normalization %d", normalization);
   TGMX_REQUIRE(indptr && diag && workspace && (E == 0 || (src && dst && cols && vals)), "cheb_laplacian: null pointer");
   hipStream_t st = (hipStream_t)stream;
-  ChebLayout l;
-  if (cheb_layout(E, N, l) != TGMX_OK || workspace_bytes < l.total) {
+  ChebWorkspace l;
+  if (cheb_carve(workspace, E, N, l) != TGMX_OK || workspace_bytes < l.total) {
     set_error("cheb_laplacian: workspace too small (%zu bytes)", workspace_bytes);
     return TGMX_E_INVALID;
   }
-  char* base = reinterpret_cast<char*>(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-  auto* kd_in = reinterpret_cast<unsigned long long*>(base + l.kd_in);
-  auto* kd_out = reinterpret_cast<unsigned long long*>(base + l.kd_out);
-  auto* pos_in = reinterpret_cast<unsigned*>(base + l.pos_in);
-  auto* pos_out = reinterpret_cast<unsigned*>(base + l.pos_out);
-  auto* ks_in = reinterpret_cast<unsigned*>(base + l.ks_in);
-  auto* ks_out = reinterpret_cast<unsigned*>(base + l.ks_out);
-  auto* ps_out = reinterpret_cast<unsigned*>(base + l.ps_out);
-  int* cnt = reinterpret_cast<int*>(base + l.cnt);
-  float* dis = reinterpret_cast<float*>(base + l.dis);
-  const int cb = spmm_col_bits(N);
+  const int cb = col_bits(N);
   const bool weighted = w != nullptr && E > 0;
-  if (!weighted && hipMemsetAsync(cnt, 0, (size_t)N * sizeof(int), st) != hipSuccess) {
+  if (!weighted && hipMemsetAsync(l.cnt, 0, (size_t)N * sizeof(int), st) != hipSuccess) {
     set_error("cheb_laplacian: clearing the degree counts failed");
     return TGMX_E_LAUNCH;
   }
   if (E > 0) {  // (a zero-length sort is not issued)
-    hipLaunchKernelGGL(cheb_keys_kernel, dim3(spmm_grid(E, 256, 4096)), dim3(256), 0, st, src, dst, idx64, (long long)E, (long long)N, cb, kd_in,
-                       pos_in, weighted ? ks_in : nullptr, cnt, skipped);
+    hipLaunchKernelGGL(cheb_keys_kernel, dim3(grid_for(E, 256, 4096)), dim3(256), 0, st, src, dst, idx64, (long long)E, (long long)N, cb, l.kd_in,
+                       l.pos_in, weighted ? l.ks_in : nullptr, l.cnt, skipped);
     TGMX_CHECK_LAUNCH("cheb_laplacian(keys)");
-    size_t tb = l.temp_bytes;
     if (weighted) {
       int sb = 1;
       while ((1ll << sb) <= N) ++sb;  // the keys go up to N itself (the skipped edges)
-      if (rocprim::radix_sort_pairs(base + l.temp, tb, (const unsigned*)ks_in, ks_out, (const unsigned*)pos_in, ps_out, (size_t)E, 0u, (unsigned)sb,
+      size_t tb = l.temp_bytes;
+      if (rocprim::radix_sort_pairs(l.temp, tb, (const unsigned*)l.ks_in, l.ks_out, (const unsigned*)l.pos_in, l.ps_out, (size_t)E, 0u, (unsigned)sb,
                                     st) != hipSuccess) {
         set_error("cheb_laplacian: radix sort (by source) failed");
         return TGMX_E_LAUNCH;
       }
     }
-    tb = l.temp_bytes;
-    if (rocprim::radix_sort_pairs(base + l.temp, tb, (const unsigned long long*)kd_in, kd_out, (const unsigned*)pos_in, pos_out, (size_t)E, 0u,
-                                  (unsigned)(2 * cb + 1), st) != hipSuccess) {
+    if (sort_keys_pos(l.temp, l.temp_bytes, l.kd_in, l.kd_out, l.pos_in, l.pos_out, (size_t)E, cb, st) != hipSuccess) {
       set_error("cheb_laplacian: radix sort (by destination) failed");
       return TGMX_E_LAUNCH;
     }
   }
-  hipLaunchKernelGGL(cheb_degree_kernel, dim3(spmm_grid(N, kChebWaves, 4096)), dim3(kChebThreads), 0, st, weighted ? ks_out : nullptr, ps_out, w, cnt,
-                     (long long)E, (long long)N, normalization, lambda_max, lambda_ptr, dis, diag);
+  hipLaunchKernelGGL(cheb_degree_kernel, dim3(grid_for(N, kChebWaves, 4096)), dim3(kChebThreads), 0, st, weighted ? l.ks_out : nullptr, l.ps_out, w,
+                     l.cnt, (long long)E, (long long)N, normalization, lambda_max, lambda_ptr, l.dis, diag);
   TGMX_CHECK_LAUNCH("cheb_laplacian(degree)");
-  hipLaunchKernelGGL(cheb_rows_kernel, dim3(spmm_grid(E > N + 1 ? E : N + 1, 256, 4096)), dim3(256), 0, st, kd_out, pos_out, w, dis, (long long)E,
-                     (long long)N, cb, normalization, lambda_max, lambda_ptr, indptr, cols, vals);
+  csr_rows_launch(l.kd_out, (long long)E, (long long)N, cb, indptr, cols, ChebEntry{l.pos_out, w, l.dis, normalization, lambda_max, lambda_ptr, vals}, st);
   TGMX_CHECK_LAUNCH("cheb_laplacian(rows)");
   return TGMX_OK;
 }
@@ -314,7 +269,7 @@ extern "C" int tgmx_gclstm_forward(const tgmx_gclstm_fwd_t* a, tgmx_stream_t str
                                          a->cols, a->vals, a->diag, a->lap_ws, a->lap_ws_bytes, a->skipped, stream)))
     return rc;
   const long long fill = in + C + (a->ldop - width);
-  hipLaunchKernelGGL(gclstm_operand_kernel, dim3(spmm_grid(N * fill, 256, 16384)), dim3(256), 0, st, a->x, in, a->H, C, (int)width, (long long)N,
+  hipLaunchKernelGGL(gclstm_operand_kernel, dim3(grid_for(N * fill, 256, 16384)), dim3(256), 0, st, a->x, in, a->H, C, (int)width, (long long)N,
                      a->op, (long long)a->ldop);
   TGMX_CHECK_LAUNCH("gclstm_forward(operand)");
   for (int k = 1; k < K; ++k) {  // Tx_1 = L_hat Tx_0;  Tx_k = 2 L_hat Tx_{k-1} - Tx_{k-2}
@@ -324,7 +279,7 @@ extern "C" int tgmx_gclstm_forward(const tgmx_gclstm_fwd_t* a, tgmx_stream_t str
       return rc;
   }
   if ((rc = tgmx_sgemm_nt(a->op, a->ldop, a->W, a->ldw, a->pre, 4 * C, N, 4 * C, (int32_t)width, a->b, 0, 1, 0, 0, 0, stream))) return rc;
-  hipLaunchKernelGGL(gclstm_gates_kernel, dim3(spmm_grid(N * C, 256, 16384)), dim3(256), 0, st, a->pre, a->Cprev, C, (long long)N, a->H_out, a->C_out);
+  hipLaunchKernelGGL(gclstm_gates_kernel, dim3(grid_for(N * C, 256, 16384)), dim3(256), 0, st, a->pre, a->Cprev, C, (long long)N, a->H_out, a->C_out);
   TGMX_CHECK_LAUNCH("gclstm_forward(gates)");
   return TGMX_OK;
 }

@@ -47,6 +47,11 @@ inline FastDiv make_fastdiv(uint32_t div) {
 
 __device__ __forceinline__ int lane_id() { return threadIdx.x & (kWave - 1); }
 
+// element i of an integer vector (ids, timestamps) handed over as int32 or int64 (a loader batch is read as it is)
+__device__ __forceinline__ long long ld_idx(const void* p, int is64, long long i) {
+  return is64 ? (long long)static_cast<const int64_t*>(p)[i] : (long long)static_cast<const int32_t*>(p)[i];
+}
+
 // RandomNegativeEdgeSamplerHook's draw i of call `call` (tgm/hooks/negatives/sampler.py:45-65: uniform ids in [low, low + range)):
 // a counter-based generator, so the stand-alone kernel (dedup.hip) and the seed fetch of the lookup kernels (recency.hip,
 // negatives generated in place) produce the same ids

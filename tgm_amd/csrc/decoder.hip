@@ -24,10 +24,6 @@ constexpr int kDecMaxH = 512;      // widest half row the score kernel keeps in 
 constexpr int kDecChunk = 256;     // candidates (or flat pairs) per workgroup of the score / tail kernels
 constexpr int kPoolRows = 128;     // rows per workgroup of the pooling's first stage
 
-__device__ __forceinline__ long long dec_idx(const void* p, int is64, long long i) {
-  return is64 ? (long long)static_cast<const int64_t*>(p)[i] : (long long)static_cast<const int32_t*>(p)[i];
-}
-
 // ---- the pair form ------------------------------------------------------------------------------------------------------------------------
 // v_mfma_f32_16x16x4_f32: lane l holds A[row l & 15][k = l >> 4] and B[k = l >> 4][col l & 15]; D: col = l & 15, row = 4 (l >> 4) + reg.
 // A wave owns 16 columns and both 16-row halves of the block (two accumulators sharing the weight operand).
@@ -145,7 +141,7 @@ __global__ __launch_bounds__(kDecThreads) void decoder_score_kernel(const float*
     j0 = (long long)blockIdx.y * chunk;
     j1 = min(cnt, j0 + chunk);
     if (j0 >= j1) return;
-    qa = dec_idx(ia, is64, b);
+    qa = ld_idx(ia, is64, b);
     q_ok = qa >= 0 && qa < NP;
     for (int c = tid; c < H; c += kDecThreads) s_q[c] = q_ok ? P[qa * ldp + c] : 0.f;
   }
@@ -158,11 +154,11 @@ __global__ __launch_bounds__(kDecThreads) void decoder_score_kernel(const float*
     bool ok = active && q_ok;
     if (active) {
       if (FLAT) {
-        a = dec_idx(ia, is64, j);
-        c = dec_idx(ib, is64, j);
+        a = ld_idx(ia, is64, j);
+        c = ld_idx(ib, is64, j);
         ok = a >= 0 && a < NP;
       } else {
-        c = j == 0 ? dec_idx(ib, is64, blockIdx.x) : dec_idx(neg, is64, neg_base + j - 1);
+        c = j == 0 ? ld_idx(ib, is64, blockIdx.x) : ld_idx(neg, is64, neg_base + j - 1);
       }
       ok = ok && c >= 0 && c < NP;
     }

@@ -57,8 +57,8 @@ struct EbUpdateArgs {
 };
 
 __device__ __forceinline__ bool eb_event(const EbUpdateArgs& a, long long e, unsigned long long* key, long long* t) {
-  const long long s = eb_ld(a.src, a.src64, e), d = eb_ld(a.dst, a.dst64, e);
-  *t = eb_ld(a.ts, a.ts64, e);
+  const long long s = ld_idx(a.src, a.src64, e), d = ld_idx(a.dst, a.dst64, e);
+  *t = ld_idx(a.ts, a.ts64, e);
   *key = eb_key(s, d);
   return eb_id_ok(s, d);
 }
@@ -190,8 +190,8 @@ __global__ __launch_bounds__(kEbThreads) void eb_query_kernel(EbQueryArgs a) {
         nbase = b * a.M;
       }
     }
-    const long long s = eb_ld(a.src, a.src64, b);
-    const long long d = c == 0 ? eb_ld(a.dst, a.dst64, b) : eb_ld(a.neg, a.neg64, nbase + c - 1);
+    const long long s = ld_idx(a.src, a.src64, b);
+    const long long d = c == 0 ? ld_idx(a.dst, a.dst64, b) : ld_idx(a.neg, a.neg64, nbase + c - 1);
     bool hit = false;
     if (eb_id_ok(s, d)) {
       long long ts;

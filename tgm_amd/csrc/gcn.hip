@@ -4,17 +4,16 @@
 // is implemented from its published definition (gcn_norm with add_remaining_self_loops), as tgcn.hip's dense builder is: parity unpinned
 // upstream.
 //
-// Normalisation: the E edges become keys (dst << cb | src), cb = bits of N, carrying their edge position through ONE stable radix sort
-// (rocPRIM); an edge with an endpoint outside [0, N), and with add_self_loops an explicit self loop, gets a key behind every row.  A self
-// loop leaves its edge position in its node's slot by an integer max (the highest position wins, whatever the order of arrival).  One wave
-// per node then finds the node's row by binary search (no scan), takes the degree over the DESTINATION index -- the row's length without
-// weights, with weights the row's weights summed in CSR order, lanes striding, folded in a fixed butterfly -- adds the loop weight and
-// writes deg^-1/2 (in double: vals and diag are then exact values rounded once) and the diagonal.  Nothing here adds floats with atomics: two runs give the same bits.
+// Normalisation: the builder of edge_csr.h with keys (dst << cb | src).  Dropped: an edge with an endpoint outside [0, N), and with
+// add_self_loops an explicit self loop, which leaves its edge position in its node's slot by an integer max (the highest position wins,
+// whatever the order of arrival).  One wave per node then finds the node's row (so indptr is written here, not by the shared rows kernel, and
+// an empty edge list needs no further launch), takes the degree over the DESTINATION index -- the row's length without weights, with weights
+// the row's weights summed in CSR order, lanes striding, folded in a fixed butterfly -- adds the loop weight and writes deg^-1/2 (in double:
+// vals and diag are then exact values rounded once) and the diagonal.
 //
 // Propagate: the gather kernels of spmm.h (shared with cheb.hip) with GcnEpi as their epilogue.
-#include <rocprim/device/device_radix_sort.hpp>
-
 #include "common.h"
+#include "edge_csr.h"
 #include "spmm.h"
 
 namespace tgmx {
@@ -25,24 +24,14 @@ __global__ __launch_bounds__(256) void gcn_keys_kernel(const void* __restrict__ 
                                                        int* __restrict__ loop_e, int* __restrict__ skipped) {
   const long long step = (long long)gridDim.x * blockDim.x;
   for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < E; e += step) {
-    const long long s = spmm_idx(src, is64, e), d = spmm_idx(dst, is64, e);
+    const long long s = ld_idx(src, is64, e), d = ld_idx(dst, is64, e);
     const bool in = s >= 0 && s < N && d >= 0 && d < N;
     const bool loop = in && add_self_loops && s == d;  // folded into the diagonal
     if (!in && skipped) atomicAdd(skipped, 1);
     if (loop) atomicMax(&loop_e[d], (int)e);
-    kd[e] = (in && !loop) ? ((unsigned long long)d << cb) | (unsigned long long)s : 1ull << (2 * cb);  // sorts behind every row
+    kd[e] = key_of(in && !loop, d, s, cb);
     pos[e] = (unsigned)e;
   }
-}
-
-__device__ __forceinline__ long long gcn_lower_bound(const unsigned long long* __restrict__ sorted, long long E, unsigned long long want) {
-  long long lo = 0, hi = E;
-  while (lo < hi) {
-    const long long mid = (lo + hi) >> 1;
-    if (sorted[mid] < want) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
 }
 
 // one wave per node: indptr[i] (and indptr[N] by the last node), dinv[i] = deg^-1/2 (0 for deg = 0), diag[i] = dinv lw dinv.  The degree and
@@ -54,8 +43,8 @@ __global__ __launch_bounds__(kSpmmThreads) void gcn_node_kernel(const unsigned l
   const int lane = lane_id();
   const long long nwaves = (long long)gridDim.x * kSpmmWaves;
   for (long long i = (long long)blockIdx.x * kSpmmWaves + threadIdx.x / kWave; i < N; i += nwaves) {
-    const long long lo = gcn_lower_bound(sorted, E, (unsigned long long)i << cb);
-    const long long hi = gcn_lower_bound(sorted, E, (unsigned long long)(i + 1) << cb);
+    const long long lo = key_lower_bound(sorted, E, key_row_start(i, cb));
+    const long long hi = key_lower_bound(sorted, E, key_row_start(i + 1, cb));
     double deg;
     if (w) {
       double part = 0.0;
@@ -86,35 +75,35 @@ __global__ __launch_bounds__(256) void gcn_entries_kernel(const unsigned long lo
                                                           const float* __restrict__ w, const double* __restrict__ dinv, long long E, int cb,
                                                           int32_t* __restrict__ cols, float* __restrict__ vals) {
   const long long step = (long long)gridDim.x * blockDim.x;
-  const unsigned long long behind = 1ull << (2 * cb);
   for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < E; t += step) {
     const unsigned long long key = sorted[t];
-    if (key >= behind) continue;
-    const long long s = (long long)(key & ((1ull << cb) - 1)), d = (long long)(key >> cb);
+    if (key >= key_behind(cb)) continue;
+    const long long s = key_col(key, cb), d = key_row(key, cb);
     cols[t] = (int32_t)s;
     vals[t] = (float)(dinv[s] * (w ? (double)w[pos_sorted[t]] : 1.0) * dinv[d]);
   }
 }
 
-struct GcnLayout {
-  size_t kd_in, kd_out, pos_in, pos_out, loop_e, dinv, temp, temp_bytes, total;
+struct GcnWorkspace {
+  unsigned long long *kd_in, *kd_out;
+  unsigned *pos_in, *pos_out;
+  int* loop_e;
+  double* dinv;
+  char* temp;
+  size_t temp_bytes, total;
 };
-static int gcn_layout(long long E, long long N, GcnLayout& w) {
-  auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+static int gcn_carve(void* workspace, long long E, long long N, GcnWorkspace& w) {
+  WorkspaceCarver c(workspace);
   const size_t n = (size_t)(E > 0 ? E : 1);
-  size_t off = 0;
-  w.kd_in = off; off = up(off + n * 8);
-  w.kd_out = off; off = up(off + n * 8);
-  w.pos_in = off; off = up(off + n * 4);
-  w.pos_out = off; off = up(off + n * 4);
-  w.loop_e = off; off = up(off + (size_t)N * 4);
-  w.dinv = off; off = up(off + (size_t)N * 8);
-  size_t tb = 0;
-  if (rocprim::radix_sort_pairs(nullptr, tb, (const unsigned long long*)nullptr, (unsigned long long*)nullptr, (const unsigned*)nullptr,
-                                (unsigned*)nullptr, n, 0u, 64u) != hipSuccess)
-    return TGMX_E_LAUNCH;
-  w.temp = off; w.temp_bytes = tb; off = up(off + tb);
-  w.total = off + 256;
+  w.kd_in = c.take<unsigned long long>(n);
+  w.kd_out = c.take<unsigned long long>(n);
+  w.pos_in = c.take<unsigned>(n);
+  w.pos_out = c.take<unsigned>(n);
+  w.loop_e = c.take<int>((size_t)N);
+  w.dinv = c.take<double>((size_t)N);
+  if (sort_keys_pos_temp_bytes(n, w.temp_bytes) != hipSuccess) return TGMX_E_LAUNCH;
+  w.temp = c.take<char>(w.temp_bytes);
+  w.total = c.total();
   return TGMX_OK;
 }
 
@@ -174,9 +163,9 @@ __global__ __launch_bounds__(256) void roland_gru_kernel(const float* __restrict
 using namespace tgmx;
 
 extern "C" size_t tgmx_gcn_workspace_bytes(int64_t E, int64_t N) {
-  GcnLayout w;
+  GcnWorkspace w;
   if (E < 0 || E >= (1ll << 31) || N <= 0 || N >= (1ll << 31)) return 0;
-  return gcn_layout(E, N, w) == TGMX_OK ? w.total : 0;
+  return gcn_carve(nullptr, E, N, w) == TGMX_OK ? w.total : 0;
 }
 
 extern "C" int tgmx_gcn_norm_csr(const void* src, const void* dst, int32_t idx64, const float* w, int64_t E, int64_t N, float fill,
@@ -185,40 +174,31 @@ extern "C" int tgmx_gcn_norm_csr(const void* src, const void* dst, int32_t idx64
   TGMX_REQUIRE(E >= 0 && E < (1ll << 31) && N > 0 && N < (1ll << 31), "gcn_norm_csr: bad sizes E=%lld N=%lld", (long long)E, (long long)N);
   TGMX_REQUIRE(indptr && diag && workspace && (E == 0 || (src && dst && cols && vals)), "gcn_norm_csr: null pointer");
   hipStream_t st = (hipStream_t)stream;
-  GcnLayout l;
-  if (gcn_layout(E, N, l) != TGMX_OK || workspace_bytes < l.total) {
+  GcnWorkspace l;
+  if (gcn_carve(workspace, E, N, l) != TGMX_OK || workspace_bytes < l.total) {
     set_error("gcn_norm_csr: workspace too small (%zu bytes)", workspace_bytes);
     return TGMX_E_INVALID;
   }
-  char* base = reinterpret_cast<char*>(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-  auto* kd_in = reinterpret_cast<unsigned long long*>(base + l.kd_in);
-  auto* kd_out = reinterpret_cast<unsigned long long*>(base + l.kd_out);
-  auto* pos_in = reinterpret_cast<unsigned*>(base + l.pos_in);
-  auto* pos_out = reinterpret_cast<unsigned*>(base + l.pos_out);
-  int* loop_e = reinterpret_cast<int*>(base + l.loop_e);
-  double* dinv = reinterpret_cast<double*>(base + l.dinv);
-  const int cb = spmm_col_bits(N);
+  const int cb = col_bits(N);
   const float* we = E > 0 ? w : nullptr;
-  if (add_self_loops && hipMemsetAsync(loop_e, 0xff, (size_t)N * sizeof(int), st) != hipSuccess) {  // -1: no explicit self loop
+  if (add_self_loops && hipMemsetAsync(l.loop_e, 0xff, (size_t)N * sizeof(int), st) != hipSuccess) {  // -1: no explicit self loop
     set_error("gcn_norm_csr: clearing the self-loop slots failed");
     return TGMX_E_LAUNCH;
   }
   if (E > 0) {  // (a zero-length sort is not issued)
-    hipLaunchKernelGGL(gcn_keys_kernel, dim3(spmm_grid(E, 256, 4096)), dim3(256), 0, st, src, dst, idx64, (long long)E, (long long)N, cb,
-                       add_self_loops ? 1 : 0, kd_in, pos_in, loop_e, skipped);
+    hipLaunchKernelGGL(gcn_keys_kernel, dim3(grid_for(E, 256, 4096)), dim3(256), 0, st, src, dst, idx64, (long long)E, (long long)N, cb,
+                       add_self_loops ? 1 : 0, l.kd_in, l.pos_in, l.loop_e, skipped);
     TGMX_CHECK_LAUNCH("gcn_norm_csr(keys)");
-    size_t tb = l.temp_bytes;
-    if (rocprim::radix_sort_pairs(base + l.temp, tb, (const unsigned long long*)kd_in, kd_out, (const unsigned*)pos_in, pos_out, (size_t)E, 0u,
-                                  (unsigned)(2 * cb + 1), st) != hipSuccess) {
+    if (sort_keys_pos(l.temp, l.temp_bytes, l.kd_in, l.kd_out, l.pos_in, l.pos_out, (size_t)E, cb, st) != hipSuccess) {
       set_error("gcn_norm_csr: radix sort failed");
       return TGMX_E_LAUNCH;
     }
   }
-  hipLaunchKernelGGL(gcn_node_kernel, dim3(spmm_grid(N, kSpmmWaves, 4096)), dim3(kSpmmThreads), 0, st, kd_out, pos_out, we, loop_e, (long long)E,
-                     (long long)N, cb, fill, add_self_loops ? 1 : 0, indptr, dinv, diag);
+  hipLaunchKernelGGL(gcn_node_kernel, dim3(grid_for(N, kSpmmWaves, 4096)), dim3(kSpmmThreads), 0, st, l.kd_out, l.pos_out, we, l.loop_e, (long long)E,
+                     (long long)N, cb, fill, add_self_loops ? 1 : 0, indptr, l.dinv, diag);
   TGMX_CHECK_LAUNCH("gcn_norm_csr(nodes)");
   if (E > 0) {
-    hipLaunchKernelGGL(gcn_entries_kernel, dim3(spmm_grid(E, 256, 4096)), dim3(256), 0, st, kd_out, pos_out, we, dinv, (long long)E, cb, cols, vals);
+    hipLaunchKernelGGL(gcn_entries_kernel, dim3(grid_for(E, 256, 4096)), dim3(256), 0, st, l.kd_out, l.pos_out, we, l.dinv, (long long)E, cb, cols, vals);
     TGMX_CHECK_LAUNCH("gcn_norm_csr(entries)");
   }
   return TGMX_OK;
@@ -280,7 +260,7 @@ extern "C" int tgmx_roland_forward(const tgmx_roland_fwd_t* a, tgmx_stream_t str
     } else {
       if ((rc = tgmx_sgemm_nt(op, 2 * C, a->w_ih[l], C, a->gi, 3 * C, N, 3 * C, C, a->b_ih[l], 0, 1, 0, 0, 0, stream))) return rc;
       if ((rc = tgmx_sgemm_nt(op + C, 2 * C, a->w_hh[l], C, a->gh, 3 * C, N, 3 * C, C, a->b_hh[l], 0, 1, 0, 0, 0, stream))) return rc;
-      hipLaunchKernelGGL(roland_gru_kernel, dim3(spmm_grid(N * C, 256, 16384)), dim3(256), 0, st, a->gi, a->gh, op + C, (long long)2 * C, C, (long long)N,
+      hipLaunchKernelGGL(roland_gru_kernel, dim3(grid_for(N * C, 256, 16384)), dim3(256), 0, st, a->gi, a->gh, op + C, (long long)2 * C, C, (long long)N,
                          a->out[l]);
       TGMX_CHECK_LAUNCH("roland_forward(gru)");
     }

@@ -32,9 +32,6 @@ namespace tgmx {
 constexpr int kHnBadId = 1, kHnOverflow = 2;  // status bits
 constexpr int kHnThreads = 256;
 
-__device__ __forceinline__ long long hn_ld(const void* p, int is64, long long i) {
-  return is64 ? reinterpret_cast<const long long*>(p)[i] : (long long)reinterpret_cast<const int*>(p)[i];
-}
 __device__ __forceinline__ int hn_seg(int r) { return 31 - __clz((r >> 2) + 1); }     // r >= 0
 __device__ __forceinline__ int hn_seg_first(int k) { return 4 * ((1 << k) - 1); }    // first rank of segment k
 
@@ -77,7 +74,7 @@ __device__ __forceinline__ long long hn_grid_step() { return (long long)gridDim.
 // (a): the draw from the state before this batch, the log, the sort's keys
 __global__ __launch_bounds__(kHnThreads) void hn_sample_kernel(HnArgs a) {
   for (long long i = hn_grid_start(); i < a.B; i += hn_grid_step()) {
-    const long long s = hn_ld(a.src, a.src64, i), d = hn_ld(a.dst, a.dst64, i);
+    const long long s = ld_idx(a.src, a.src64, i), d = ld_idx(a.dst, a.dst64, i);
     const bool ok = s >= 0 && s < a.N;
     a.memory[a.count + i] = (int)s;
     a.memory[a.mem_cap + a.count + i] = (int)d;

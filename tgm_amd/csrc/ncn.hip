@@ -2,33 +2,21 @@
 // batch's sampled subgraph as sorted rows, the per-pair row intersection with its gather-sum over x, and the inference forward as one call
 // (the two Linear layers run on the exact-fp32 MFMA GEMM of csrc/tgat.hip through tgmx_sgemm_nt_ep).
 //
-// Adjacency: the 2 E half-edges (a -> b) and (b -> a) become keys (row << cb | col), cb = bits of N, and ONE radix sort of the keys
-// (rocPRIM) IS the adjacency: equal keys are interchangeable, so no stability argument is needed and nothing depends on scheduling.  The
-// rows keep multiplicities as repeated entries; indptr is a binary search per node over the sorted keys (no atomics, no scan).  A row may be
-// as long as 2 E.
+// Adjacency: the builder of edge_csr.h over the 2 E half-edges (a -> b) and (b -> a), keys only: the sorted keys ARE the adjacency (equal
+// keys are interchangeable, so no edge position rides along).  Dropped: an edge with an endpoint outside [0, N).  The rows keep
+// multiplicities as repeated entries; a row may be as long as 2 E.
 //
 // Pair kernel: one wave per pair.  The lanes take entries of the shorter row, 64 at a time; the first entry of every run of equal ids
 // binary-searches the longer row (and its own run's end), the wave ballots the matches and visits them in ascending id, the lanes spread
 // over the channels.  The order of the sum is fixed and there are no float atomics: two runs give the same bits.
-#include <rocprim/device/device_radix_sort.hpp>
-
 #include "common.h"
+#include "edge_csr.h"
 
 namespace tgmx {
 
 constexpr int kNcnThreads = 256;
 constexpr int kNcnWaves = kNcnThreads / kWave;
 constexpr int kNcnChPerLane = 4;  // channels a lane accumulates per pass over the intersection: 256 channels a pass
-
-__device__ __forceinline__ long long ld_idx(const void* p, int is64, long long i) {
-  return is64 ? (long long)reinterpret_cast<const int64_t*>(p)[i] : (long long)reinterpret_cast<const int32_t*>(p)[i];
-}
-
-static int col_bits(long long N) {
-  int cb = 1;
-  while ((1ll << cb) < N) ++cb;
-  return cb;
-}
 
 // ---- adjacency ----------------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void ncn_keys_kernel(const void* __restrict__ ei, int is64, long long stride, long long E, long long N, int cb,
@@ -39,43 +27,25 @@ __global__ __launch_bounds__(256) void ncn_keys_kernel(const void* __restrict__ 
     const long long a = ld_idx(ei, is64, e), b = ld_idx(ei, is64, stride + e);
     const bool ok = a >= 0 && a < N && b >= 0 && b < N;
     const long long row = h < E ? a : b, col = h < E ? b : a;
-    keys[h] = ok ? ((unsigned long long)row << cb) | (unsigned long long)col : 1ull << (2 * cb);  // an edge with an endpoint outside sorts behind every row
+    keys[h] = key_of(ok, row, col, cb);
   }
 }
 
-__global__ __launch_bounds__(256) void ncn_rows_kernel(const unsigned long long* __restrict__ sorted, long long n, long long N, int cb,
-                                                       int32_t* __restrict__ indptr, int32_t* __restrict__ cols) {
-  const long long step = (long long)gridDim.x * blockDim.x;
-  const long long total = n > N + 1 ? n : N + 1;
-  for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += step) {
-    if (t < n) cols[t] = (int32_t)(sorted[t] & ((1ull << cb) - 1));
-    if (t <= N) {
-      const unsigned long long want = (unsigned long long)t << cb;
-      long long lo = 0, hi = n;
-      while (lo < hi) {
-        const long long mid = (lo + hi) >> 1;
-        if (sorted[mid] < want) lo = mid + 1;
-        else hi = mid;
-      }
-      indptr[t] = (int32_t)lo;
-    }
-  }
-}
-
-struct AdjLayout {
-  size_t k_in, k_out, temp, temp_bytes, total;
+struct AdjWorkspace {
+  unsigned long long *k_in, *k_out;
+  char* temp;
+  size_t temp_bytes, total;
 };
-static int adj_layout(long long E, AdjLayout& w) {
-  auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+static int adj_carve(void* workspace, long long E, AdjWorkspace& w) {
+  WorkspaceCarver c(workspace);
   const size_t n = (size_t)(E > 0 ? 2 * E : 1);
-  size_t off = 0;
-  w.k_in = off; off = up(off + n * 8);
-  w.k_out = off; off = up(off + n * 8);
-  size_t tb = 0;
-  if (rocprim::radix_sort_keys(nullptr, tb, (const unsigned long long*)nullptr, (unsigned long long*)nullptr, n, 0u, 64u) != hipSuccess)
+  w.k_in = c.take<unsigned long long>(n);
+  w.k_out = c.take<unsigned long long>(n);
+  w.temp_bytes = 0;
+  if (rocprim::radix_sort_keys(nullptr, w.temp_bytes, (const unsigned long long*)nullptr, (unsigned long long*)nullptr, n, 0u, 64u) != hipSuccess)
     return TGMX_E_LAUNCH;
-  w.temp = off; w.temp_bytes = tb; off = up(off + tb);
-  w.total = off + 256;
+  w.temp = c.take<char>(w.temp_bytes);
+  w.total = c.total();
   return TGMX_OK;
 }
 
@@ -207,19 +177,14 @@ __global__ __launch_bounds__(kNcnThreads) void ncn_cn_kernel(CnArgs a) {
   }
 }
 
-static unsigned grid_for(long long items, int per_block, long long cap) {
-  long long blocks = (items + per_block - 1) / per_block;
-  return (unsigned)(blocks < 1 ? 1 : (blocks > cap ? cap : blocks));
-}
-
 }  // namespace tgmx
 
 using namespace tgmx;
 
 extern "C" size_t tgmx_ncn_adj_workspace_bytes(int64_t E) {
-  AdjLayout w;
+  AdjWorkspace w;
   if (E < 0 || 2 * E >= (1ll << 31)) return 0;
-  return adj_layout(E, w) == TGMX_OK ? w.total : 0;
+  return adj_carve(nullptr, E, w) == TGMX_OK ? w.total : 0;
 }
 
 extern "C" int tgmx_ncn_adj_build(const void* edge_index, int32_t is64, int64_t row_stride, int64_t E, int64_t N, int32_t* indptr,
@@ -232,25 +197,22 @@ extern "C" int tgmx_ncn_adj_build(const void* edge_index, int32_t is64, int64_t 
   const long long n = 2 * E;
   const unsigned long long* sorted = nullptr;
   if (E > 0) {
-    AdjLayout w;
-    if (adj_layout(E, w) != TGMX_OK || workspace_bytes < w.total) {
+    AdjWorkspace w;
+    if (adj_carve(workspace, E, w) != TGMX_OK || workspace_bytes < w.total) {
       set_error("ncn_adj_build: workspace too small (%zu bytes)", workspace_bytes);
       return TGMX_E_INVALID;
     }
-    char* base = reinterpret_cast<char*>(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-    auto* k_in = reinterpret_cast<unsigned long long*>(base + w.k_in);
-    auto* k_out = reinterpret_cast<unsigned long long*>(base + w.k_out);
     hipLaunchKernelGGL(ncn_keys_kernel, dim3(grid_for(n, 256, 4096)), dim3(256), 0, st, edge_index, is64, (long long)row_stride, (long long)E,
-                       (long long)N, cb, k_in);
+                       (long long)N, cb, w.k_in);
     TGMX_CHECK_LAUNCH("ncn_adj_build(keys)");
-    size_t tb = w.temp_bytes;
-    if (rocprim::radix_sort_keys(base + w.temp, tb, (const unsigned long long*)k_in, k_out, (size_t)n, 0u, (unsigned)(2 * cb + 1), st) != hipSuccess) {
+    if (rocprim::radix_sort_keys(w.temp, w.temp_bytes, (const unsigned long long*)w.k_in, w.k_out, (size_t)n, 0u, (unsigned)(2 * cb + 1), st) !=
+        hipSuccess) {
       set_error("ncn_adj_build: radix sort failed");
       return TGMX_E_LAUNCH;
     }
-    sorted = k_out;
+    sorted = w.k_out;
   }
-  hipLaunchKernelGGL(ncn_rows_kernel, dim3(grid_for(n > N + 1 ? n : N + 1, 256, 4096)), dim3(256), 0, st, sorted, n, (long long)N, cb, indptr, cols);
+  csr_rows_launch(sorted, n, (long long)N, cb, indptr, cols, NoEntryValue{}, st);
   TGMX_CHECK_LAUNCH("ncn_adj_build(rows)");
   return TGMX_OK;
 }

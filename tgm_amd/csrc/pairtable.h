@@ -22,9 +22,6 @@ __device__ __forceinline__ unsigned long long eb_hash(unsigned long long x) {  /
   x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
   return x ^ (x >> 31);
 }
-__device__ __forceinline__ long long eb_ld(const void* p, int is64, long long i) {
-  return is64 ? (long long)reinterpret_cast<const int64_t*>(p)[i] : (long long)reinterpret_cast<const int32_t*>(p)[i];
-}
 __device__ __forceinline__ bool eb_id_ok(long long s, long long d) { return s >= 0 && s < (1ll << 31) && d >= 0 && d < (1ll << 31); }
 
 // slot of `key`, claimed if absent; -1 when `cap` probes found neither the key nor room

@@ -1,5 +1,5 @@
-// The gather SpMM the sparse propagations share (cheb.hip: the scaled Laplacian of ChebConv; gcn.hip: GCN's normalised adjacency), and the
-// small helpers of their CSR builders.  out[i] = epi(i, diag[i] t[i] + sum_{j in row i} vals[j] t[cols[j]]) over a CSR by destination.
+// The gather SpMM the sparse propagations share (cheb.hip: the scaled Laplacian of ChebConv; gcn.hip: GCN's normalised adjacency; the CSR
+// comes from edge_csr.h).  out[i] = epi(i, diag[i] t[i] + sum_{j in row i} vals[j] t[cols[j]]) over a CSR by destination.
 //
 // A workgroup of four waves owns four destination rows; a wave walks its row's entries four at a time (four source rows requested before the
 // first is used), the lanes spread over the channels.  A row of more than kSpmmLongRow entries is cut into four contiguous pieces, one per
@@ -23,21 +23,6 @@ constexpr int kSpmmLongRow = 64;   // entries; longer rows are split over the wo
 constexpr int kSpmmChPerLane = 4;  // channels a lane covers per pass: 256 channels a pass
 constexpr int kSpmmChunk = 1024;   // entries of the CSR one workgroup of the chunk launch covers
 constexpr int kSpmmVeryLong = 2 * kSpmmChunk;  // rows longer than this go through the chunk launch: a chunk then meets at most two of them
-
-__device__ __forceinline__ long long spmm_idx(const void* p, int is64, long long i) {
-  return is64 ? (long long)reinterpret_cast<const int64_t*>(p)[i] : (long long)reinterpret_cast<const int32_t*>(p)[i];
-}
-
-static int spmm_col_bits(long long N) {
-  int cb = 1;
-  while ((1ll << cb) < N) ++cb;
-  return cb;
-}
-
-static unsigned spmm_grid(long long items, int per_block, long long cap) {
-  long long blocks = (items + per_block - 1) / per_block;
-  return (unsigned)(blocks < 1 ? 1 : (blocks > cap ? cap : blocks));
-}
 
 // a lane's channels of one pass: VEC: the float4 at c0 + 4 lane;  else c0 + lane + 64 q, q < 4
 template <bool VEC>

@@ -68,9 +68,9 @@ __global__ __launch_bounds__(kTcBlockMax) void tc_update_kernel(TcArgs a, TcUpda
   long long s = -1, d = -1, t = 0;
   bool live = false;
   if (tid < u.n) {
-    s = eb_ld(u.src, u.src64, u.first + tid);
-    d = eb_ld(u.dst, u.dst64, u.first + tid);
-    t = eb_ld(u.ts, u.ts64, u.first + tid);
+    s = ld_idx(u.src, u.src64, u.first + tid);
+    d = ld_idx(u.dst, u.dst64, u.first + tid);
+    t = ld_idx(u.ts, u.ts64, u.first + tid);
     int bad = 0;
     if (!eb_id_ok(s, d)) bad = kTcBadId;
     else bad = (s >= a.N ? kTcBadSrc : 0) | (d >= a.N ? kTcBadDst : 0);
@@ -156,7 +156,7 @@ __global__ __launch_bounds__(kEbThreads) void tc_query_kernel(TcArgs a, TcQueryA
   const long long waves = (long long)gridDim.x * (kEbThreads / kWave);
   const long long negs = q.total - q.B;  // entries of neg[]
   for (long long b = (long long)blockIdx.x * (kEbThreads / kWave) + threadIdx.x / kWave; b < q.B; b += waves) {
-    const long long s = eb_ld(q.src, q.src64, b);
+    const long long s = ld_idx(q.src, q.src64, b);
     long long nbase = 0, obase = b, cnt = 1;  // flat: row b is the one pair (src[b], dst[b])
     if (q.neg) {                               // one against many: (src[b], dst[b]) then (src[b], neg[b][m])
       if (q.neg_off) {
@@ -174,7 +174,7 @@ __global__ __launch_bounds__(kEbThreads) void tc_query_kernel(TcArgs a, TcQueryA
     const float base = src_ok ? tc_base(a, s, endf, start, size) : 0.0f;  // (the branch is the wave's)
     for (long long c = lane_id(); c < cnt; c += kWave) {
       if (nbase < 0 || obase + c >= q.total || (c > 0 && nbase + c - 1 >= negs)) break;  // offsets that do not describe `total` answers
-      const long long d = c == 0 ? eb_ld(q.dst, q.dst64, b) : eb_ld(q.neg, q.neg64, nbase + c - 1);
+      const long long d = c == 0 ? ld_idx(q.dst, q.dst64, b) : ld_idx(q.neg, q.neg64, nbase + c - 1);
       float v = 0.0f;
       if (d < 0 || d >= (1ll << 31)) {
         atomicOr(a.status, kTcBadId);

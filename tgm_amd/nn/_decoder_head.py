@@ -15,7 +15,7 @@ from .. import _native
 from ._fwd_plumbing import Unsupported, cached_block, carve_scratch, check_supported, needs_torch
 from ._paramver import TransientCaches
 from .aggregation import ConcatMerge, LearnableSumMerge
-from .gclstm import _Skipped
+from ._snapshot import _Skipped
 
 ACT_NONE, ACT_RELU = 0, 1
 

@@ -27,6 +27,17 @@ def i64(t: Tensor) -> Tensor:
     return t if (t.dtype == torch.int64 and t.is_contiguous()) else t.to(torch.int64).contiguous()
 
 
+def ids(t: Tensor) -> Tensor:
+    """int32 / int64 are read in place; anything else (floating tensors of integral values, narrow integers) goes through .long()"""
+    if t.dtype not in (torch.int32, torch.int64):
+        t = t.long()
+    return t.contiguous()
+
+
+def pow2ceil(n: int) -> int:
+    return 1 << max(1, (int(n) - 1).bit_length())
+
+
 class Unsupported(RuntimeError):
     """A native entry point answered TGMX_E_UNSUPPORTED: the caller takes the composed path."""
 
@@ -74,16 +85,25 @@ def weight_keeper() -> Tuple[list, Callable[..., int]]:
     return keep, f32
 
 
-def cached_block(owner: nn.Module, build: Callable[[Callable[..., int]], object]) -> tuple:
-    """(argument block with the weights filled in, the tensors it points at), cached on ``owner`` against its parameters' versions;
-    ``build(f32)`` makes the block, taking every weight pointer from ``f32``."""
+def cached_weights(owner: nn.Module, build: Callable[[], object]):
+    """What ``build()`` makes of ``owner``'s parameters (stacked weights, an argument block), cached on ``owner`` against their versions."""
     d = owner.__dict__
     key = param_key(owner)
     if d.get('_tgmx_wkey') != key:
-        keep, f32 = weight_keeper()
-        d['_tgmx_w'] = (build(f32), keep)
+        d['_tgmx_w'] = build()
         d['_tgmx_wkey'] = key
     return d['_tgmx_w']
+
+
+def cached_block(owner: nn.Module, build: Callable[[Callable[..., int]], object]) -> tuple:
+    """(argument block with the weights filled in, the tensors it points at), cached on ``owner`` against its parameters' versions;
+    ``build(f32)`` makes the block, taking every weight pointer from ``f32``."""
+
+    def block():
+        keep, f32 = weight_keeper()
+        return build(f32), keep
+
+    return cached_weights(owner, block)
 
 
 def fill_mixer_layers(blk, mixers: Iterable[nn.Module], f32: Callable[..., int], who: str) -> float:

@@ -27,15 +27,12 @@ import numpy as np
 import torch
 
 from .. import _native
+from ._fwd_plumbing import ids as _ids, pow2ceil as _pow2ceil
 
 _EMPTY = -1  # the empty key, all ones, as the int64 the table tensor shows
 _OUT_DTYPES = {torch.int32: 0, torch.int64: 1, torch.float32: 2, torch.float64: 3}
 _STATE_WORDS = 4  # tgmx_edgebank_state_bytes() / 8
 STATUS_BAD_ID, STATUS_OVERFLOW = 1, 2
-
-
-def _pow2ceil(n: int) -> int:
-    return 1 << max(1, (int(n) - 1).bit_length())
 
 
 def grow_capacity(capacity: int, offered: int, kept: int, incoming: int) -> int:
@@ -44,13 +41,6 @@ def grow_capacity(capacity: int, offered: int, kept: int, incoming: int) -> int:
     host counts events, not pairs: the load never passes 0.5 without a read from the device."""
     need = 2 * (offered + kept + incoming)
     return capacity if need <= capacity else _pow2ceil(need)
-
-
-def _ids(t: torch.Tensor) -> torch.Tensor:
-    """int32 / int64 are read in place; anything else (floating tensors of integral values, narrow integers) goes through .long()"""
-    if t.dtype not in (torch.int32, torch.int64):
-        t = t.long()
-    return t.contiguous()
 
 
 class EdgeBankPredictor:

@@ -22,8 +22,9 @@ from torch import Tensor
 
 from .. import _native
 from . import _ops
-from ._fwd_plumbing import carve_scratch, needs_torch, up4
-from ._paramver import TransientCaches, param_key
+from ._fwd_plumbing import cached_weights, carve_scratch, needs_torch, up4
+from ._paramver import TransientCaches
+from ._snapshot import _edge_weight, _endpoints, _Skipped, csr_scratch_sizes, propagate, propagate_scratch, scaled_laplacian
 
 _NORMS = (None, 'sym', 'rw')
 LambdaMax = Union[None, float, int, Tensor]
@@ -50,84 +51,6 @@ def _lambda(lambda_max: LambdaMax, normalization: Optional[str], device) -> Tupl
             t = t.to(device)
         return 0.0, t if t.dtype == torch.float32 else t.float()
     return float(lambda_max), None
-
-
-def _endpoints(edge_index: Tensor) -> Tuple[Tensor, Tensor]:
-    """The two rows as contiguous int32 / int64 vectors (an int32 loader batch is read as it is)."""
-    _native.require_device(edge_index, 'edge_index')
-    if edge_index.dim() != 2 or edge_index.shape[0] != 2:
-        raise ValueError(f'expected edge_index [2, E], got {list(edge_index.shape)}')
-    ei = edge_index if edge_index.dtype in (torch.int64, torch.int32) else edge_index.to(torch.int64)
-    src, dst = ei[0], ei[1]
-    return (src if src.is_contiguous() else src.contiguous()), (dst if dst.is_contiguous() else dst.contiguous())
-
-
-def _edge_weight(edge_weight: Optional[Tensor], E: int) -> Optional[Tensor]:
-    if edge_weight is None:
-        return None
-    w = _ops._f32c(edge_weight.detach(), 'edge_weight').reshape(-1)
-    if w.numel() != E:
-        raise ValueError(f'expected one edge weight per edge ({E}), got {w.numel()}')
-    return w
-
-
-class _Skipped:
-    """The device counter of edges skipped for an endpoint outside [0, N), and the ``check()`` that reports it once."""
-
-    def _skipped(self, device) -> Tensor:
-        c = self.__dict__.get('_tgmx_skipped')
-        if c is None or c.device != device:
-            c = self.__dict__['_tgmx_skipped'] = torch.zeros(1, dtype=torch.int32, device=device)
-        return c
-
-    def check(self) -> None:
-        """Raise if a forward saw an ``edge_index`` entry outside ``[0, num_nodes)`` (such edges are skipped).  Reads the device."""
-        c = self.__dict__.get('_tgmx_skipped')
-        if c is not None and int(c.item()):
-            c.zero_()
-            raise ValueError(f'{type(self).__name__}: edge_index held node ids outside [0, num_nodes); those edges were skipped')
-
-
-def scaled_laplacian(edge_index: Tensor, edge_weight: Optional[Tensor], N: int, normalization: Optional[str], lam: float, lam_t: Optional[Tensor],
-                     skipped: Optional[Tensor] = None, bufs: Optional[List[Tensor]] = None) -> Tuple[Tensor, Tensor, Tensor, Tensor]:  # fmt: skip
-    """(indptr, cols, vals, diag) of ``tgmx_cheb_laplacian``; ``bufs``: the caller's five regions (indptr, cols, vals, diag, workspace)."""
-    lib = _native.load()
-    src, dst = _endpoints(edge_index)
-    E, dev = src.numel(), src.device
-    w = _edge_weight(edge_weight, E)
-    nbytes = lib.tgmx_cheb_workspace_bytes(E, N)
-    if nbytes == 0:
-        raise ValueError(f'ChebConv: {E} edges over {N} nodes are out of range')
-    if bufs is None:
-        bufs = [torch.empty(n, dtype=torch.int32, device=dev) for n in (N + 1, max(E, 1), max(E, 1), N, (nbytes + 3) // 4)]
-    indptr, cols, vals, diag, ws = bufs
-    _native.check(
-        lib.tgmx_cheb_laplacian(src.data_ptr(), dst.data_ptr(), 1 if src.dtype == torch.int64 else 0, _native.ptr(w), E, N, _native.CHEB_NORM[normalization],
-                                lam, _native.ptr(lam_t), indptr.data_ptr(), cols.data_ptr(), vals.data_ptr(), diag.data_ptr(), ws.data_ptr(),
-                                ws.numel() * 4, _native.ptr(skipped), _native.stream_ptr()),
-        'tgmx_cheb_laplacian',
-    )  # fmt: skip
-    return indptr, cols, vals, diag
-
-
-def propagate_scratch(lap: Tuple[Tensor, Tensor, Tensor, Tensor], C: int) -> Optional[Tensor]:
-    """The scratch ``propagate`` splits very long rows (hubs) with; ``None`` when the graph is too small to hold one."""
-    n = _native.load().tgmx_cheb_propagate_scratch_floats(lap[1].numel(), C)
-    return torch.empty(n, dtype=torch.float32, device=lap[1].device) if n else None
-
-
-def propagate(lap: Tuple[Tensor, Tensor, Tensor, Tensor], t: Tensor, out: Tensor, prev: Optional[Tensor] = None, alpha: float = 1.0, beta: float = 0.0,
-              scratch: Optional[Tensor] = None) -> Tensor:  # fmt: skip
-    """out = alpha (L_hat t) + beta prev over 2-D row-major float32 views (column slices of a wider operand are fine)."""
-    indptr, cols, vals, diag = lap
-    _native.check(
-        _native.load().tgmx_cheb_propagate(indptr.data_ptr(), cols.data_ptr(), vals.data_ptr(), diag.data_ptr(), t.shape[0], t.shape[1], t.data_ptr(),
-                                           t.stride(0), _native.ptr(prev), 0 if prev is None else prev.stride(0), alpha, beta, out.data_ptr(),
-                                           out.stride(0), cols.numel(), _native.ptr(scratch), 0 if scratch is None else scratch.numel(),
-                                           _native.stream_ptr()),
-        'tgmx_cheb_propagate',
-    )  # fmt: skip
-    return out
 
 
 # ---- the composed path: the same arithmetic from torch ops, with autograd ---------------------------------------------------------------------
@@ -220,15 +143,14 @@ class ChebConv(_Skipped, TransientCaches, nn.Module):
         out = torch.empty((N, self.out_channels), dtype=torch.float32, device=dev)
         if N == 0:
             return out
-        d = self.__dict__
-        key = param_key(self)
         ld = up4(K * cin)
-        if d.get('_tgmx_wkey') != key:
+
+        def stacked():
             W = torch.zeros((self.out_channels, ld), dtype=torch.float32, device=dev)
             W[:, : K * cin] = torch.cat([lin.weight.detach().float() for lin in self.lins], dim=1)
-            d['_tgmx_w'] = (W, None if self.bias is None else _ops._f32c(self.bias.detach(), 'bias'))
-            d['_tgmx_wkey'] = key
-        W, b = d['_tgmx_w']
+            return W, None if self.bias is None else _ops._f32c(self.bias.detach(), 'bias')
+
+        W, b = cached_weights(self, stacked)
         op = (torch.zeros if ld > K * cin else torch.empty)((N, ld), dtype=torch.float32, device=dev)  # [Tx_0 | ... | Tx_{K-1}]
         op[:, :cin].copy_(x)
         if K > 1:
@@ -321,9 +243,8 @@ class GCLSTM(_Skipped, TransientCaches, nn.Module):
             raise ValueError(f'expected H and C [{N}, {Co}], got {list(H.shape)} and {list(C.shape)}')
         width = cin + K * Co
         ld = up4(width)
-        d = self.__dict__
-        key = param_key(self)
-        if d.get('_tgmx_wkey') != key:  # rows of gate g: [W_g^T | lins_g,0 | ... | lins_g,K-1], bias b_g + conv_g.bias
+
+        def stacked():  # rows of gate g: [W_g^T | lins_g,0 | ... | lins_g,K-1], bias b_g + conv_g.bias
             W = torch.zeros((4 * Co, ld), **f32)
             b = torch.empty(4 * Co, **f32)
             for g, (Wg, bg, conv) in enumerate(self._gates()):
@@ -331,20 +252,19 @@ class GCLSTM(_Skipped, TransientCaches, nn.Module):
                 W[rows, :cin] = Wg.detach().t()
                 W[rows, cin:width] = torch.cat([lin.weight.detach().float() for lin in conv.lins], dim=1)
                 b[rows] = bg.detach().reshape(-1) if conv.bias is None else bg.detach().reshape(-1) + conv.bias.detach()
-            d['_tgmx_w'], d['_tgmx_wkey'] = (W, b), key
-        W, b = d['_tgmx_w']
+            return W, b
+
+        W, b = cached_weights(self, stacked)
         src, dst = _endpoints(edge_index)
         E = src.numel()
         w = _edge_weight(edge_weight, E)
-        nbytes = nprop = 0
+        csr, nprop = [N + 1, 0, 0, N, 0], 0  # K = 1: no Laplacian is built
         if K > 1:
             nprop = lib.tgmx_cheb_propagate_scratch_floats(E, Co)
-            nbytes = lib.tgmx_cheb_workspace_bytes(E, N)
-            if nbytes == 0:
-                raise ValueError(f'GCLSTM: {E} edges over {N} nodes are out of range')
-        En = E if K > 1 else 0
-        # indptr, cols, vals, diag, sort workspace (4-byte words), op, pre, the propagate's chunk sums
-        bufs = carve_scratch(self, [N + 1, En, En, N, (nbytes + 3) // 4, N * ld, N * 4 * Co, nprop], dev)
+            csr = csr_scratch_sizes(E, N, lib.tgmx_cheb_workspace_bytes(E, N), 'GCLSTM')
+        # indptr, cols, vals, diag, sort workspace, op, pre, the propagate's chunk sums
+        bufs = carve_scratch(self, csr + [N * ld, N * 4 * Co, nprop], dev)
+        d = self.__dict__
         a = d.get('_tgmx_args')
         if a is None:
             a = d['_tgmx_args'] = _native.GclstmFwd()

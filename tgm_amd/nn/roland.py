@@ -29,7 +29,7 @@ from .. import _native
 from . import _ops
 from ._fwd_plumbing import cached_block, carve_scratch
 from ._paramver import TransientCaches
-from .gclstm import _endpoints, _Skipped
+from ._snapshot import _endpoints, _Skipped, csr_scratch_sizes
 from .tgcn import GCNConv, composed_gcn_conv
 
 _UPDATES = ('moving', 'learnable', 'gru', 'mlp', None)
@@ -138,17 +138,15 @@ class ROLAND(_Skipped, TransientCaches, nn.Module):
             return out
         src, dst = _endpoints(edge_index)
         E = src.numel()
-        nbytes = lib.tgmx_gcn_workspace_bytes(E, N)
-        if nbytes == 0:
-            raise ValueError(f'ROLAND: {E} edges over {N} nodes are out of range')
+        csr = csr_scratch_sizes(E, N, lib.tgmx_gcn_workspace_bytes(E, N), 'ROLAND')
         nprop = lib.tgmx_cheb_propagate_scratch_floats(E, C)
         mode = _native.ROLAND_UPDATE[self.update]
         a, _keep = cached_block(self, self._weights)
         a.x, a.N, a.in_ch, a.C, a.update, a.add_self_loops, a.fill = x.data_ptr(), N, cin, C, mode, 1, 1.0
         a.src, a.dst, a.E, a.idx64 = src.data_ptr(), dst.data_ptr(), E, 1 if src.dtype == torch.int64 else 0
         gru = 3 * N * C if self.update == 'gru' else 0
-        # indptr, cols, vals, diag, sort workspace (4-byte words), the propagate's chunk sums, xw, gi, gh
-        bufs = carve_scratch(self, [N + 1, E, E, N, (nbytes + 3) // 4, nprop, N * C, gru, gru], dev)
+        # indptr, cols, vals, diag, sort workspace, the propagate's chunk sums, xw, gi, gh
+        bufs = carve_scratch(self, csr + [nprop, N * C, gru, gru], dev)
         a.indptr, a.cols, a.vals, a.diag, a.norm_ws = (t.data_ptr() for t in bufs[:5])
         a.norm_ws_bytes, a.skipped = bufs[4].numel() * 4, self._skipped(dev).data_ptr()
         a.prop_ws, a.prop_ws_floats = (bufs[5].data_ptr() if nprop else None), nprop

@@ -32,7 +32,8 @@ import numpy as np
 import torch
 
 from .. import _native
-from .edgebank import EdgeBankPredictor, _ids, _pow2ceil, grow_capacity
+from ._fwd_plumbing import ids as _ids, pow2ceil as _pow2ceil
+from .edgebank import EdgeBankPredictor, grow_capacity
 
 _EMPTY = -1  # the empty key, all ones, as the int64 the table tensor shows
 _QUERY_DTYPES = {torch.int32: 0, torch.int64: 1, torch.float32: 2, torch.float64: 3}

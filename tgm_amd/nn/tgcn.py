@@ -13,7 +13,7 @@ from __future__ import annotations
 import ctypes
 import math
 import os
-from typing import List, Optional, Tuple, Union
+from typing import Optional
 
 import torch
 import torch.nn as nn
@@ -23,7 +23,7 @@ from .. import _native
 from . import _ops
 from ._fwd_plumbing import carve_scratch, up4
 from ._paramver import TransientCaches
-from .gclstm import _edge_weight, _endpoints, _Skipped
+from ._snapshot import _Skipped, gcn_norm_csr, gcn_propagate
 
 _MAX_DENSE_NODES = 16384  # A_hat is dense: 16384^2 floats = 1 GiB
 
@@ -87,50 +87,6 @@ def normalized_adjacency(edge_index: Tensor, edge_weight: Optional[Tensor], N: i
         'tgmx_gcn_norm_dense',
     )  # fmt: skip
     return A[:, :N]
-
-
-def gcn_norm_csr(edge_index: Tensor, edge_weight: Optional[Tensor], N: int, fill: float, add_self_loops: bool, skipped: Optional[Tensor] = None,
-                 bufs: Optional[List[Tensor]] = None) -> Tuple[Tensor, Tensor, Tensor, Tensor]:  # fmt: skip
-    """(indptr, cols, vals, diag) of ``tgmx_gcn_norm_csr``: D^-1/2 (A + I) D^-1/2 as a CSR by destination, any number of nodes;
-    ``bufs``: the caller's five regions (indptr, cols, vals, diag, workspace)."""
-    lib = _native.load()
-    src, dst = _endpoints(edge_index)
-    E, dev = src.numel(), src.device
-    w = _edge_weight(edge_weight, E)
-    nbytes = lib.tgmx_gcn_workspace_bytes(E, N)
-    if nbytes == 0:
-        raise ValueError(f'GCNConv: {E} edges over {N} nodes are out of range')
-    if bufs is None:
-        bufs = [torch.empty(n, dtype=torch.int32, device=dev) for n in (N + 1, max(E, 1), max(E, 1))]
-        bufs += [torch.empty(N, dtype=torch.float32, device=dev), torch.empty((nbytes + 3) // 4, dtype=torch.int32, device=dev)]
-    indptr, cols, vals, diag, ws = bufs
-    _native.check(
-        lib.tgmx_gcn_norm_csr(src.data_ptr(), dst.data_ptr(), 1 if src.dtype == torch.int64 else 0, _native.ptr(w), E, N, float(fill),
-                              1 if add_self_loops else 0, indptr.data_ptr(), cols.data_ptr(), vals.data_ptr(), diag.data_ptr(), ws.data_ptr(),
-                              ws.numel() * 4, _native.ptr(skipped), _native.stream_ptr()),
-        'tgmx_gcn_norm_csr',
-    )  # fmt: skip
-    return indptr, cols, vals.view(torch.float32), diag
-
-
-def gcn_propagate(csr: Tuple[Tensor, Tensor, Tensor, Tensor], t: Tensor, out: Tensor, bias: Optional[Tensor] = None, epilogue: str = 'none',
-                  prev: Optional[Tensor] = None, tau: Union[float, Tensor] = 0.0, prev_copy: Optional[Tensor] = None,
-                  scratch: Optional[Tensor] = None, E: Optional[int] = None) -> Tensor:  # fmt: skip
-    """out = epi(A_hat t + bias) over 2-D row-major float32 views (column slices of a wider operand are fine); ``epilogue``: ``'none'``,
-    ``'relu'`` or ``'tau'`` (``tau prev + (1 - tau) relu(.)``, ``tau`` a float or a one-element float32 tensor on the device, which is
-    not read back).  ``E``: the edge count the CSR was built from when ``cols`` is longer."""
-    indptr, cols, vals, diag = csr
-    tau_t = tau if isinstance(tau, Tensor) else None
-    _native.check(
-        _native.load().tgmx_gcn_propagate(indptr.data_ptr(), cols.data_ptr(), vals.data_ptr(), diag.data_ptr(), t.shape[0], t.shape[1], t.data_ptr(),
-                                          t.stride(0), _native.ptr(bias), _native.GCN_EPI[epilogue], _native.ptr(prev),
-                                          0 if prev is None else prev.stride(0), 0.0 if tau_t is not None else float(tau), _native.ptr(tau_t),
-                                          _native.ptr(prev_copy), 0 if prev_copy is None else prev_copy.stride(0), out.data_ptr(), out.stride(0),
-                                          cols.numel() if E is None else E, _native.ptr(scratch), 0 if scratch is None else scratch.numel(),
-                                          _native.stream_ptr()),
-        'tgmx_gcn_propagate',
-    )  # fmt: skip
-    return out
 
 
 def composed_gcn_conv(conv: GCNConv, x: Tensor, edge_index: Tensor, skipped: Optional[Tensor] = None) -> Tensor:
