@@ -485,7 +485,7 @@ int tgmx_tgat_rres(const float* x, int64_t ldx, int32_t d, const float* tb, cons
                    int32_t T, int32_t O, int64_t R, float* out, int64_t ldo /* 0 = O; columns [O, ldo) zeroed */,
                    tgmx_stream_t stream);
 
-/* C[b] = act(A[b] (M x K, lda) * B[b]^T (B is N x K, ldb) + bias[b]), b < batch with
+/* (csrc/dense.hip, the dense library every model calls.)  C[b] = act(A[b] (M x K, lda) * B[b]^T (B is N x K, ldb) + bias[b]), b < batch with
  * element strides (bias: [batch, N], i.e. [N] when batch = 1); exact-fp32 MFMA.  Replaces the nn.Linear calls of
  * attention.py:96,125 and tgat.py:36-38 and the folded W_K / W_V contractions.
  * Determinism: a call is reproducible bit for bit.  The ORDER in which a row's K products are summed depends on the kernel the call

@@ -144,6 +144,32 @@ def test_sgemm_nt_many_rows_unaligned_views_equal_the_aligned_call():
     assert (o_view.double() - _ref(A, B, None, False)).abs().max().item() <= 4e-4
 
 
+@pytest.mark.parametrize('M', [1, 33, 2048, 2049, 6143, 6144])
+@pytest.mark.parametrize('N,K', [(1, 17), (65, 100), (40, 513), (64, 16)])
+def test_sgemm_nt_ep_epilogues(M, N, K):
+    """``tgmx_sgemm_nt_ep`` on its own, on both sides of every routing boundary (few-row | K-split | LDS-staged rows; K = 16: the direct
+    kernel; K = 513: past the few-row kernel's K).  Without a residual, act 0 / 1 is ``tgmx_sgemm_nt`` with relu 0 / 1: the same route, the
+    same kernel, the same bits.  GELU + residual against float64: the file's 2e-5 sqrt(K) for the product times GELU's largest slope
+    (1.13), plus a few float32 roundings of the epilogue -- 2.5e-5 sqrt(K)."""
+    from tgm_amd.nn import _ops
+    from tgm_amd.nn.mlp_mixer import sgemm_ep
+
+    g = torch.Generator(device='cpu').manual_seed(M * 1000003 + N * 1009 + K)
+    A = torch.randn(M, K, generator=g).cuda()
+    B = torch.randn(N, K, generator=g).cuda()
+    bias = torch.randn(N, generator=g).cuda()
+    res = torch.randn(M, N, generator=g).cuda()
+    for act in (0, 1):
+        ep = sgemm_ep(A, B, torch.full((M, N), float('nan'), device='cuda'), bias=bias, act=act)
+        nt = _ops.sgemm_nt(A, B, torch.full((M, N), float('nan'), device='cuda'), bias=bias, relu=bool(act))
+        assert torch.equal(ep, nt), (M, N, K, act)
+    out = sgemm_ep(A, B, torch.full((M, N), float('nan'), device='cuda'), bias=bias, act=2, res=res)
+    y = A.double() @ B.double().t() + bias.double()
+    ref = 0.5 * y * (1.0 + torch.erf(y * 0.5**0.5)) + res.double()
+    err = (out.double() - ref).abs().max().item()
+    assert err <= 2.5e-5 * (K**0.5), (M, N, K, err)
+
+
 _PAIR_SCRIPT = r'''
 import hashlib, sys, torch
 sys.path.insert(0, %r)

@@ -2,15 +2,14 @@
 // prologue that builds the node / edge / time channel inputs straight from the sampler's hop-0 output (through row indices: no gathered
 // copy of nbr_edge_x), LayerNorm over token rows, multi-head self-attention over the 2 Np tokens of one (src, dst) pair on the exact-fp32
 // MFMA, and the per-side patch mean.  The dense contractions (patch projections, in / out projections, FFN, output layer) run on the
-// GEMM of csrc/tgat.hip through tgmx_sgemm_nt_ep.
+// GEMM of csrc/dense.hip through tgmx_sgemm_nt_ep.
 //
 // Sequence order everywhere: sequence q = 2 p + side (side 0 = the pair's source, 1 = its destination), slot j of it at row q L + j;
 // slot 0 is the seed itself, slot j > 0 the sampler's slot j - 1 of row src_rows[p] / dst_rows[p] (NULL: rows p and P + p).
 #include "common.h"
+#include "gemm.h"
 
 namespace tgmx {
-
-using floatx4 = __attribute__((__vector_size__(4 * sizeof(float)))) float;
 
 constexpr int kDygMaxL = 2048;       // co-occurrence: both id sequences in LDS (16 KiB)
 constexpr int kMhaMaxT = 128;        // tokens per pair
@@ -123,33 +122,6 @@ __global__ __launch_bounds__(256) void dyg_prologue_kernel(DygSeqs sq, const flo
       time_out[r * ldt + ct] = v;
     }
   }
-}
-
-// ---- LayerNorm over token rows ----------------------------------------------------------------------------------------------------------
-
-// one wave per row, biased variance; columns [d, ldy) of y are left alone
-__global__ __launch_bounds__(256) void layernorm_rows_kernel(const float* __restrict__ x, long long ldx, long long R, int d,
-                                                            const float* __restrict__ g, const float* __restrict__ b, float eps,
-                                                            float* __restrict__ y, long long ldy) {
-  const int lane = threadIdx.x & (kWave - 1);
-  const long long r = (long long)blockIdx.x * (blockDim.x / kWave) + threadIdx.x / kWave;
-  if (r >= R) return;
-  const float* __restrict__ row = x + r * ldx;
-  float sum = 0.f;
-  for (int c = lane; c < d; c += kWave) sum += row[c];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
-  const float mean = sum / (float)d;
-  float var = 0.f;
-  for (int c = lane; c < d; c += kWave) {
-    const float t = row[c] - mean;
-    var = __fmaf_rn(t, t, var);
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) var += __shfl_xor(var, o);
-  const float rstd = 1.f / sqrtf(var / (float)d + eps);
-  float* __restrict__ yo = y + r * ldy;
-  for (int c = lane; c < d; c += kWave) yo[c] = (row[c] - mean) * rstd * g[c] + b[c];
 }
 
 // ---- multi-head self-attention over short sequences ---------------------------------------------------------------------------------------
@@ -306,17 +278,6 @@ extern "C" int tgmx_dygformer_prologue(const float* node_x, int64_t num_nodes, i
   hipLaunchKernelGGL(dyg_prologue_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, sq, node_x, (long long)num_nodes, dN, edge_time,
                      nbr_nids, nbr_t, nbr_x, k, dE, tw, tb, dT, node_out, (int)ldn, edge_out, (int)lde, time_out, (int)ldt);
   TGMX_CHECK_LAUNCH("dygformer_prologue");
-  return TGMX_OK;
-}
-
-extern "C" int tgmx_layernorm_rows(const float* x, int64_t ldx, int64_t R, int32_t d, const float* gamma, const float* beta, float eps, float* y,
-                                   int64_t ldy, tgmx_stream_t stream) {
-  TGMX_REQUIRE(R >= 0 && d > 0 && ldx >= d && ldy >= d && (R + 3) / 4 < (1ll << 31), "layernorm_rows: bad sizes R=%lld d=%d", (long long)R, d);
-  if (R == 0) return TGMX_OK;
-  TGMX_REQUIRE(x && gamma && beta && y, "layernorm_rows: null pointer");
-  hipLaunchKernelGGL(layernorm_rows_kernel, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, (hipStream_t)stream, x, (long long)ldx, (long long)R, d,
-                     gamma, beta, eps, y, (long long)ldy);
-  TGMX_CHECK_LAUNCH("layernorm_rows");
   return TGMX_OK;
 }
 

@@ -1,7 +1,7 @@
 // GraphMixer (the reference's examples/linkproppred/graphmixer.py) for gfx950: the time-gap neighbour grouping of its hook and the
 // inference forward of its encoder -- Time2Vec prologue, MLPMixer token mixing (with the next channel LayerNorm fused in), the tail
 // (masked mean over the sampled slots, time-gap node encoder, concatenation).  The dense contractions (projection, channel FFNs, output
-// layer) run on the exact-fp32 MFMA GEMM of csrc/tgat.hip through tgmx_sgemm_nt_ep (GELU / residual epilogues).
+// layer) run on the exact-fp32 MFMA GEMM of csrc/dense.hip through tgmx_sgemm_nt_ep (GELU / residual epilogues).
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include "common.h"

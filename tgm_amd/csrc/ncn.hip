@@ -1,6 +1,6 @@
 // NCNPredictor, the common-neighbour decoder of TNCN (the reference's tgm/nn/decoder/ncnpred.py), for gfx950: the symmetric adjacency of a
 // batch's sampled subgraph as sorted rows, the per-pair row intersection with its gather-sum over x, and the inference forward as one call
-// (the two Linear layers run on the exact-fp32 MFMA GEMM of csrc/tgat.hip through tgmx_sgemm_nt_ep).
+// (the two Linear layers run on the exact-fp32 MFMA GEMM of csrc/dense.hip through tgmx_sgemm_nt_ep).
 //
 // Adjacency: the builder of edge_csr.h over the 2 E half-edges (a -> b) and (b -> a), keys only: the sorted keys ARE the adjacency (equal
 // keys are interchangeable, so no edge position rides along).  Dropped: an edge with an endpoint outside [0, N).  The rows keep

@@ -10,13 +10,12 @@
 //                   d(folded query), d(neighbor features), per-row Time2Vec gradient partials
 // The "NN" products (dX = dY W) reuse sgemm_nt with transposed weight copies.
 #include "common.h"
+#include "gemm.h"
 #include "lanes.h"
 
 #include <type_traits>
 
 namespace tgmx {
-
-using floatx16 = __attribute__((__vector_size__(16 * sizeof(float)))) float;
 
 // ---------------------------------------------------------------------------
 // partial[z][m][n] = sum over rows r in split z of A[r, m] * B[r, n]

@@ -8,7 +8,7 @@
 // all events -- the aggregation kernel walks a node's window and builds only the
 // row(s) it needs.  Everything is a segmented, HBM/latency-bound reduction: one wave
 // per node row, lanes across the message columns.  The dense GRU contractions reuse
-// sgemm_nt (exact-fp32 MFMA) from tgat.hip.
+// sgemm_nt (exact-fp32 MFMA) from dense.hip.
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/iterator/transform_iterator.hpp>

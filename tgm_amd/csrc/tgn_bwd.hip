@@ -1,5 +1,5 @@
 // TGN training: backward of the hand-written forward kernels in tgn.hip (the dense projections differentiate through
-// sgemm_nt / sgemm_tn / colsum from tgat.hip / tgat_bwd.hip).  The reference trains through torch autograd
+// sgemm_nt / sgemm_tn / colsum from dense.hip / tgat_bwd.hip).  The reference trains through torch autograd
 // (examples/linkproppred/tgn.py:97-118); memory and last_update are buffers (no gradient), so the parameters reached
 // are the shared Time2Vec, the GRU cell and the TransformerConv projections.
 #include "common.h"

@@ -1,7 +1,7 @@
 // TPNet (the reference's tgm/nn/encoder/tpnet.py) for gfx950: the streaming temporal walk matrices as random projections (decay +
 // deterministic scatter-add per batch), the pair features (small Gram matrices over gathered table rows), the token-matrix assembly of the
 // encoder, the token mean, and the inference forward as one call.  The dense contractions (the pair-feature MLP, the two projections,
-// the channel FFNs) run on the exact-fp32 MFMA GEMM of csrc/tgat.hip through tgmx_sgemm_nt_ep; token mixing is csrc/mixer.hip's block with a
+// the channel FFNs) run on the exact-fp32 MFMA GEMM of csrc/dense.hip through tgmx_sgemm_nt_ep; token mixing is csrc/mixer.hip's block with a
 // corrected column mean (tgmx_tpnet_token_mix).
 #include "common.h"
 

@@ -1,5 +1,5 @@
 """Thin typed wrappers every encoder shares: the contiguous-float32 conversion of an input on the device (``_f32c``) and the
-``tgmx_time2vec``, ``tgmx_gather_rows`` and ``tgmx_sgemm_nt`` entry points of libtgm_amd.so."""
+``tgmx_time2vec``, ``tgmx_gather_rows`` and ``tgmx_sgemm_nt`` entry points of libtgm_amd.so (``csrc/dense.hip``)."""
 from __future__ import annotations
 
 from typing import Optional

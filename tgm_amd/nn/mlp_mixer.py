@@ -3,7 +3,7 @@
 
 Inference (no gradient needed, and no active dropout) runs natively: ``tgmx_mixer_token`` does the whole token-mixing block of a seed --
 LayerNorm over the K tokens, Linear K -> int(f_t K), exact-erf GELU, Linear -> K, residual -- and also writes the channel LayerNorm of
-its result; the channel FFN is two exact-fp32 MFMA GEMMs with a GELU and a residual epilogue (``tgmx_sgemm_nt_ep``).
+its result; the channel FFN is two exact-fp32 MFMA GEMMs with a GELU and a residual epilogue (``tgmx_sgemm_nt_ep``, ``csrc/dense.hip``).
 
 Training (gradients enabled, or train mode with dropout > 0) is NOT native: it composes the reference arithmetic from torch ops on the
 device under autograd, with the same parameters.  A native backward is future work.  CPU tensors raise ``NativeLibraryError``.

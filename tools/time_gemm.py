@@ -26,7 +26,7 @@ def bench(M, N, K, label=''):
     print(f'{label:14s} M={M:6d} N={N:4d} K={K:4d}: {us:8.1f} us  {2 * M * N * K / us / 1e6:7.2f} TF/s  relerr {err:.1e}', flush=True)
 
 
-print('KS', os.environ.get('TGMX_GEMM_KS'), 'SPLIT', os.environ.get('TGMX_GEMM_SPLIT'))
+print(*(f'{k}={os.environ.get(k)}' for k in ('TGMX_GEMM_SMALL', 'TGMX_GEMM_LDS', 'TGMX_GEMM_PAIR')))  # the A/B knobs of csrc/dense.hip
 bench(12600, 102, 102, 'L1 W_O')
 bench(12600, 273, 51, 'L1 qf/head')
 bench(12600, 51, 273, 'L1 V/head')
