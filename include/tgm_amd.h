@@ -1557,6 +1557,71 @@ typedef struct tgmx_decoder_fwd {
 } tgmx_decoder_fwd_t;
 int tgmx_decoder_forward(const tgmx_decoder_fwd_t* args, tgmx_stream_t stream);
 
+/* ---- BatchAnalyticsHook, EdgeEventsSeenNodesTrackHook, NodeAnalyticsHook (the reference's tgm/hooks/analytics/, tgm/hooks/node_tracks.py):
+ * distinct counts within a batch, membership in sets that grow over the stream, an ordered compaction (csrc/analytics.hip) ---- */
+
+#define TGMX_AN_BAD_ID 1     /* status bits: an id outside [0, num_nodes) was offered (the event took no part) */
+#define TGMX_AN_TABLE_FULL 2 /*              a claim found no room in a pair table (the host's capacity rule makes that a bug) */
+#define TGMX_AN_BAD_TIME 4   /*              a negative time was offered (the pair tables' empty key is all ones; the event took no part) */
+
+/* One batch as the analytics hooks read it.  Any pointer may be NULL (the field is None) with its count 0; src and dst go together.  E edges,
+ * Et edge times (E, or 0 without edge_time), Nn node events, Nt node times (Nn, or 0 without node_x_time).  Integer vectors are int64 where
+ * their *_is64 flag is set, else int32. */
+typedef struct tgmx_an_batch {
+  const void* src; const void* dst; int64_t E; int32_t src_is64, dst_is64;
+  const void* edge_time; int64_t Et; int32_t edge_time_is64, reserved0_;
+  const void* nids; int64_t Nn; int32_t nids_is64, reserved1_;
+  const void* node_time; int64_t Nt; int32_t node_time_is64, reserved2_;
+} tgmx_an_batch_t;
+
+/* out [8] int64 (device): 0 E, 1 Nn, 2 distinct values of edge_time u node_time (time_as_f32 != 0: of the values rounded to float32, the
+ * reference's count when exactly one of the two fields is None), 3 distinct ids of src u dst u nids, 4 the float32 quotient
+ * (float)(2 E) / (float)out[7] in the word's first four bytes (0.0f without edges), 5 E - distinct (src, dst, time) triples (0 unless
+ * Et = E), 6 Nn - distinct (nid, time) pairs (0 unless Nt = Nn), 7 distinct ids of src u dst.  Five batch-local hash sets in `workspace`,
+ * each a power of two >= 2 x its keys of int32 slots holding the index of the key that claimed them; three launches (reset, insert,
+ * finish), nothing read back.  Sizes below 2^28.  Every count is an integer sum: the result does not depend on scheduling. */
+size_t tgmx_batch_analytics_workspace_bytes(int64_t E, int64_t Et, int64_t Nn, int64_t Nt);
+int tgmx_batch_analytics(const tgmx_an_batch_t* batch, int32_t time_as_f32, int64_t* out, void* workspace, size_t workspace_bytes,
+                         tgmx_stream_t stream);
+
+/* mask [num_nodes] bytes.  First launch: mask[id] = 1 for every id of src and dst (ids outside [0, num_nodes) set TGMX_AN_BAD_ID in
+ * state[1] and store nothing).  Second launch (Ny > 0), one workgroup: the positions i of nids [Ny] with mask[nids[i]] != 0, ascending, into
+ * out_pos, the ids there into out_ids (an array of nids' type), their number into state[0].  state: two int64 {count, status}, status
+ * accumulating; the caller reads both at once. */
+int tgmx_seen_nodes_step(uint8_t* mask, int64_t num_nodes, const void* src, int32_t src_is64, const void* dst, int32_t dst_is64, int64_t E,
+                         const void* nids, int32_t nids_is64, int64_t Ny, int64_t* out_pos, void* out_ids, int64_t* state,
+                         tgmx_stream_t stream);
+
+/* NodeAnalyticsHook's state.  slot_of [num_nodes]: index of a tracked node in [0, T), or -1.  first_seen / last_seen [T]: -1 = never.
+ * appearances [T].  Four pair tables (slots as tgmx_edgebank_t's, empty key all ones, capacities powers of two): edges key = src << 32 | dst;
+ * nbrs key = tracked index << 32 | neighbour; times key = the timestamp, value = its dense id in [0, 2^32); apps key = tracked index << 32
+ * | time id.  counters [8] int64: 0 distinct times so far (the next dense id), 1-3 occupancy of edges / nbrs / apps, 4 status
+ * (TGMX_AN_* bits, accumulating), 5 entries moved by rehashes.  Per-call scratch, zeroed when new and left zero by every call: degree / new_nbrs / present [T] int32,
+ * scalars [16] int64.  stamp [num_nodes] int32, zeroed when new: the number of the last call that met the node as an edge endpoint. */
+typedef struct tgmx_node_analytics {
+  const int32_t* slot_of; int64_t num_nodes, T;
+  int64_t* first_seen; int64_t* last_seen; int64_t* appearances;
+  void* edges; int64_t edges_cap; void* nbrs; int64_t nbrs_cap; void* times; int64_t times_cap; void* apps; int64_t apps_cap;
+  int64_t* counters;
+  int32_t* degree; int32_t* new_nbrs; int32_t* present; int32_t* stamp; int64_t* scalars;
+} tgmx_node_analytics_t;
+
+/* One batch, `call` = 1, 2, ... over the state's life.  Events with an id outside [0, num_nodes) or a negative time take no part (status
+ * bits).  Time pass: every time claims its slot in `times` (a new one takes the next dense id) and folds into the batch maximum.  Event pass:
+ * every edge claims (src, dst) in `edges`; per tracked endpoint degree + 1, (endpoint, other end) claimed in `nbrs`, (endpoint, time)
+ * in `apps`; per node event (node, time) in `apps`.  Finalise writes out [T + 2, 8] int64:
+ *   row i < T: {2, degree, appearances, new neighbours, current - first_seen, 0, 0, 0} for a tracked node present in the batch (first_seen
+ *              set if it was -1, last_seen = current), {1, 0, appearances, 0, last - first, current - last, 0, 0} for one seen before, zeros else;
+ *   row T:     {distinct times so far, pairs new to `edges`, distinct edge endpoints of this batch, edges taking part, node events taking part,
+ *              node events of untracked ids, current = max(times of the batch, 0), status};
+ *   row T + 1: {occupancy of edges, nbrs, times, apps, 0, 0, 0, 0}.
+ * Three launches, integer atomics only, nothing read back. */
+int tgmx_node_analytics_step(const tgmx_node_analytics_t* st, const tgmx_an_batch_t* batch, int64_t call, int64_t* out, tgmx_stream_t stream);
+
+/* Every entry of the pair table `from` moves into `to` (to_cap slots, all empty).  state: two int64, counters + 4 of the state above:
+ * {status: TGMX_AN_TABLE_FULL where a claim found no room; entries moved, accumulating}. */
+int tgmx_node_analytics_rehash(const void* from, int64_t from_cap, void* to, int64_t to_cap, int64_t* state, tgmx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

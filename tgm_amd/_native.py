@@ -648,6 +648,39 @@ SIGNATURES['tgmx_pool_rows'] = (c_int32, [_P, c_int64, c_int64, c_int32, c_int32
 SIGNATURES['tgmx_decoder_row_mlp'] = (c_int32, [_P, ctypes.POINTER(DecoderLayer), c_int32, _P, _P])
 SIGNATURES['tgmx_decoder_forward'] = (c_int32, [ctypes.POINTER(DecoderFwd), _P])
 
+AN_BAD_ID, AN_TABLE_FULL, AN_BAD_TIME = 1, 2, 4  # TGMX_AN_*
+
+
+class AnBatch(ctypes.Structure):
+    """tgmx_an_batch_t (include/tgm_amd.h)."""
+
+    _fields_ = [
+        ('src', c_void_p), ('dst', c_void_p), ('E', c_int64), ('src_is64', c_int32), ('dst_is64', c_int32),
+        ('edge_time', c_void_p), ('Et', c_int64), ('edge_time_is64', c_int32), ('reserved0_', c_int32),
+        ('nids', c_void_p), ('Nn', c_int64), ('nids_is64', c_int32), ('reserved1_', c_int32),
+        ('node_time', c_void_p), ('Nt', c_int64), ('node_time_is64', c_int32), ('reserved2_', c_int32),
+    ]  # fmt: skip
+
+
+class NodeAnalytics(ctypes.Structure):
+    """tgmx_node_analytics_t (include/tgm_amd.h)."""
+
+    _fields_ = [
+        ('slot_of', c_void_p), ('num_nodes', c_int64), ('T', c_int64),
+        ('first_seen', c_void_p), ('last_seen', c_void_p), ('appearances', c_void_p),
+        ('edges', c_void_p), ('edges_cap', c_int64), ('nbrs', c_void_p), ('nbrs_cap', c_int64),
+        ('times', c_void_p), ('times_cap', c_int64), ('apps', c_void_p), ('apps_cap', c_int64),
+        ('counters', c_void_p),
+        ('degree', c_void_p), ('new_nbrs', c_void_p), ('present', c_void_p), ('stamp', c_void_p), ('scalars', c_void_p),
+    ]  # fmt: skip
+
+
+SIGNATURES['tgmx_batch_analytics_workspace_bytes'] = (c_size_t, [c_int64, c_int64, c_int64, c_int64])
+SIGNATURES['tgmx_batch_analytics'] = (c_int32, [ctypes.POINTER(AnBatch), c_int32, _P, _P, c_size_t, _P])
+SIGNATURES['tgmx_seen_nodes_step'] = (c_int32, [_P, c_int64, _P, c_int32, _P, c_int32, c_int64, _P, c_int32, c_int64, _P, _P, _P, _P])
+SIGNATURES['tgmx_node_analytics_step'] = (c_int32, [ctypes.POINTER(NodeAnalytics), ctypes.POINTER(AnBatch), c_int64, _P, _P])
+SIGNATURES['tgmx_node_analytics_rehash'] = (c_int32, [_P, c_int64, _P, c_int64, _P, _P])
+
 _lib: Optional[ctypes.CDLL] = None
 
 

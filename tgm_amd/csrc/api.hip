@@ -45,6 +45,8 @@ extern "C" size_t tgmx_abi_sizeof(int32_t which) {
     case 24: return sizeof(tgmx_gclstm_fwd_t);  // (23 stays 0: an existing test pins it as the first unused index)
     case 26: return sizeof(tgmx_roland_fwd_t);  // (25 stays 0 for the same reason)
     case 27: return sizeof(tgmx_decoder_fwd_t);
+    case 28: return sizeof(tgmx_an_batch_t);
+    case 29: return sizeof(tgmx_node_analytics_t);
     default: return 0;
   }
 }

@@ -36,6 +36,26 @@ __device__ __forceinline__ long long eb_claim(EbSlot* __restrict__ table, long l
   }
   return -1;
 }
+// eb_claim that also tells whether THIS call took the slot (*fresh: the compare-and-swap returned the empty key): of all the claims of one
+// key, in one launch or over many, exactly one is fresh
+__device__ __forceinline__ long long eb_claim_fresh(EbSlot* __restrict__ table, long long cap, unsigned long long key, bool* fresh) {
+  unsigned long long* keys = reinterpret_cast<unsigned long long*>(table);
+  long long i = (long long)(eb_hash(key) & (unsigned long long)(cap - 1));
+  *fresh = false;
+  for (long long p = 0; p < cap; ++p) {
+    unsigned long long cur = __hip_atomic_load(&keys[2 * i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (cur == kEbEmpty) {
+      cur = atomicCAS(&keys[2 * i], kEbEmpty, key);
+      if (cur == kEbEmpty) {
+        *fresh = true;
+        return i;
+      }
+    }
+    if (cur == key) return i;
+    i = (i + 1) & (cap - 1);
+  }
+  return -1;
+}
 // slot of `key`, or -1 (absent: an empty slot ends the probe)
 __device__ __forceinline__ long long eb_find(const EbSlot* __restrict__ table, long long cap, unsigned long long key, long long* val_out) {
   long long i = (long long)(eb_hash(key) & (unsigned long long)(cap - 1));

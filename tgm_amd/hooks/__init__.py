@@ -8,14 +8,22 @@ from .uniform import NeighborSamplerHook
 from .time_gap import TimeGapNeighborHook
 from .registry import hook, list_hooks
 from . import neighbors  # noqa: E402,F401  (the reference's import path: tgm.hooks.neighbors.recency)
+from .analytics import BatchAnalyticsHook, NodeAnalyticsHook
+from .device import DeviceTransferHook, PinMemoryHook
+from .node_tracks import EdgeEventsSeenNodesTrackHook
 
 __all__ = [
     'BaseDGHook',
+    'BatchAnalyticsHook',
     'DGHook',
     'DeduplicationHook',
+    'DeviceTransferHook',
+    'EdgeEventsSeenNodesTrackHook',
     'HistoricalNegativeEdgeSamplerHook',
     'HookManager',
     'NeighborSamplerHook',
+    'NodeAnalyticsHook',
+    'PinMemoryHook',
     'RandomNegativeEdgeSamplerHook',
     'RecencyNeighborHook',
     'SampledEdgeListHook',
