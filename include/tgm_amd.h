@@ -57,7 +57,7 @@ int tgmx_version(void);
  * 0 tgmx_adj_t, 1 tgmx_recency_step_t, 2 tgmx_tgat_layer_t, 3 tgmx_tgat_model_t, 4 tgmx_tgat_hop_t, 5 tgmx_tgat_layout_t,
  * 6 tgmx_pipeline_t, 7 tgmx_pipeline_out_t, 8 tgmx_dropout_t, 9 tgmx_tgn_memory_fwd_t, 10 tgmx_tconv_fwd_t, 11 tgmx_pipeline_post_t,
  * 12 tgmx_tgn_step_t, ..., 22 tgmx_ctan_fwd_t, 24 tgmx_gclstm_fwd_t, 26 tgmx_roland_fwd_t, 27 tgmx_decoder_fwd_t (23 and 25 are reserved and answer 0: tests/test_ctan_cpu.py and
- * tests/test_gclstm_cpu.py pin them) */
+ * tests/test_gclstm_cpu.py pin them), 28 tgmx_an_batch_t, 29 tgmx_node_analytics_t, 30 tgmx_decoder_train_t */
 size_t tgmx_abi_sizeof(int32_t which);
 const char* tgmx_last_error(void);
 
@@ -1556,6 +1556,64 @@ typedef struct tgmx_decoder_fwd {
   float* P; float* h[2]; float* pooled; float* pool_ws; size_t pool_ws_floats; int32_t* bad; float* out;
 } tgmx_decoder_fwd_t;
 int tgmx_decoder_forward(const tgmx_decoder_fwd_t* args, tgmx_stream_t stream);
+
+/* ---- decoder training (csrc/decoder_bwd.hip): the saving forward and the backward of the ROWS, PAIR and flat TABLE heads, ONE call each.
+ * No float atomics anywhere: every sum has one fixed order, two runs give the same bits. ---- */
+
+/* The last layer's backward, out_dim <= 16 (the tgmx_decoder_tail case): dout [R, out_dim], x [R, K] the layer's saved input, W [out_dim, K]:
+ *   dx[r, j] = (relu == 0 || x[r, j] > 0) * sum_o dout[r, o] W[o, j]   (ascending o; the mask reads the saved activation, x == 0 gives 0)
+ *   dW[o, j] = sum_r dout[r, o] x[r, j],  db[o] = sum_r dout[r, o]
+ * A workgroup owns a block of rows (their number follows R: 4 up to R = 1024, at most 256 blocks) and 64 columns; its four waves take the
+ * block's rows in turn, their partial sums add in wave order, and a second launch adds the blocks' partials in ascending block order.
+ * dx, dW, db may each be NULL (not computed).  workspace: tgmx_decoder_tail_bwd_workspace_floats() floats (0 when dW and db are NULL).
+ * R = 0 writes nothing.  TGMX_E_UNSUPPORTED for out_dim > 16. */
+size_t tgmx_decoder_tail_bwd_workspace_floats(int64_t R, int32_t K, int32_t out_dim);
+int tgmx_decoder_tail_bwd(const float* dout, int64_t lddout, const float* x, int64_t ldx, int64_t R, int32_t K, const float* W, int32_t out_dim,
+                          int32_t relu, float* dx, int64_t lddx, float* dW, float* db, float* workspace, size_t workspace_floats,
+                          tgmx_stream_t stream);
+
+/* The table form's scatter: dP [NP, 2H] (contiguous) from dh [R, H] and the pairs (ia[r], ib[r]):
+ *   dP[n, :H] = sum_{r: ia[r] = n} dh[r],  dP[n, H:] = sum_{r: ib[r] = n} dh[r]
+ * read back through an inverted index: keys ((n or NP + n) << cb | r), one rocPRIM radix sort, row pointers by binary search (edge_csr.h),
+ * then spmm.h's gather (a row's pairs add in ascending r; rows of more than 64 / 2048 pairs take its fixed-order splits).  Every row of dP
+ * is written, rows without a pair as zeros.  A pair with an index outside [0, NP) is dropped from both halves and never dereferenced.
+ * ids int64 where idx64 is set, else int32.  2R < 2^31, 2NP < 2^31. */
+size_t tgmx_decoder_scatter_workspace_bytes(int64_t R, int64_t NP, int32_t H);
+int tgmx_decoder_scatter(const float* dh, int64_t lddh, int64_t R, int32_t H, const void* ia, const void* ib, int32_t idx64, int64_t NP,
+                         float* dP, void* workspace, size_t workspace_bytes, tgmx_stream_t stream);
+
+/* For every job: dst[r, :C] = src[r, :C] (src NULL: dst as it is) where both of pair r's indices lie in [0, NP), zeros elsewhere.  ONE
+ * launch: the backward's first in the table form, over the upstream gradient and every saved activation (a dropped pair's rows are NaN). */
+typedef struct tgmx_drop_job {
+  const float* src; float* dst; int64_t lds, ldd; int32_t C, reserved_;
+} tgmx_drop_job_t;
+int tgmx_decoder_drop_rows(const void* ia, const void* ib, int32_t idx64, int64_t NP, int64_t R, const tgmx_drop_job_t* jobs, int32_t n_jobs,
+                           tgmx_stream_t stream); /* n_jobs <= TGMX_DECODER_MAX_LAYERS + 1 */
+
+/* The training argument block (tgmx_abi_sizeof(30)).  fwd: the head as tgmx_decoder_forward takes it, with these differences: pool is
+ * NONE; TABLE takes flat pairs only (M = -1) and reads the merge weights WHERE THE PARAMETERS ARE, as PAIR does (wa, wb [H, ld >= D],
+ * two GEMMs into the halves of P; nothing stacked per step); fwd.h is not used.  The forward keeps what the backward reads in buffers of
+ * THIS call: act[0] [R, H] the merge stage's output (PAIR, TABLE; the table form never fuses the last layer into tgmx_decoder_score),
+ * act[l] [R, layers[l].in] the input of layer l >= 1.  ROWS reads a1 as layer 0's input (act[0] unused).
+ * Backward: dout [R, out_dim] with leading dimension lddout.  Every gradient pointer may be NULL: that gradient's launch is not issued.
+ * d_a1 [R, D] (TABLE: [n1, D]) and d_a2 [R, D] contiguous; d_wa / d_wb [H, D] with their leading dimensions (ConcatMerge: the column halves
+ * of the first Linear's gradient, ld 2D); d_mbias, d_mbias2 [H] both receive the merge bias's gradient; d_w[l] / d_b[l] as layers[l].
+ * Order: [TABLE: tgmx_decoder_drop_rows] -> the weights transposed (one tgmx_pack2d) -> the last layer (tgmx_decoder_tail_bwd, or the
+ * generic route) -> the hidden layers from the back (dW: tgmx_sgemm_tn, db: tgmx_colsum, dX: tgmx_sgemm_nt on the transposed weight,
+ * tgmx_relu_mask) -> the merge stage (PAIR: two tgmx_sgemm_tn, tgmx_colsum, two tgmx_sgemm_nt; TABLE: tgmx_decoder_scatter, then the same
+ * over the NP rows of dP, one tgmx_sgemm_nt with K = 2H for d_a1).  In the table form the saved activations of a dropped pair are zeroed
+ * in place.  workspace: tgmx_decoder_backward_workspace_bytes(). */
+typedef struct tgmx_decoder_train {
+  tgmx_decoder_fwd_t fwd;
+  float* act[TGMX_DECODER_MAX_LAYERS];
+  const float* dout; int64_t lddout;
+  float* d_a1; float* d_a2; float* d_wa; int64_t ld_dwa; float* d_wb; int64_t ld_dwb; float* d_mbias; float* d_mbias2;
+  float* d_w[TGMX_DECODER_MAX_LAYERS]; float* d_b[TGMX_DECODER_MAX_LAYERS];
+  void* workspace; size_t workspace_bytes;
+} tgmx_decoder_train_t;
+int tgmx_decoder_forward_save(const tgmx_decoder_train_t* args, tgmx_stream_t stream);
+size_t tgmx_decoder_backward_workspace_bytes(const tgmx_decoder_train_t* args);
+int tgmx_decoder_backward(const tgmx_decoder_train_t* args, tgmx_stream_t stream);
 
 /* ---- BatchAnalyticsHook, EdgeEventsSeenNodesTrackHook, NodeAnalyticsHook (the reference's tgm/hooks/analytics/, tgm/hooks/node_tracks.py):
  * distinct counts within a batch, membership in sets that grow over the stream, an ordered compaction (csrc/analytics.hip) ---- */

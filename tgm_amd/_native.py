@@ -648,6 +648,35 @@ SIGNATURES['tgmx_pool_rows'] = (c_int32, [_P, c_int64, c_int64, c_int32, c_int32
 SIGNATURES['tgmx_decoder_row_mlp'] = (c_int32, [_P, ctypes.POINTER(DecoderLayer), c_int32, _P, _P])
 SIGNATURES['tgmx_decoder_forward'] = (c_int32, [ctypes.POINTER(DecoderFwd), _P])
 
+
+class DropJob(ctypes.Structure):
+    """tgmx_drop_job_t (include/tgm_amd.h)."""
+
+    _fields_ = [('src', c_void_p), ('dst', c_void_p), ('lds', c_int64), ('ldd', c_int64), ('C', c_int32), ('reserved_', c_int32)]
+
+
+class DecoderTrain(ctypes.Structure):
+    """tgmx_decoder_train_t (include/tgm_amd.h)."""
+
+    _fields_ = [
+        ('fwd', DecoderFwd), ('act', c_void_p * DECODER_MAX_LAYERS),
+        ('dout', c_void_p), ('lddout', c_int64),
+        ('d_a1', c_void_p), ('d_a2', c_void_p), ('d_wa', c_void_p), ('ld_dwa', c_int64), ('d_wb', c_void_p), ('ld_dwb', c_int64),
+        ('d_mbias', c_void_p), ('d_mbias2', c_void_p),
+        ('d_w', c_void_p * DECODER_MAX_LAYERS), ('d_b', c_void_p * DECODER_MAX_LAYERS),
+        ('workspace', c_void_p), ('workspace_bytes', c_size_t),
+    ]  # fmt: skip
+
+
+SIGNATURES['tgmx_decoder_tail_bwd_workspace_floats'] = (c_size_t, [c_int64, c_int32, c_int32])
+SIGNATURES['tgmx_decoder_tail_bwd'] = (c_int32, [_P, c_int64, _P, c_int64, c_int64, c_int32, _P, c_int32, c_int32, _P, c_int64, _P, _P, _P, c_size_t, _P])
+SIGNATURES['tgmx_decoder_scatter_workspace_bytes'] = (c_size_t, [c_int64, c_int64, c_int32])
+SIGNATURES['tgmx_decoder_scatter'] = (c_int32, [_P, c_int64, c_int64, c_int32, _P, _P, c_int32, c_int64, _P, _P, c_size_t, _P])
+SIGNATURES['tgmx_decoder_drop_rows'] = (c_int32, [_P, _P, c_int32, c_int64, c_int64, ctypes.POINTER(DropJob), c_int32, _P])
+SIGNATURES['tgmx_decoder_forward_save'] = (c_int32, [ctypes.POINTER(DecoderTrain), _P])
+SIGNATURES['tgmx_decoder_backward_workspace_bytes'] = (c_size_t, [ctypes.POINTER(DecoderTrain)])
+SIGNATURES['tgmx_decoder_backward'] = (c_int32, [ctypes.POINTER(DecoderTrain), _P])
+
 AN_BAD_ID, AN_TABLE_FULL, AN_BAD_TIME = 1, 2, 4  # TGMX_AN_*
 
 

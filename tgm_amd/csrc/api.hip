@@ -47,6 +47,7 @@ extern "C" size_t tgmx_abi_sizeof(int32_t which) {
     case 27: return sizeof(tgmx_decoder_fwd_t);
     case 28: return sizeof(tgmx_an_batch_t);
     case 29: return sizeof(tgmx_node_analytics_t);
+    case 30: return sizeof(tgmx_decoder_train_t);
     default: return 0;
   }
 }

@@ -12,7 +12,14 @@
 //   template <bool VEC> __device__ void apply(long long i, int c0, int C, int lane, float o[kSpmmChPerLane]) const
 // which turns a row's sums of one channel pass into what is stored (o holds diag[i] t[i] + the gathered sum on entry).  It runs wherever a
 // row finishes: the short row, wave 0 of a long row, the join kernel.
+//
+// An epilogue that declares `static constexpr bool kGatherOnly = true` makes the propagation a plain row gather (decoder_bwd.hip: the
+// scatter of the pair gradients, read back through the inverted index): every value is 1 (vals is not read: acc += x), there is no
+// diagonal term (diag and t[i] are not read: out has other rows than t), apply() is not called, and row i is stored at
+//   __device__ float* row(float* out, long long ldo, long long i) const
 #pragma once
+#include <type_traits>
+
 #include "common.h"
 
 namespace tgmx {
@@ -54,8 +61,13 @@ __device__ __forceinline__ void spmm_store(float* __restrict__ row, int c0, int 
   }
 }
 
-// acc += sum over the entries [lo, hi) in ascending order, four source rows requested ahead
-template <bool VEC>
+template <typename Epi, typename = void>
+struct spmm_gather_only : std::false_type {};
+template <typename Epi>
+struct spmm_gather_only<Epi, std::void_t<decltype(Epi::kGatherOnly)>> : std::bool_constant<Epi::kGatherOnly> {};
+
+// acc += sum over the entries [lo, hi) in ascending order, four source rows requested ahead (UNIT: every value is 1)
+template <bool VEC, bool UNIT = false>
 __device__ __forceinline__ void spmm_accumulate(const int32_t* __restrict__ cols, const float* __restrict__ vals, int lo, int hi,
                                                 const float* __restrict__ t, long long ldt, int c0, int C, int lane, float acc[kSpmmChPerLane]) {
   int j = lo;
@@ -63,20 +75,20 @@ __device__ __forceinline__ void spmm_accumulate(const int32_t* __restrict__ cols
     float x[4][kSpmmChPerLane], v[4];
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
-      v[u] = vals[j + u];
+      v[u] = UNIT ? 1.f : vals[j + u];
       spmm_load<VEC>(t + (long long)cols[j + u] * ldt, c0, C, lane, x[u]);
     }
 #pragma unroll
     for (int u = 0; u < 4; ++u)
 #pragma unroll
-      for (int q = 0; q < kSpmmChPerLane; ++q) acc[q] = __fmaf_rn(v[u], x[u][q], acc[q]);
+      for (int q = 0; q < kSpmmChPerLane; ++q) acc[q] = UNIT ? __fadd_rn(acc[q], x[u][q]) : __fmaf_rn(v[u], x[u][q], acc[q]);
   }
   for (; j < hi; ++j) {
     float x[kSpmmChPerLane];
-    const float v = vals[j];
+    const float v = UNIT ? 1.f : vals[j];
     spmm_load<VEC>(t + (long long)cols[j] * ldt, c0, C, lane, x);
 #pragma unroll
-    for (int q = 0; q < kSpmmChPerLane; ++q) acc[q] = __fmaf_rn(v, x[q], acc[q]);
+    for (int q = 0; q < kSpmmChPerLane; ++q) acc[q] = UNIT ? __fadd_rn(acc[q], x[q]) : __fmaf_rn(v, x[q], acc[q]);
   }
 }
 
@@ -100,13 +112,17 @@ struct SpmmArgs {
 // out row i of one channel pass from the gathered sum acc
 template <bool VEC, typename Epi>
 __device__ __forceinline__ void spmm_finish(const SpmmArgs<Epi>& a, long long i, int c0, int lane, float acc[kSpmmChPerLane]) {
-  float self[kSpmmChPerLane], o[kSpmmChPerLane];
-  spmm_load<VEC>(a.t + i * a.ldt, c0, a.C, lane, self);
-  const float d = a.diag[i];
+  if constexpr (spmm_gather_only<Epi>::value) {
+    spmm_store<VEC>(a.epi.row(a.out, a.ldo, i), c0, a.C, lane, acc);
+  } else {
+    float self[kSpmmChPerLane], o[kSpmmChPerLane];
+    spmm_load<VEC>(a.t + i * a.ldt, c0, a.C, lane, self);
+    const float d = a.diag[i];
 #pragma unroll
-  for (int q = 0; q < kSpmmChPerLane; ++q) o[q] = __fmaf_rn(d, self[q], acc[q]);
-  a.epi.template apply<VEC>(i, c0, a.C, lane, o);
-  spmm_store<VEC>(a.out + i * a.ldo, c0, a.C, lane, o);
+    for (int q = 0; q < kSpmmChPerLane; ++q) o[q] = __fmaf_rn(d, self[q], acc[q]);
+    a.epi.template apply<VEC>(i, c0, a.C, lane, o);
+    spmm_store<VEC>(a.out + i * a.ldo, c0, a.C, lane, o);
+  }
 }
 
 // the sum over the entries [lo, hi) by the four waves of a workgroup, a contiguous quarter each, the partial sums added in wave order: the
@@ -118,7 +134,7 @@ __device__ __forceinline__ void spmm_block_sum(const SpmmArgs<Epi>& a, int lo, i
   const int mylo = min(lo + wave * piece, hi), myhi = min(mylo + piece, hi);
 #pragma unroll
   for (int q = 0; q < kSpmmChPerLane; ++q) acc[q] = 0.f;
-  spmm_accumulate<VEC>(a.cols, a.vals, mylo, myhi, a.t, a.ldt, c0, a.C, lane, acc);
+  spmm_accumulate<VEC, spmm_gather_only<Epi>::value>(a.cols, a.vals, mylo, myhi, a.t, a.ldt, c0, a.C, lane, acc);
 #pragma unroll
   for (int q = 0; q < kSpmmChPerLane; ++q) part[wave][q][lane] = acc[q];
   __syncthreads();
@@ -147,7 +163,7 @@ __global__ __launch_bounds__(kSpmmThreads) void spmm_propagate_kernel(SpmmArgs<E
       if (hi - lo <= kSpmmLongRow) {
         for (int c0 = 0; c0 < a.C; c0 += kWave * kSpmmChPerLane) {
           float acc[kSpmmChPerLane] = {0.f, 0.f, 0.f, 0.f};
-          spmm_accumulate<VEC>(a.cols, a.vals, lo, hi, a.t, a.ldt, c0, a.C, lane, acc);
+          spmm_accumulate<VEC, spmm_gather_only<Epi>::value>(a.cols, a.vals, lo, hi, a.t, a.ldt, c0, a.C, lane, acc);
           spmm_finish<VEC>(a, i, c0, lane, acc);
         }
       }

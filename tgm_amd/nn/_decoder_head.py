@@ -12,6 +12,7 @@ import torch.nn as nn
 from torch import Tensor
 
 from .. import _native
+from . import _decoder_train
 from ._fwd_plumbing import Unsupported, cached_block, carve_scratch, check_supported, needs_torch
 from ._paramver import TransientCaches
 from .aggregation import ConcatMerge, LearnableSumMerge
@@ -64,6 +65,22 @@ class DecoderHead(_Skipped, TransientCaches):
             return False
         lins = linears(self.model)
         return lins is not None and all(_plain(p, x.device) for p in self.parameters())
+
+    def _trainable(self, *inputs: Tensor) -> bool:
+        """The native training path applies (``_decoder_train.py``): autograd has something to track and the call is otherwise inside the
+        native envelope -- on the device, float32 everywhere and no autocast, contiguous parameters, the constructor's layer chain, at
+        least one row.  ``TGMX_DECODER_BWD=torch`` keeps the composed path."""
+        x = inputs[0]
+        if x.device.type != 'cuda' or any(t.device != x.device or t.dtype != torch.float32 for t in inputs) or x.shape[0] == 0:
+            return False
+        if not needs_torch(self, 0.0, *inputs) or torch.is_autocast_enabled() or _decoder_train.mode() == 'torch':
+            return False
+        lins = linears(self.model)
+        return lins is not None and len(lins) - (self._merge_kind() == 'concat') <= _native.DECODER_MAX_LAYERS and all(
+            _plain(p, x.device) for p in self.parameters())  # fmt: skip
+
+    def _train(self, form: str, idx, shape: tuple, *inputs: Tensor) -> Tensor:
+        return _decoder_train.apply(self, linears(self.model), self._merge_kind(), form, idx, shape, *inputs)
 
     def _merge_kind(self) -> Optional[str]:
         """'concat' / 'sum' when the merge is one of the two shipped and fits the model; None: the merge runs as torch ops."""

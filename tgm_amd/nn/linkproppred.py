@@ -2,9 +2,11 @@
 
 ``forward(z_src, z_dst)`` is the reference's.  Without gradients on the device it is one native call (``tgmx_decoder_forward``, pair
 form): the first layer reads the two operands where they are -- no ``[R, 2D]`` concatenation -- and a last layer of at most 16 outputs is
-a row dot.  With gradients to track, on the host, or outside the native envelope (parameters that are not contiguous float32, a model that
-is not the Linear / ReLU chain the constructor builds) the same arithmetic runs as torch ops; a merge other than ``ConcatMerge`` /
-``LearnableSumMerge`` runs in torch and the MLP after it natively.
+a row dot.  With gradients to track it is the same head as a ``torch.autograd.Function`` (``_decoder_train.py``): one native call that
+keeps its activations per call, one native call backward; ``score_pairs`` in the table form likewise, with the gradient of the table.
+On the host, or outside the native envelope (parameters that are not contiguous float32, a model that is not the Linear / ReLU chain
+the constructor builds, autocast) the same arithmetic runs as torch ops; a merge other than ``ConcatMerge`` / ``LearnableSumMerge`` runs in
+torch and the MLP after it natively (with gradients: all of it in torch).
 
 New here, for the evaluation loop of the examples (for every positive edge: index ``z`` twice, concatenate, run the MLP on ``1 + M`` rows):
 
@@ -30,7 +32,7 @@ from torch import Tensor
 
 from .. import _native
 from ._decoder_head import DecoderHead, build_mlp, linears
-from ._fwd_plumbing import i32
+from ._fwd_plumbing import i32, needs_torch
 from .aggregation import Aggregator, ConcatMerge, require_aggregator
 
 _INT = (torch.int32, torch.int64)
@@ -57,7 +59,10 @@ class LinkPredictor(DecoderHead, nn.Module):
 
     # ---- the reference's call ---------------------------------------------------------------------------------------------------------------
     def forward(self, z_src: Tensor, z_dst: Tensor) -> Tensor:
-        if not (z_src.dim() == 2 and z_dst.dim() == 2 and z_src.shape == z_dst.shape and self._ready(z_src, z_dst)):
+        shaped = z_src.dim() == 2 and z_dst.dim() == 2 and z_src.shape == z_dst.shape
+        if shaped and self._train_ready(z_src, z_dst):  # gradients to track: the saving forward, one native call back
+            return self._train('pair', None, (-1,), z_src.contiguous(), z_dst.contiguous())
+        if not (shaped and self._ready(z_src, z_dst)):
             return self.model(self.merge(z_src, z_dst)).view(-1)
         if self._merge_kind() is None:
             return self._mlp_rows(self.merge(z_src, z_dst).contiguous()).view(-1)
@@ -79,6 +84,10 @@ class LinkPredictor(DecoderHead, nn.Module):
             return len(linears(self.model)) <= _native.DECODER_MAX_LAYERS
         return zs[0].shape[1] == self.merge.dim
 
+    def _train_ready(self, *zs: Tensor) -> bool:
+        """The native training path applies: :meth:`_ready`'s envelope with something for autograd to track, one of the two shipped merges."""
+        return self._trainable(*zs) and self._merge_kind() is not None and zs[0].shape[1] == self.merge.dim
+
     def _form(self, n_table: int, R: int) -> str:
         H = self.merge.dim if self._merge_kind() == 'sum' else self.model[0].out_features
         if H > _native.DECODER_MAX_H:  # the score kernel keeps a half row in LDS
@@ -94,6 +103,10 @@ class LinkPredictor(DecoderHead, nn.Module):
         indices (int32 or int64, one per pair) point into it."""
         if src_idx.numel() != dst_idx.numel():
             raise ValueError(f'mismatch shape: src_idx: {src_idx.numel()}, dst_idx: {dst_idx.numel()}')
+        if (z.dim() == 2 and src_idx.dtype in _INT and dst_idx.dtype in _INT and src_idx.device == z.device and dst_idx.device == z.device
+                and src_idx.numel() > 0 and self._train_ready(z) and self._form(z.shape[0], src_idx.numel()) == 'table'):  # fmt: skip
+            # gradients to track and the table form: one GEMM over the table forward, its gradient gathered per table row backward
+            return self._train('table', tuple(_ids(src_idx.reshape(-1), dst_idx.reshape(-1))), (-1,), z.contiguous())
         if not (z.dim() == 2 and src_idx.dtype in _INT and dst_idx.dtype in _INT and self._ready(z) and self._merge_kind() is not None
                 and src_idx.device == z.device and dst_idx.device == z.device):  # fmt: skip
             return self(z[src_idx.reshape(-1).long()], z[dst_idx.reshape(-1).long()])
@@ -137,7 +150,8 @@ class LinkPredictor(DecoderHead, nn.Module):
             else:
                 ia = src_idx.long().repeat_interleave(M + 1)
                 ib = torch.cat((dst_idx.long().unsqueeze(1), negatives.long()), dim=1).reshape(-1)
-            flat = self(z[ia], z[ib])
+            # (with gradients to track this method stays on the composed path: only forward / score_pairs have a native backward)
+            flat = self.model(self.merge(z[ia], z[ib])).view(-1) if needs_torch(self, 0.0, z) else self(z[ia], z[ib])
         else:
             off = None
             if ragged:
