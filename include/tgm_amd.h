@@ -57,7 +57,8 @@ int tgmx_version(void);
  * 0 tgmx_adj_t, 1 tgmx_recency_step_t, 2 tgmx_tgat_layer_t, 3 tgmx_tgat_model_t, 4 tgmx_tgat_hop_t, 5 tgmx_tgat_layout_t,
  * 6 tgmx_pipeline_t, 7 tgmx_pipeline_out_t, 8 tgmx_dropout_t, 9 tgmx_tgn_memory_fwd_t, 10 tgmx_tconv_fwd_t, 11 tgmx_pipeline_post_t,
  * 12 tgmx_tgn_step_t, ..., 22 tgmx_ctan_fwd_t, 24 tgmx_gclstm_fwd_t, 26 tgmx_roland_fwd_t, 27 tgmx_decoder_fwd_t (23 and 25 are reserved and answer 0: tests/test_ctan_cpu.py and
- * tests/test_gclstm_cpu.py pin them), 28 tgmx_an_batch_t, 29 tgmx_node_analytics_t, 30 tgmx_decoder_train_t */
+ * tests/test_gclstm_cpu.py pin them), 28 tgmx_an_batch_t, 29 tgmx_node_analytics_t, 30 tgmx_decoder_train_t, 32 tgmx_gclstm_bwd_t (31 is
+ * reserved the same way: tests/test_decoder_train_cpu.py) */
 size_t tgmx_abi_sizeof(int32_t which);
 const char* tgmx_last_error(void);
 
@@ -1390,6 +1391,56 @@ typedef struct tgmx_gclstm_fwd {
   float* H_out; float* C_out;                          /* [N, C] each */
 } tgmx_gclstm_fwd_t;
 int tgmx_gclstm_forward(const tgmx_gclstm_fwd_t* args, tgmx_stream_t stream);
+
+/* ---- GCLSTM / ChebConv training (csrc/cheb_bwd.hip; composed by tgm_amd/nn/_gclstm_train.py, TGMX_GCLSTM_BWD = py | torch picks the
+ * per-launch or the composed torch path instead of the one call) ---- */
+
+/* The gate backward.  pre [N, 4C] (the forward's pre-activations, gates i, f, c, o), Cprev [N, C]; dH_out / dC_out [N, C] with leading
+ * dimensions lddh / lddc, either may be NULL and then counts as zero.  I, F, T, O, C', tanh(C') are recomputed with the forward's own
+ * expressions; dCn = dC' + dH' O (1 - tanh^2 C'); dpre [N, 4C] = [dCn T I(1-I) | dCn Cprev F(1-F) | dCn I (1-T^2) | dH' tanh(C') O(1-O)];
+ * dCprev [N, C] = dCn F (may be NULL). */
+int tgmx_gclstm_gate_backward(const float* pre, const float* Cprev, int64_t N, int32_t C, const float* dH_out, int64_t lddh,
+                              const float* dC_out, int64_t lddc, float* dpre, float* dCprev, tgmx_stream_t stream);
+
+/* tgmx_cheb_laplacian's transpose: the same L_hat as rows BY SOURCE, cols = the destinations ascending within a row, duplicates in edge
+ * order.  Same arguments and workspace (tgmx_cheb_workspace_bytes); the degrees, the entry arithmetic and diag are the forward builder's
+ * own code, so the multiset of (row, col, value) equals the forward's with row and col swapped, bit for bit, and diag is identical. */
+int tgmx_cheb_laplacian_t(const void* src, const void* dst, int32_t idx64, const float* w, int64_t E, int64_t N, int32_t normalization,
+                          float lambda_max, const float* lambda_ptr, int32_t* indptr, int32_t* cols, float* vals, float* diag,
+                          void* workspace, size_t workspace_bytes, int32_t* skipped, tgmx_stream_t stream);
+
+/* tgmx_cheb_propagate with two addends: out = alpha (M t) + beta prev + gamma prev2 (prev / prev2 are not read when their factor is 0).
+ * prev or prev2 may be out itself (a lane reads the elements it writes); t must not overlap out.  Same three routes, lanes and scratch. */
+int tgmx_cheb_propagate2(const int32_t* indptr, const int32_t* cols, const float* vals, const float* diag, int64_t N, int32_t C,
+                         const float* t, int64_t ldt, const float* prev, int64_t ldp, const float* prev2, int64_t ldp2, float alpha,
+                         float beta, float gamma, float* out, int64_t ldo, int64_t nnz, float* scratch, size_t scratch_floats,
+                         tgmx_stream_t stream);
+
+/* The reverse of the Chebyshev recurrence in Clenshaw form over M = L_hat^T (tgmx_cheb_laplacian_t), K >= 2: g [N, ldg >= K C] holds the
+ * gradient at Tx_k in its columns [k C, (k + 1) C) and is overwritten (b_k = g_k + 2 M b_{k+1} - b_{k+2}, k = K - 2 .. 1);
+ * out [N, ldo] = g_0 + M b_1 - b_2.  K - 1 tgmx_cheb_propagate2 launches. */
+int tgmx_cheb_clenshaw(const int32_t* indptr, const int32_t* cols, const float* vals, const float* diag, int64_t N, int32_t C, int32_t K,
+                       float* g, int64_t ldg, float* out, int64_t ldo, int64_t nnz, float* scratch, size_t scratch_floats,
+                       tgmx_stream_t stream);
+
+/* The cell's backward as ONE call (tgmx_abi_sizeof(32)).  op / ldop / pre / Cprev: what tgmx_gclstm_forward wrote and read (buffers of
+ * that call).  Order: the gate backward -> d_W = x^T dpre_g (one batched tgmx_sgemm_tn, [4, in, C]) -> d_lins = dpre^T Tx_k (one batched
+ * tgmx_sgemm_tn, [K, 4, C, C]: [k][g] is conv_g.lins.k.weight's) -> d_b = the column sums of dpre (one tgmx_colsum; d_conv_bias gets a
+ * copy) -> d_x = dpre WT[:in]^T, the gradient at the basis = dpre WT[in:]^T (tgmx_sgemm_nt; WT [in + K C, ldwt >= 4C] is the transposed
+ * stacked weight) -> K > 1: tgmx_cheb_laplacian_t (skipped edges are not counted again) and tgmx_cheb_clenshaw into d_H.  Every gradient
+ * pointer may be NULL: its launches are not issued; the graph is read only for d_H with K > 1.  edge_w and lambda_max get no gradient. */
+typedef struct tgmx_gclstm_bwd {
+  int64_t N; int32_t in_ch, C, K, normalization;
+  const float* op; int64_t ldop; const float* pre; const float* Cprev;
+  const float* dH_out; int64_t lddh; const float* dC_out; int64_t lddc;   /* [N, C] each, or NULL */
+  const float* WT; int64_t ldwt;
+  const void* src; const void* dst; const float* edge_w; int64_t E; int32_t idx64; float lambda_max; const float* lambda_ptr;
+  float* d_W; float* d_lins; float* d_b; float* d_conv_bias;              /* [4, in, C], [K, 4, C, C], [4C], [4C] */
+  float* d_x; float* d_H; float* d_Cprev;                                 /* [N, in], [N, C], [N, C], contiguous */
+  void* workspace; size_t workspace_bytes;                                /* tgmx_gclstm_backward_workspace_bytes(args) */
+} tgmx_gclstm_bwd_t;
+size_t tgmx_gclstm_backward_workspace_bytes(const tgmx_gclstm_bwd_t* args);
+int tgmx_gclstm_backward(const tgmx_gclstm_bwd_t* args, tgmx_stream_t stream);
 
 /* ---- GCNConv above the dense cap / ROLAND (the reference's tgm/nn/encoder/roland.py; GCNConv from its published PyG definition): GCN's
  * normalised adjacency as a CSR by destination, the gather SpMM over it with a fused epilogue, and ROLAND's forward as one call ---- */

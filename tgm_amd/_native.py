@@ -566,6 +566,31 @@ SIGNATURES['tgmx_cheb_propagate_scratch_floats'] = (c_size_t, [c_int64, c_int32]
 SIGNATURES['tgmx_cheb_propagate'] = (c_int32, [_P, _P, _P, _P, c_int64, c_int32, _P, c_int64, _P, c_int64, ctypes.c_float, ctypes.c_float, _P, c_int64, c_int64, _P, c_size_t, _P])
 SIGNATURES['tgmx_gclstm_forward'] = (c_int32, [ctypes.POINTER(GclstmFwd), _P])
 
+
+class GclstmBwd(ctypes.Structure):
+    """tgmx_gclstm_bwd_t (include/tgm_amd.h)."""
+
+    _fields_ = [
+        ('N', c_int64), ('in_ch', c_int32), ('C', c_int32), ('K', c_int32), ('normalization', c_int32),
+        ('op', c_void_p), ('ldop', c_int64), ('pre', c_void_p), ('Cprev', c_void_p),
+        ('dH_out', c_void_p), ('lddh', c_int64), ('dC_out', c_void_p), ('lddc', c_int64),
+        ('WT', c_void_p), ('ldwt', c_int64),
+        ('src', c_void_p), ('dst', c_void_p), ('edge_w', c_void_p), ('E', c_int64), ('idx64', c_int32), ('lambda_max', ctypes.c_float),
+        ('lambda_ptr', c_void_p),
+        ('d_W', c_void_p), ('d_lins', c_void_p), ('d_b', c_void_p), ('d_conv_bias', c_void_p),
+        ('d_x', c_void_p), ('d_H', c_void_p), ('d_Cprev', c_void_p),
+        ('workspace', c_void_p), ('workspace_bytes', c_size_t),
+    ]  # fmt: skip
+
+
+SIGNATURES['tgmx_gclstm_gate_backward'] = (c_int32, [_P, _P, c_int64, c_int32, _P, c_int64, _P, c_int64, _P, _P, _P])
+SIGNATURES['tgmx_cheb_laplacian_t'] = SIGNATURES['tgmx_cheb_laplacian']
+SIGNATURES['tgmx_cheb_propagate2'] = (c_int32, [_P, _P, _P, _P, c_int64, c_int32, _P, c_int64, _P, c_int64, _P, c_int64, ctypes.c_float, ctypes.c_float,
+                                                ctypes.c_float, _P, c_int64, c_int64, _P, c_size_t, _P])  # fmt: skip
+SIGNATURES['tgmx_cheb_clenshaw'] = (c_int32, [_P, _P, _P, _P, c_int64, c_int32, c_int32, _P, c_int64, _P, c_int64, c_int64, _P, c_size_t, _P])
+SIGNATURES['tgmx_gclstm_backward_workspace_bytes'] = (c_size_t, [ctypes.POINTER(GclstmBwd)])
+SIGNATURES['tgmx_gclstm_backward'] = (c_int32, [ctypes.POINTER(GclstmBwd), _P])
+
 GCN_EPI = {'none': 0, 'relu': 1, 'tau': 2}  # TGMX_GCN_EPI_*
 ROLAND_UPDATE = {'moving': 0, 'learnable': 0, None: 0, 'mlp': 1, 'gru': 2}  # TGMX_ROLAND_*
 

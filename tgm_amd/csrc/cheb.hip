@@ -7,6 +7,9 @@
 // degree is taken over the SOURCE index: without weights it is an integer count (integer atomics do not depend on the order of arrival); with
 // weights a second stable sort by source groups the positions and one wave per node sums its group in a fixed order.
 //
+// The transpose (tgmx_cheb_laplacian_t, the backward's operator) is the same builder with the key roles swapped, (src << cb | dst): the
+// degrees, ChebEntry's arithmetic and the diagonal are the very same code, so its entries are those of the forward's CSR bit for bit.
+//
 // Propagate: out = alpha (L_hat t) + beta prev, the gather kernels of spmm.h (shared with gcn.hip) with ChebEpi as their epilogue.
 #include "common.h"
 #include "edge_csr.h"
@@ -18,9 +21,10 @@ constexpr int kChebThreads = kSpmmThreads;
 constexpr int kChebWaves = kSpmmWaves;
 
 // ---- Laplacian --------------------------------------------------------------------------------------------------------------------------
-// keys by destination (and by source when the degrees are weighted); cnt: the unweighted degree as an integer count
+// keys by destination, or by source for the transpose (and by source when the degrees are weighted); cnt: the unweighted degree as an
+// integer count
 __global__ __launch_bounds__(256) void cheb_keys_kernel(const void* __restrict__ src, const void* __restrict__ dst, int is64, long long E, long long N,
-                                                        int cb, unsigned long long* __restrict__ kd, unsigned* __restrict__ pos,
+                                                        int cb, int by_src, unsigned long long* __restrict__ kd, unsigned* __restrict__ pos,
                                                         unsigned* __restrict__ ks, int* __restrict__ cnt, int* __restrict__ skipped) {
   const long long step = (long long)gridDim.x * blockDim.x;
   for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < E; e += step) {
@@ -28,7 +32,7 @@ __global__ __launch_bounds__(256) void cheb_keys_kernel(const void* __restrict__
     const bool in = s >= 0 && s < N && d >= 0 && d < N;
     const bool ok = in && s != d;
     if (!in && skipped) atomicAdd(skipped, 1);
-    kd[e] = key_of(ok, d, s, cb);
+    kd[e] = by_src ? key_of(ok, s, d, cb) : key_of(ok, d, s, cb);
     pos[e] = (unsigned)e;
     if (ks) ks[e] = ok ? (unsigned)s : (unsigned)N;
     else if (ok) atomicAdd(&cnt[s], 1);
@@ -79,6 +83,7 @@ __global__ __launch_bounds__(kChebThreads) void cheb_degree_kernel(const unsigne
 }
 
 // entry t of the Laplacian, from source s to destination d: -w_e scaled by the normalisation's degree factors, then 2 / lambda_max
+// (by_src: the rows are the sources, so the key's column is the destination)
 struct ChebEntry {
   const unsigned* pos_sorted;
   const float* w;
@@ -87,7 +92,9 @@ struct ChebEntry {
   float lambda_max;
   const float* lambda_ptr;
   float* vals;
-  __device__ __forceinline__ void operator()(long long t, long long s, long long d) const {
+  int by_src;
+  __device__ __forceinline__ void operator()(long long t, long long col, long long row) const {
+    const long long s = by_src ? row : col, d = by_src ? col : row;
     const float lmax = lambda_ptr ? lambda_ptr[0] : lambda_max;
     const float we = w ? w[pos_sorted[t]] : 1.f;
     float m;
@@ -195,49 +202,64 @@ extern "C" size_t tgmx_cheb_workspace_bytes(int64_t E, int64_t N) {
   return cheb_carve(nullptr, E, N, w) == TGMX_OK ? w.total : 0;
 }
 
-extern "C" int tgmx_cheb_laplacian(const void* src, const void* dst, int32_t idx64, const float* w, int64_t E, int64_t N, int32_t normalization,
-                                   float lambda_max, const float* lambda_ptr, int32_t* indptr, int32_t* cols, float* vals, float* diag,
-                                   void* workspace, size_t workspace_bytes, int32_t* skipped, tgmx_stream_t stream) {
-  TGMX_REQUIRE(E >= 0 && E < (1ll << 31) && N > 0 && N < (1ll << 31), "cheb_laplacian: bad sizes E=%lld N=%lld", (long long)E, (long long)N);
-  TGMX_REQUIRE(normalization >= TGMX_CHEB_NORM_NONE && normalization <= TGMX_CHEB_NORM_RW, "cheb_laplacian: unknown normalization %d", normalization);
-  TGMX_REQUIRE(indptr && diag && workspace && (E == 0 || (src && dst && cols && vals)), "cheb_laplacian: null pointer");
+// rows by destination (by_src = 0) or by source (the transpose); `what` names the entry point in the messages
+static int cheb_laplacian_build(int by_src, const char* what, const void* src, const void* dst, int32_t idx64, const float* w, int64_t E, int64_t N,
+                                int32_t normalization, float lambda_max, const float* lambda_ptr, int32_t* indptr, int32_t* cols, float* vals,
+                                float* diag, void* workspace, size_t workspace_bytes, int32_t* skipped, tgmx_stream_t stream) {
+  TGMX_REQUIRE(E >= 0 && E < (1ll << 31) && N > 0 && N < (1ll << 31), "%s: bad sizes E=%lld N=%lld", what, (long long)E, (long long)N);
+  TGMX_REQUIRE(normalization >= TGMX_CHEB_NORM_NONE && normalization <= TGMX_CHEB_NORM_RW, "%s: unknown normalization %d", what, normalization);
+  TGMX_REQUIRE(indptr && diag && workspace && (E == 0 || (src && dst && cols && vals)), "%s: null pointer", what);
   hipStream_t st = (hipStream_t)stream;
   ChebWorkspace l;
   if (cheb_carve(workspace, E, N, l) != TGMX_OK || workspace_bytes < l.total) {
-    set_error("cheb_laplacian: workspace too small (%zu bytes)", workspace_bytes);
+    set_error("%s: workspace too small (%zu bytes)", what, workspace_bytes);
     return TGMX_E_INVALID;
   }
   const int cb = col_bits(N);
   const bool weighted = w != nullptr && E > 0;
   if (!weighted && hipMemsetAsync(l.cnt, 0, (size_t)N * sizeof(int), st) != hipSuccess) {
-    set_error("cheb_laplacian: clearing the degree counts failed");
+    set_error("%s: clearing the degree counts failed", what);
     return TGMX_E_LAUNCH;
   }
   if (E > 0) {  // (a zero-length sort is not issued)
-    hipLaunchKernelGGL(cheb_keys_kernel, dim3(grid_for(E, 256, 4096)), dim3(256), 0, st, src, dst, idx64, (long long)E, (long long)N, cb, l.kd_in,
+    hipLaunchKernelGGL(cheb_keys_kernel, dim3(grid_for(E, 256, 4096)), dim3(256), 0, st, src, dst, idx64, (long long)E, (long long)N, cb, by_src, l.kd_in,
                        l.pos_in, weighted ? l.ks_in : nullptr, l.cnt, skipped);
-    TGMX_CHECK_LAUNCH("cheb_laplacian(keys)");
+    TGMX_CHECK_LAUNCH(what);
     if (weighted) {
       int sb = 1;
       while ((1ll << sb) <= N) ++sb;  // the keys go up to N itself (the skipped edges)
       size_t tb = l.temp_bytes;
       if (rocprim::radix_sort_pairs(l.temp, tb, (const unsigned*)l.ks_in, l.ks_out, (const unsigned*)l.pos_in, l.ps_out, (size_t)E, 0u, (unsigned)sb,
                                     st) != hipSuccess) {
-        set_error("cheb_laplacian: radix sort (by source) failed");
+        set_error("%s: radix sort (by source) failed", what);
         return TGMX_E_LAUNCH;
       }
     }
     if (sort_keys_pos(l.temp, l.temp_bytes, l.kd_in, l.kd_out, l.pos_in, l.pos_out, (size_t)E, cb, st) != hipSuccess) {
-      set_error("cheb_laplacian: radix sort (by destination) failed");
+      set_error("%s: radix sort (of the rows) failed", what);
       return TGMX_E_LAUNCH;
     }
   }
   hipLaunchKernelGGL(cheb_degree_kernel, dim3(grid_for(N, kChebWaves, 4096)), dim3(kChebThreads), 0, st, weighted ? l.ks_out : nullptr, l.ps_out, w,
                      l.cnt, (long long)E, (long long)N, normalization, lambda_max, lambda_ptr, l.dis, diag);
-  TGMX_CHECK_LAUNCH("cheb_laplacian(degree)");
-  csr_rows_launch(l.kd_out, (long long)E, (long long)N, cb, indptr, cols, ChebEntry{l.pos_out, w, l.dis, normalization, lambda_max, lambda_ptr, vals}, st);
-  TGMX_CHECK_LAUNCH("cheb_laplacian(rows)");
+  TGMX_CHECK_LAUNCH(what);
+  csr_rows_launch(l.kd_out, (long long)E, (long long)N, cb, indptr, cols, ChebEntry{l.pos_out, w, l.dis, normalization, lambda_max, lambda_ptr, vals, by_src}, st);
+  TGMX_CHECK_LAUNCH(what);
   return TGMX_OK;
+}
+
+extern "C" int tgmx_cheb_laplacian(const void* src, const void* dst, int32_t idx64, const float* w, int64_t E, int64_t N, int32_t normalization,
+                                   float lambda_max, const float* lambda_ptr, int32_t* indptr, int32_t* cols, float* vals, float* diag,
+                                   void* workspace, size_t workspace_bytes, int32_t* skipped, tgmx_stream_t stream) {
+  return cheb_laplacian_build(0, "cheb_laplacian", src, dst, idx64, w, E, N, normalization, lambda_max, lambda_ptr, indptr, cols, vals, diag, workspace,
+                              workspace_bytes, skipped, stream);
+}
+
+extern "C" int tgmx_cheb_laplacian_t(const void* src, const void* dst, int32_t idx64, const float* w, int64_t E, int64_t N, int32_t normalization,
+                                     float lambda_max, const float* lambda_ptr, int32_t* indptr, int32_t* cols, float* vals, float* diag,
+                                     void* workspace, size_t workspace_bytes, int32_t* skipped, tgmx_stream_t stream) {
+  return cheb_laplacian_build(1, "cheb_laplacian_t", src, dst, idx64, w, E, N, normalization, lambda_max, lambda_ptr, indptr, cols, vals, diag,
+                              workspace, workspace_bytes, skipped, stream);
 }
 
 extern "C" size_t tgmx_cheb_propagate_scratch_floats(int64_t nnz, int32_t C) { return spmm_scratch_floats(nnz, C); }

@@ -7,13 +7,18 @@ Same constructors, argument names and ``state_dict`` keys as the reference (``W_
 Inference (no grad): the scaled Laplacian of the snapshot is built ONCE as a CSR by destination (``tgmx_cheb_laplacian``: one stable radix
 sort, no float atomics), the Chebyshev basis ``Tx_0 .. Tx_{K-1}`` is K - 1 gather SpMMs (``tgmx_cheb_propagate``) written straight into the
 column slices of ONE GEMM operand, and the cell -- four convolutions sharing the basis, the four input projections, the gates -- is one
-native call (``tgmx_gclstm_forward``): one GEMM against the stacked weights, one pointwise epilogue, no read back.  Training composes the
-same arithmetic from torch ops on the device (``index_add_`` and ``matmul``; not native), so autograd does the backward.
+native call (``tgmx_gclstm_forward``): one GEMM against the stacked weights, one pointwise epilogue, no read back.
+
+Training (autograd has something to track): the same forward call, with the activations the backward reads kept in buffers of the call,
+and a hand-written backward as one native call (``_gclstm_train.py``, ``csrc/cheb_bwd.hip``).  Outside that path's envelope -- a gradient
+asked of ``edge_weight`` or of a tensor ``lambda_max``, autocast, another dtype, ``TGMX_GCLSTM_BWD=torch`` -- the same arithmetic is
+composed from torch ops on the device (``forward_composed``: ``index_add_`` and ``matmul``) and autograd does the backward.
 """
 from __future__ import annotations
 
 import ctypes
 import math
+from types import SimpleNamespace
 from typing import List, Optional, Tuple, Union
 
 import torch
@@ -21,7 +26,7 @@ import torch.nn as nn
 from torch import Tensor
 
 from .. import _native
-from . import _ops
+from . import _gclstm_train, _ops
 from ._fwd_plumbing import cached_weights, carve_scratch, needs_torch, up4
 from ._paramver import TransientCaches
 from ._snapshot import _edge_weight, _endpoints, _Skipped, csr_scratch_sizes, propagate, propagate_scratch, scaled_laplacian
@@ -135,7 +140,25 @@ class ChebConv(_Skipped, TransientCaches, nn.Module):
         _native.require_device(x, 'x')
         lam, lam_t = _lambda(lambda_max, self.normalization, x.device)
         if needs_torch(self, 0.0, x):
+            if x.dim() == 2 and x.shape[1] == self.in_channels and _gclstm_train.in_envelope(self, (x,), edge_weight, lambda_max):
+                return _gclstm_train.apply_conv(self, x, edge_index, edge_weight, lam, lam_t)
             return self.forward_composed(x, edge_index, edge_weight, lambda_max)
+        return self._forward_native(x, edge_index, edge_weight, lam, lam_t)
+
+    def _stacked(self, dev):
+        """([lins.0 | ... | lins.K-1] as [out, up4(K in)], bias), cached against the parameters' versions."""
+        K, cin = len(self.lins), self.in_channels
+        ld = up4(K * cin)
+
+        def stacked():
+            W = torch.zeros((self.out_channels, ld), dtype=torch.float32, device=dev)
+            W[:, : K * cin] = torch.cat([lin.weight.detach().float() for lin in self.lins], dim=1)
+            return W, None if self.bias is None else _ops._f32c(self.bias.detach(), 'bias')
+
+        return cached_weights(self, stacked)
+
+    def _forward_native(self, x: Tensor, edge_index: Tensor, edge_weight: Optional[Tensor], lam: float, lam_t: Optional[Tensor], own: bool = False):
+        """``own``: the training path's call -- also returns what its backward reads (the basis ``op`` is a tensor of the call either way)."""
         x = _ops._f32c(x, 'x')
         N, K, cin, dev = x.shape[0], len(self.lins), self.in_channels, x.device
         if x.dim() != 2 or x.shape[1] != cin:
@@ -144,13 +167,7 @@ class ChebConv(_Skipped, TransientCaches, nn.Module):
         if N == 0:
             return out
         ld = up4(K * cin)
-
-        def stacked():
-            W = torch.zeros((self.out_channels, ld), dtype=torch.float32, device=dev)
-            W[:, : K * cin] = torch.cat([lin.weight.detach().float() for lin in self.lins], dim=1)
-            return W, None if self.bias is None else _ops._f32c(self.bias.detach(), 'bias')
-
-        W, b = cached_weights(self, stacked)
+        W, b = self._stacked(dev)
         op = (torch.zeros if ld > K * cin else torch.empty)((N, ld), dtype=torch.float32, device=dev)  # [Tx_0 | ... | Tx_{K-1}]
         op[:, :cin].copy_(x)
         if K > 1:
@@ -159,7 +176,12 @@ class ChebConv(_Skipped, TransientCaches, nn.Module):
             for k in range(1, K):
                 sl = lambda j: op[:, j * cin : (j + 1) * cin]
                 propagate(lap, sl(k - 1), sl(k), sl(k - 2) if k > 1 else None, 2.0 if k > 1 else 1.0, -1.0 if k > 1 else 0.0, scratch)
-        return _ops.sgemm_nt(op, W, out, bias=b, K=K * cin)
+        _ops.sgemm_nt(op, W, out, bias=b, K=K * cin)
+        if not own:
+            return out
+        s = _gclstm_train.saved_graph(edge_index, edge_weight, lam, lam_t)
+        s.N, s.op, s.ld = N, op, ld
+        return out, s
 
 
 def _lambda_any(lambda_max: LambdaMax, normalization: Optional[str]) -> Tuple[float, Optional[Tensor]]:
@@ -224,12 +246,36 @@ class GCLSTM(_Skipped, TransientCaches, nn.Module):
         lam, lam_t = _lambda(lambda_max, self.normalization, node_x.device)
         if node_x.dim() != 2 or node_x.shape[1] != self.in_channels:
             raise ValueError(f'expected node_x [N, {self.in_channels}], got {list(node_x.shape)}')
-        if needs_torch(self, 0.0, node_x, *[t for t in (H, C) if t is not None]):
+        states = [t for t in (H, C) if t is not None]
+        if needs_torch(self, 0.0, node_x, *states):
+            if _gclstm_train.in_envelope(self, (node_x, *states), edge_weight, lambda_max):
+                return _gclstm_train.apply(self, node_x, edge_index, edge_weight, H, C, lam, lam_t)
             return self.forward_composed(node_x, edge_index, edge_weight, H, C, lambda_max)
         return self._forward_native(node_x, edge_index, edge_weight, H, C, lam, lam_t)
 
+    def _stacked(self, dev):
+        """(W [4C, up4(in + K C)], b [4C]), cached against the parameters' versions.  Rows of gate g: [W_g^T | lins_g,0 | ... | lins_g,K-1],
+        bias b_g + conv_g.bias."""
+        Co, K, cin = self.out_channels, self.K, self.in_channels
+        width = cin + K * Co
+        f32 = dict(dtype=torch.float32, device=dev)
+
+        def stacked():
+            W = torch.zeros((4 * Co, up4(width)), **f32)
+            b = torch.empty(4 * Co, **f32)
+            for g, (Wg, bg, conv) in enumerate(self._gates()):
+                rows = slice(g * Co, (g + 1) * Co)
+                W[rows, :cin] = Wg.detach().t()
+                W[rows, cin:width] = torch.cat([lin.weight.detach().float() for lin in conv.lins], dim=1)
+                b[rows] = bg.detach().reshape(-1) if conv.bias is None else bg.detach().reshape(-1) + conv.bias.detach()
+            return W, b
+
+        return cached_weights(self, stacked)
+
     def _forward_native(self, node_x: Tensor, edge_index: Tensor, edge_weight: Optional[Tensor], H: Optional[Tensor], C: Optional[Tensor], lam: float,
-                        lam_t: Optional[Tensor]) -> Tuple[Tensor, Tensor]:  # fmt: skip
+                        lam_t: Optional[Tensor], own: bool = False):  # fmt: skip
+        """``own``: the training path's call -- ``op`` and ``pre`` are tensors of this call instead of regions of the module's scratch, and
+        what the backward reads is returned as a third value."""
         lib = _native.load()
         x = _ops._f32c(node_x, 'node_x')
         N, Co, K, cin, dev = x.shape[0], self.out_channels, self.K, self.in_channels, x.device
@@ -244,17 +290,7 @@ class GCLSTM(_Skipped, TransientCaches, nn.Module):
         width = cin + K * Co
         ld = up4(width)
 
-        def stacked():  # rows of gate g: [W_g^T | lins_g,0 | ... | lins_g,K-1], bias b_g + conv_g.bias
-            W = torch.zeros((4 * Co, ld), **f32)
-            b = torch.empty(4 * Co, **f32)
-            for g, (Wg, bg, conv) in enumerate(self._gates()):
-                rows = slice(g * Co, (g + 1) * Co)
-                W[rows, :cin] = Wg.detach().t()
-                W[rows, cin:width] = torch.cat([lin.weight.detach().float() for lin in conv.lins], dim=1)
-                b[rows] = bg.detach().reshape(-1) if conv.bias is None else bg.detach().reshape(-1) + conv.bias.detach()
-            return W, b
-
-        W, b = cached_weights(self, stacked)
+        W, b = self._stacked(dev)
         src, dst = _endpoints(edge_index)
         E = src.numel()
         w = _edge_weight(edge_weight, E)
@@ -263,7 +299,9 @@ class GCLSTM(_Skipped, TransientCaches, nn.Module):
             nprop = lib.tgmx_cheb_propagate_scratch_floats(E, Co)
             csr = csr_scratch_sizes(E, N, lib.tgmx_cheb_workspace_bytes(E, N), 'GCLSTM')
         # indptr, cols, vals, diag, sort workspace, op, pre, the propagate's chunk sums
-        bufs = carve_scratch(self, csr + [N * ld, N * 4 * Co, nprop], dev)
+        bufs = carve_scratch(self, csr + ([0, 0] if own else [N * ld, N * 4 * Co]) + [nprop], dev)
+        if own:
+            bufs[5], bufs[6] = torch.empty(N * ld, **f32), torch.empty(N * 4 * Co, **f32)
         d = self.__dict__
         a = d.get('_tgmx_args')
         if a is None:
@@ -279,4 +317,7 @@ class GCLSTM(_Skipped, TransientCaches, nn.Module):
         a.prop_ws, a.prop_ws_floats = (bufs[7].data_ptr() if nprop else None), nprop
         a.H_out, a.C_out = H_out.data_ptr(), C_out.data_ptr()
         _native.check(lib.tgmx_gclstm_forward(ctypes.byref(a), _native.stream_ptr()), 'tgmx_gclstm_forward')
-        return H_out, C_out
+        if not own:
+            return H_out, C_out
+        s = SimpleNamespace(N=N, op=bufs[5], pre=bufs[6], ld=ld, C=C, src=src, dst=dst, E=E, w=w, lam=lam, lam_t=lam_t)
+        return H_out, C_out, s
