@@ -1177,7 +1177,7 @@ typedef struct tgmx_tpnet_fwd {
 } tgmx_tpnet_fwd_t;
 int tgmx_tpnet_forward(const tgmx_tpnet_fwd_t* args, tgmx_stream_t stream);
 
-/* ---- NCNPredictor (the reference's tgm/nn/decoder/ncnpred.py): the common-neighbour decoder of TNCN, inference ---- */
+/* ---- NCNPredictor (the reference's tgm/nn/decoder/ncnpred.py): the common-neighbour decoder of TNCN, forward ---- */
 
 /* The symmetric adjacency of edge_index [2, E] (int64 when is64, else int32; row 1 starts row_stride entries after row 0) over N local
  * node ids, as sorted rows: A[a, b] = how often (a, b) or (b, a) occurs, so a self-loop counts twice.  indptr [N + 1]; cols [2 E] holds
@@ -1214,6 +1214,44 @@ typedef struct tgmx_ncn_fwd {
   float* out;                                                   /* [B, out_ch] */
 } tgmx_ncn_fwd_t;
 int tgmx_ncn_forward(const tgmx_ncn_fwd_t* args, tgmx_stream_t stream);
+
+/* ---- NCNPredictor training (csrc/ncn_bwd.hip): the backward of the common-neighbour stage, and the whole backward as ONE call.  No float
+ * atomics anywhere: every sum has one fixed order, two runs give the same bits.  Nothing is read back to the host. ---- */
+
+/* dx [N, C] (contiguous; EVERY row is written, zeros where nothing contributes) from dxs [B, lddxs], the gradient of tgmx_ncn_cn_emb's xs,
+ * with g0 .. g3 the C-wide column blocks of dxs[r] (g_cn the last of the k).  Node n receives, in this order:
+ *   (1) every in-range pair r with tar_i[r] = n, ascending r:  g0[r] * x[tar_j[r]]; then, k = 4, r active, m = A[i, j] > 0:  m W[r, i] g1[r]
+ *   (2) every in-range pair r with tar_j[r] = n, ascending r:  g0[r] * x[tar_i[r]]; then, k = 4, r active, m > 0:            m W[r, j] g2[r]
+ *   (3) every active pair r with A[n, i_r] > 0 and A[n, j_r] > 0, ascending (i_r, r):  A[n, i_r] A[n, j_r] W[r, n] g_cn[r]
+ * A pair with i = j contributes through (1) and (2).  Active is the forward's rule: last = NULL: every in-range pair; else last [2 N] as
+ * tgmx_ncn_cn_emb left it.  A pair with a target outside [0, N) contributes nothing and is never dereferenced.  W and A are the forward's,
+ * bit for bit (last_update / edge_time NULL: W = 1).  indptr / cols: the adjacency of tgmx_ncn_adj_build over E edges.
+ * The pairs are read through two inverted indexes (by tar_i, by tar_j: ONE radix sort of 2 B keys); a wave per node keeps 256 channels in
+ * registers and stores once.  A row of more than 512 entries leaves term (3) to two further launches, issued whenever 2 E > 512: a wave per
+ * 256-entry chunk of the entry array, then the row's chunk sums in ascending chunk order onto its terms (1) and (2).  No degree bound.
+ * 2 N, 2 E, 2 B < 2^31.  workspace: tgmx_ncn_dx_workspace_bytes(N, E, B, C) bytes, host arithmetic only (0: a size out of range). */
+size_t tgmx_ncn_dx_workspace_bytes(int64_t N, int64_t E, int64_t B, int32_t C);
+int tgmx_ncn_dx(const float* x, int64_t N, int32_t C, int32_t k, const int32_t* indptr, const int32_t* cols, int64_t E, const void* tar,
+                int32_t tar_is64, int64_t tar_stride, int64_t B, const int64_t* last_update, const int64_t* edge_time, const int32_t* last,
+                const float* dxs, int64_t lddxs, float* dx, void* workspace, size_t workspace_bytes, tgmx_stream_t stream);
+
+/* The backward's argument block (tgmx_abi_sizeof(33)).  fwd: the block tgmx_ncn_forward ran with -- the inputs, the weights where the
+ * parameters are, and what that call wrote into buffers of ITS OWN: xs, h (post-ReLU), last, indptr, cols (or the prepared adjacency);
+ * edge_index, adj_ws and out are not read.  dout [B, out_ch] with leading dimension lddout.  Every gradient pointer may be NULL: that
+ * gradient, and every launch that only feeds it, is skipped.  d_x [N, C], d_w1 [H, k C], d_b1 [H], d_w2 [out_ch, H], d_b2 [out_ch], all
+ * contiguous, in the parameters' own layouts.  last_update / edge_time get no gradient (W depends on integers only).
+ * Order: the weights transposed (one tgmx_pack2d) -> the last layer (tgmx_decoder_tail_bwd with the ReLU mask read from h where
+ * out_ch <= 16 and W2 fits 48 KB; else tgmx_sgemm_tn, tgmx_colsum, tgmx_sgemm_nt, tgmx_relu_mask) -> d_w1 = dpre^T xs (tgmx_sgemm_tn),
+ * d_b1 (tgmx_colsum) -> dxs = dpre W1 (tgmx_sgemm_nt; only for d_x) -> tgmx_ncn_dx.  B = 0: the gradients asked for are zeroed.
+ * workspace: tgmx_ncn_backward_workspace_bytes() (host only; 0 for sizes out of range, e.g. 2 E >= 2^31). */
+typedef struct tgmx_ncn_bwd {
+  tgmx_ncn_fwd_t fwd;
+  const float* dout; int64_t lddout;
+  float *d_x, *d_w1, *d_b1, *d_w2, *d_b2;
+  void* workspace; size_t workspace_bytes;
+} tgmx_ncn_bwd_t;
+size_t tgmx_ncn_backward_workspace_bytes(const tgmx_ncn_bwd_t* args);
+int tgmx_ncn_backward(const tgmx_ncn_bwd_t* args, tgmx_stream_t stream);
 
 /* ---- EdgeBankPredictor (the reference's tgm/nn/modules/edgebank.py): the edge memory as a device hash table ---- */
 

@@ -484,6 +484,24 @@ SIGNATURES['tgmx_ncn_cn_emb'] = (c_int32, [_P, c_int64, c_int32, c_int32, _P, _P
 SIGNATURES['tgmx_ncn_forward'] = (c_int32, [ctypes.POINTER(NCNFwd), _P])
 
 
+class NcnBwd(ctypes.Structure):
+    """tgmx_ncn_bwd_t (include/tgm_amd.h)."""
+
+    _fields_ = [
+        ('fwd', NCNFwd),
+        ('dout', c_void_p), ('lddout', c_int64),
+        ('d_x', c_void_p), ('d_w1', c_void_p), ('d_b1', c_void_p), ('d_w2', c_void_p), ('d_b2', c_void_p),
+        ('workspace', c_void_p), ('workspace_bytes', c_size_t),
+    ]  # fmt: skip
+
+
+SIGNATURES['tgmx_ncn_dx_workspace_bytes'] = (c_size_t, [c_int64, c_int64, c_int64, c_int32])
+SIGNATURES['tgmx_ncn_dx'] = (c_int32, [_P, c_int64, c_int32, c_int32, _P, _P, c_int64, _P, c_int32, c_int64, c_int64, _P, _P, _P, _P, c_int64, _P,
+                                       _P, c_size_t, _P])  # fmt: skip
+SIGNATURES['tgmx_ncn_backward_workspace_bytes'] = (c_size_t, [ctypes.POINTER(NcnBwd)])
+SIGNATURES['tgmx_ncn_backward'] = (c_int32, [ctypes.POINTER(NcnBwd), _P])
+
+
 class EdgeBank(ctypes.Structure):
     """tgmx_edgebank_t (include/tgm_amd.h)."""
 

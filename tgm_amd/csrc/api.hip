@@ -49,6 +49,7 @@ extern "C" size_t tgmx_abi_sizeof(int32_t which) {
     case 29: return sizeof(tgmx_node_analytics_t);
     case 30: return sizeof(tgmx_decoder_train_t);
     case 32: return sizeof(tgmx_gclstm_bwd_t);  // (31 stays 0 for the same reason)
+    case 33: return sizeof(tgmx_ncn_bwd_t);
     default: return 0;
   }
 }

@@ -11,6 +11,7 @@
 // over the channels.  The order of the sum is fixed and there are no float atomics: two runs give the same bits.
 #include "common.h"
 #include "edge_csr.h"
+#include "ncn_rows.h"
 
 namespace tgmx {
 
@@ -62,26 +63,6 @@ __global__ __launch_bounds__(256) void ncn_last_kernel(const void* __restrict__ 
     // a pair with either target outside the node table gets a zero row: it marks nothing, on either side
     if (i >= 0 && i < N && j >= 0 && j < N) atomicMax(&last[side * N + (side ? j : i)], (int)r);
   }
-}
-
-__device__ __forceinline__ int lower_bound_i32(const int32_t* __restrict__ c, int lo, int hi, long long v) {
-  while (lo < hi) {
-    const int mid = (int)(((long long)lo + hi) >> 1);
-    if ((long long)c[mid] < v) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
-}
-// how often id v occurs in the sorted run c[lo, hi)
-__device__ __forceinline__ int count_in(const int32_t* __restrict__ c, int lo, int hi, long long v) {
-  const int a = lower_bound_i32(c, lo, hi, v);
-  if (a == hi || c[a] != v) return 0;
-  return lower_bound_i32(c, a, hi, v + 1) - a;
-}
-// exp(-(float32(edge_time - last_update) / 10000)): the int64 gap rounded to float32 as torch does, a correctly rounded division, an accurate expf
-__device__ __forceinline__ float decay_weight(const int64_t* __restrict__ last_update, long long et, long long n) {
-  const float gap = (float)(et - (long long)last_update[n]);
-  return expf(-(gap / 10000.f));
 }
 
 struct CnArgs {

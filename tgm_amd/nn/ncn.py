@@ -27,9 +27,19 @@ Three quirks of the reference are part of the contract:
 
 Inference (no gradient needed) is ONE native call, ``tgmx_ncn_forward``: a radix sort of the 2 E half-edges is the adjacency, one wave
 per pair intersects two sorted rows and gather-sums ``x`` over the matches in ascending id (deterministic, no float atomics), then the two
-Linear layers on the exact-fp32 GEMM.  Training is NOT native: the same arithmetic from torch ops on the device under autograd, through
-dense ``[B, N]`` rows (never ``[N, N]``).  ``k = 8`` is accepted by the constructor and not implemented: ``forward`` raises
-``NotImplementedError``.  CPU tensors raise ``NativeLibraryError``.  A pair with a target id outside ``[0, N)`` gives a zero row on both paths.
+Linear layers on the exact-fp32 GEMM.
+
+Training (autograd has something to track) is native too: ``forward`` is the same ``tgmx_ncn_forward`` call, writing what the backward
+reads into buffers of the call (so the result is the no-grad call's bit for bit, and the positives' and negatives' calls of one step do
+not share them), and the backward is ONE native call, ``tgmx_ncn_backward`` (``_ncn_train.py``, ``csrc/ncn_bwd.hip``): the two Linear layers
+from the shared blocks, then ``dx`` node by node through two inverted indexes of the pairs and the forward's adjacency -- fixed summation
+order, no float atomics, no ``[B, N]`` intermediates.  ``last_update`` / ``edge_time`` get no gradient (the decay weight depends on integers
+only) and ``xslin`` gets ``None``.  Outside that path -- autocast, parameters of another dtype, ``get_cn_emb`` under gradients,
+``TGMX_NCN_BWD=torch`` -- the same arithmetic is composed from torch ops on the device under autograd, through dense ``[B, N]`` rows (never
+``[N, N]``).  ``TGMX_NCN_BWD=py`` issues the native backward's launches one ctypes call each (the same bits).
+
+``k = 8`` is accepted by the constructor and not implemented: ``forward`` raises ``NotImplementedError``.  CPU tensors raise
+``NativeLibraryError``.  A pair with a target id outside ``[0, N)`` gives a zero row, and no gradient, on every path.
 """
 from __future__ import annotations
 
@@ -41,7 +51,7 @@ import torch.nn as nn
 from torch import Tensor
 
 from .. import _native
-from . import _ops
+from . import _ncn_train, _ops
 from ._fwd_plumbing import cached_block, carve_scratch, i64, needs_torch, up4
 from ._paramver import TransientCaches
 
@@ -164,11 +174,13 @@ class NCNPredictor(TransientCaches, nn.Module):
                 edge_time: Optional[Tensor] = None) -> Tensor:  # fmt: skip
         a = self._inputs(x, edge_index, tar_ei, last_update, edge_time)
         if needs_torch(self, 0.0, x):
+            if _ncn_train.in_envelope(self, a['x']):
+                return _ncn_train.apply(self, a)
             # (the reference's xs.relu() discards its result)
             return self.xsmlp(self._torch_xs(a)).view(-1)
         return self._native_xs(a, mlp=True)[1].view(-1)
 
-    # -- training: torch ops under autograd (not native) ---------------------------------------------------------------------------------
+    # -- the composed path: torch ops under autograd ---------------------------------------------------------------------------------------
     def _torch_rows(self, a: dict) -> Tuple[Tensor, Tensor]:
         """(half-edge rows, half-edge columns) int64 [2 E]; a half-edge with an endpoint outside [0, N) is left out or gets row N."""
         if a['adj'] is not None:
