@@ -325,6 +325,13 @@ int tgmx_defer_flush(tgmx_defer_t* d, tgmx_stream_t stream); /* enqueue the pend
 /* hop-1 rows per wave of the fused hop-0 + hop-1 lookup launch from now on (0: one wave per row, the default; -1: back to
  * TGMX_FUSED_ROWS / the default); returns the previous value.  A/B and tests. */
 int32_t tgmx_set_fused_rows(int32_t rows);
+/* Row order of that launch's one-wave-per-row schedule from now on: 0 hop-1 rows in output order, 1 the seeds dealt round-robin
+ * across equal seed groups, 2 also every seed's newest quad of rows first (-1: back to TGMX_FUSED_ORDER / the default); returns
+ * the previous value.  Outputs do not depend on it.  A/B and tests. */
+int32_t tgmx_set_fused_order(int32_t mode);
+/* out_idx[i], i in [0, S0 * k0): the hop-1 row (s0 * k0 + j) that the i-th hop-1 wave of the launch takes under `mode`, for S0
+ * hop-0 seeds in `groups` groups ending at group_end[g] (groups = 0: plain seed arrays).  Host only: the function the kernel runs. */
+int32_t tgmx_fused_row_order(int64_t S0, int32_t k0, int32_t groups, const int64_t* group_end, int32_t mode, int64_t* out_idx);
 
 /* ------------------------------------------------------------------------
  * The loader's per-batch call as ONE entry point: DGDataLoader.__call__ (tgm/data/loader.py:158-170: slice,

@@ -342,6 +342,8 @@ SIGNATURES['tgmx_defer_pending'] = (c_int32, [_P])
 SIGNATURES['tgmx_defer_count'] = (c_int64, [_P])
 SIGNATURES['tgmx_defer_flush'] = (c_int32, [_P, _P])
 SIGNATURES['tgmx_set_fused_rows'] = (c_int32, [c_int32])
+SIGNATURES['tgmx_set_fused_order'] = (c_int32, [c_int32])
+SIGNATURES['tgmx_fused_row_order'] = (c_int32, [c_int64, c_int32, c_int32, _P, c_int32, _P])
 SIGNATURES['tgmx_tgn_gru_gate_backward'] = (c_int32, [_P, _P, _P, _P, c_int32, c_int64, _P, _P, _P])
 SIGNATURES['tgmx_tgn_aggregate_backward'] = (c_int32, [c_int64, _P, _P, _P, _P, _P, _P, c_int32, c_int32, _P, _P, c_int32, c_int32, _P, _P, _P])
 SIGNATURES['tgmx_tconv_edge_attr_backward'] = (c_int32, [_P, _P, _P, _P, _P, _P, c_int32, c_int32, c_int64, _P, _P])

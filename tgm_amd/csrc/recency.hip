@@ -68,6 +68,83 @@ struct SeedGroups {
   int64_t* gen_out_ts;
 };
 
+// FastDiv's quotient on host and device alike (n * d < 2^32: exact)
+__host__ __device__ __forceinline__ uint32_t fastdiv_of(const FastDiv& f, uint32_t n) {
+  return (uint32_t)(((unsigned long long)n * f.m) >> 32) + (n & f.pass);
+}
+__host__ __device__ __forceinline__ unsigned long long mulhi_u64(unsigned long long x, unsigned long long y) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __umul64hi(x, y);
+#else
+  return (unsigned long long)(((unsigned __int128)x * y) >> 64);
+#endif
+}
+
+// Row order of the fused hop-0 + hop-1 launch: which hop-1 row (s0, j) -- row s0 * k0 + j of hop 1's outputs -- the i-th hop-1
+// wave takes.  It changes which wave runs when and nothing else.
+//   identity           t = i / k0, j = i % k0, s0 = t
+//   deal               s0 = (t % G) * n + t / G: the seeds taken round-robin from G >= 2 seed groups of n seeds each ([src | dst | neg])
+//   quads              u = i / R, r = i % R, c = C - 1 - u / S0, t = u % S0, j = c * R + r (R = kFusedWaves, C = k0 / R): the R rows of a
+//                      workgroup are one quad of one seed's rows, and every seed's newest quad (rows are right-aligned: the highest j)
+//                      runs before any seed's next one, the pad-heavy quad 0 last
+// fused_order_make decides what applies (TGMX_FUSED_ORDER: 0 identity, 1 deal, 2 deal + quads); each piece is a bijection by itself.
+constexpr int kFusedWaves = 4;  // waves per workgroup of the fused launch
+struct FusedOrder {
+  FastDiv dk0, dS0, dG;  // filled on the host (dS0 only under quads, dG only under deal)
+  uint32_t n;            // seeds per group (deal)
+  int quads, deal;
+  int wide;              // rows * max(S0, k0) >= 2^32: the 32-bit reciprocals are not exact, identity through m64
+  unsigned long long m64;  // floor(2^64 / k0) + 1 (k0 >= 2)
+};
+
+static FusedOrder fused_order_make(long long S0, int k0, int groups, const long long* group_end, int mode) {
+  FusedOrder o{};
+  const long long rows = S0 * k0, big = S0 > k0 ? S0 : k0;
+  o.m64 = k0 >= 2 ? ~0ull / (unsigned long long)k0 + 1ull : 0ull;
+  o.wide = rows <= 0 || big >= (1ll << 32) || rows >= ((1ll << 32) + big - 1) / big;  // rows * big >= 2^32 (groups <= 8 < big or S0 < 8)
+  if (o.wide) return o;
+  o.dk0 = make_fastdiv((uint32_t)k0);
+  if (mode >= 1 && groups >= 2 && S0 % groups == 0 && rows * groups < (1ll << 32)) {
+    const long long n = S0 / groups;
+    bool equal = true;
+    for (int g = 0; g < groups; ++g) equal = equal && group_end[g] == (g + 1) * n;
+    if (equal) {
+      o.deal = 1;
+      o.n = (uint32_t)n;
+      o.dG = make_fastdiv((uint32_t)groups);
+    }
+  }
+  if (mode == 2 && k0 % kFusedWaves == 0) {
+    o.quads = 1;
+    o.dS0 = make_fastdiv((uint32_t)S0);
+  }
+  return o;
+}
+
+// hop-1 wave i -> (s0, j); the row is s0 * k0 + j
+__host__ __device__ __forceinline__ void fused_row_of(const FusedOrder& o, long long i, int k0, long long S0, long long& s0, int& j) {
+  if (o.wide) {  // (never at the shapes the launch is planned for: kept exact for any size)
+    s0 = k0 >= 2 ? (long long)mulhi_u64((unsigned long long)i, o.m64) : i;
+    j = (int)(i - s0 * k0);
+    return;
+  }
+  uint32_t t;
+  if (o.quads) {
+    const uint32_t u = (uint32_t)i / kFusedWaves, r = (uint32_t)i % kFusedWaves;
+    const uint32_t cq = fastdiv_of(o.dS0, u);
+    t = u - cq * (uint32_t)S0;
+    j = (int)(((uint32_t)k0 / kFusedWaves - 1 - cq) * kFusedWaves + r);
+  } else {
+    t = fastdiv_of(o.dk0, (uint32_t)i);
+    j = (int)((uint32_t)i - t * (uint32_t)k0);
+  }
+  if (o.deal) {
+    const uint32_t b = fastdiv_of(o.dG, t);
+    t = (t - b * o.dG.d) * o.n + b;
+  }
+  s0 = t;
+}
+
 struct LookupArgs {
   SeedGroups grp;
   const int64_t* indptr;    // CSR
@@ -122,6 +199,7 @@ struct LookupArgs {
   int32_t* out_valid_prev1;
   // fused launch: hop-1 rows per wave (recency_lookup_fused01_kernel; 0 = one wave per row), and the debug timestamps (TGMX_FUSED_TS)
   int fused_rows;
+  FusedOrder ord;  // row order of the one-wave-per-row schedule (fused_order_make)
   long long* ts;
 };
 
@@ -1453,10 +1531,11 @@ __device__ __forceinline__ void gather_rows(const LookupArgs& a, long long s, in
 }
 
 // the k most recent neighbors of (n, q) into row s of (out_nid, out_ts, out_x)
-template <bool RING, int VEC, bool SMALL>
+// PRE: the caller read the row's old span (out_valid[s]) itself, ahead of the chain of dependent loads that ends here: v_old_pre
+template <bool RING, int VEC, bool SMALL, bool PRE = false>
 __device__ __forceinline__ void lookup_seed(const LookupArgs& a, long long s, int n, long long q, int k, int lane, int* lds_eid,
                                             int32_t* out_nid, int64_t* out_ts, float* out_x, int32_t* out_valid, int32_t* out_valid_prev,
-                                            int32_t* out_eid = nullptr) {
+                                            int32_t* out_eid = nullptr, int v_old_pre = 0) {
   const bool live = n >= 0 && n < a.N;
   // the row's SPAN: slots from its leftmost non-pad one to the end (0: all pads).  Valid slots sit at the right end of a row, but a
   // ring can hold a pad record between real ones (the oracle's lookup keeps it: an interior -1), so it is the leftmost
@@ -1507,7 +1586,7 @@ __device__ __forceinline__ void lookup_seed(const LookupArgs& a, long long s, in
   if (a.D == 0 || out_x == nullptr) return;  // no features, or the consumer gathers them by edge id (out_eid)
   int first_slot = 0;
   if (out_valid) {  // the row's previous contents are known: leave the zeros left of both valid tails alone
-    const int v_old = out_valid[s];
+    const int v_old = PRE ? v_old_pre : out_valid[s];
     first_slot = k - (v_old > v_new ? v_old : v_new);
     if (lane == 0) {
       out_valid[s] = v_new;
@@ -1547,6 +1626,7 @@ __global__ __launch_bounds__(256) void recency_lookup_kernel(const LookupArgs a,
 // Debug timestamps of the fused launch (TGMX_FUSED_TS, off by default; launch_fused01).  Lane 0 of every wave writes one record
 // of kFusedTsWords words at ts[wave of the grid]: wall_clock64() at start and end, the role, and for hop-1 waves the end of the seed
 // phase (hop 0's pick for s0) and the clock spent in the rows' index phase (the pick: waiting for its loads) and gather phase.
+// Word 6 of a one-row hop-1 wave is its row s0 * k0 + j (-1 elsewhere): tools/fused_ts_report.py splits the lives by group and quad.
 constexpr int kFusedTsWords = 8;
 // hop-1 rows per wave of the fused launch (TGMX_FUSED_ROWS): 0, the one-wave-per-row schedule, measured fastest at the wiki
 // shape (row runs of G = 1 - 5 were not faster)
@@ -1618,27 +1698,38 @@ __global__ __launch_bounds__(256) void recency_lookup_fused01_kernel(const Looku
   const long long S0 = a.S;
   const int G = ROWS ? a.fused_rows : 0;
   const int runs = G > 0 ? (k0 + G - 1) / G : k0;  // hop-1 waves per hop-0 seed
-  long long role = 0, t_seed = 0, t_index = 0, t_gather = 0;
+  long long role = 0, t_seed = 0, t_index = 0, t_gather = 0, ts_row = -1;
   for (long long w = (long long)bid * (blockDim.x >> 6) + wave_in_block; w < S0 + S0 * runs; w += waves_total) {
     int n;
     long long q;
     if (w < S0) {
       role = kTsHop0;
-      fetch_seed(a, w, lane, true, n, q);
-      check_seed(a, n, q, 0, lane);
-      lookup_seed<RING, VEC, true>(a, w, n, q, k0, lane, lds_eid, a.out_nid, a.out_ts, a.out_x, a.out_valid, a.out_valid_prev, a.out_eid);
+      if constexpr (ROWS) {
+        fetch_seed(a, w, lane, true, n, q);
+        check_seed(a, n, q, 0, lane);
+        lookup_seed<RING, VEC, true>(a, w, n, q, k0, lane, lds_eid, a.out_nid, a.out_ts, a.out_x, a.out_valid, a.out_valid_prev, a.out_eid);
+      } else {
+        // the row's old span depends on nothing but w: read ahead of the seed -> pick -> gather chain, not inside it
+        const int v_old = (a.D > 0 && a.out_x && a.out_valid) ? a.out_valid[w] : 0;
+        fetch_seed(a, w, lane, true, n, q);
+        check_seed(a, n, q, 0, lane);
+        lookup_seed<RING, VEC, true, true>(a, w, n, q, k0, lane, lds_eid, a.out_nid, a.out_ts, a.out_x, a.out_valid, a.out_valid_prev, a.out_eid, v_old);
+      }
     } else if (!ROWS) {
       role = kTsHop1;
-      const long long idx = w - S0;
-      const long long s0 = idx / k0;
-      const int j = (int)(idx - s0 * k0);
+      long long s0;
+      int j;
+      fused_row_of(a.ord, w - S0, k0, S0, s0, j);
+      const long long idx = s0 * k0 + j;
+      const int v_old = (a.D > 0 && a.out_x1 && a.out_valid1) ? a.out_valid1[idx] : 0;  // (as for hop 0: off the chain)
+      if (TS) ts_row = idx;
       int n0;
       long long q0;
       fetch_seed(a, s0, lane, false, n0, q0);
       const SmallPick o = small_pick<RING>(a, n0, q0, k0, n0 >= 0 && n0 < a.N, lane);
       n = __shfl(o.nbr, j);
       q = __shfl(o.ts, j);
-      lookup_seed<RING, VEC, true>(a, idx, n, q, k1, lane, lds_eid, a.out_nid1, a.out_ts1, a.out_x1, a.out_valid1, a.out_valid_prev1, a.out_eid1);
+      lookup_seed<RING, VEC, true, true>(a, idx, n, q, k1, lane, lds_eid, a.out_nid1, a.out_ts1, a.out_x1, a.out_valid1, a.out_valid_prev1, a.out_eid1, v_old);
     } else {
       const long long run = w - S0;
       const long long s0 = run / runs;
@@ -1707,6 +1798,7 @@ __global__ __launch_bounds__(256) void recency_lookup_fused01_kernel(const Looku
     ts_rec[3] = t_seed;
     ts_rec[4] = t_index;
     ts_rec[5] = t_gather;
+    ts_rec[6] = ts_row;
   }
 }
 
@@ -2661,6 +2753,21 @@ static int fused_rows_per_wave(int k0) {
   return g > k0 ? k0 : g;
 }
 
+// row order of the fused launch (FusedOrder): TGMX_FUSED_ORDER (0 identity, 1 deal, 2 deal + quads; A/B knob), read once;
+// tgmx_set_fused_order overrides it in a running process
+constexpr int kFusedOrderDefault = 2;
+static std::atomic<int> g_fused_order{-1};  // -1: not read yet
+
+static int fused_order_mode() {
+  int m = g_fused_order.load(std::memory_order_relaxed);
+  if (m < 0) {
+    const char* e = getenv("TGMX_FUSED_ORDER");
+    m = (e && *e && atoi(e) >= 0 && atoi(e) <= 2) ? atoi(e) : kFusedOrderDefault;
+    g_fused_order.store(m, std::memory_order_relaxed);
+  }
+  return m;
+}
+
 // hop 0 (a: seeds / groups, k, outputs) and hop 1 (k1, out_*1) as one launch; the caller checked plan_fuse01
 // commit (RING, optional): the previous batch's deferred commit, run by ceil(m / 4) workgroups behind the riders
 template <bool RING>
@@ -2672,10 +2779,11 @@ static int launch_fused01(LookupArgs a, hipStream_t stream, hipEvent_t ev_start,
   a.side_stage = side_stage;
   a.commit_blocks = (RING && commit) ? (unsigned)((c.m + 3) / 4) : 0u;
   a.fused_rows = fused_rows_per_wave(a.k);
+  a.ord = fused_order_make(a.S, a.k, a.grp.groups, a.grp.end, a.fused_rows > 0 ? 0 : fused_order_mode());
   const int kmax = a.k > a.k1 ? a.k : a.k1;
   const int vec = prepare_lookup(a, a.out_x1, kmax);
   if (vec < 0) return vec;
-  const int waves_per_block = 4;
+  const int waves_per_block = kFusedWaves;
   const long long runs = a.fused_rows > 0 ? (a.k + a.fused_rows - 1) / a.fused_rows : a.k;  // hop-1 waves per hop-0 seed
   const long long waves = a.S + a.S * runs;
   long long blocks = (waves + waves_per_block - 1) / waves_per_block;
@@ -3519,6 +3627,28 @@ extern "C" int32_t tgmx_set_fused_rows(int32_t rows) {
   const int old = fused_rows_per_wave(1 << 30);
   g_fused_rows.store(rows < 0 ? -1 : rows, std::memory_order_relaxed);
   return old;
+}
+
+extern "C" int32_t tgmx_set_fused_order(int32_t mode) {
+  const int old = fused_order_mode();
+  g_fused_order.store((mode < 0 || mode > 2) ? -1 : mode, std::memory_order_relaxed);
+  return old;
+}
+
+extern "C" int32_t tgmx_fused_row_order(int64_t S0, int32_t k0, int32_t groups, const int64_t* group_end, int32_t mode, int64_t* out_idx) {
+  TGMX_REQUIRE(S0 >= 0 && k0 > 0 && out_idx, "fused_row_order: bad sizes or no output");
+  TGMX_REQUIRE(mode >= 0 && mode <= 2, "fused_row_order: mode is 0, 1 or 2");
+  TGMX_REQUIRE(groups >= 0 && groups <= TGMX_MAX_SEED_GROUPS && (groups == 0 || group_end), "fused_row_order: bad seed groups");
+  long long end[TGMX_MAX_SEED_GROUPS] = {};
+  for (int g = 0; g < groups; ++g) end[g] = group_end[g];
+  const FusedOrder o = fused_order_make(S0, k0, groups, end, mode);
+  for (long long i = 0; i < S0 * k0; ++i) {
+    long long s0;
+    int j;
+    fused_row_of(o, i, k0, S0, s0, j);
+    out_idx[i] = s0 * k0 + j;
+  }
+  return TGMX_OK;
 }
 
 extern "C" int tgmx_defer_flush(tgmx_defer_t* d, tgmx_stream_t stream) {
