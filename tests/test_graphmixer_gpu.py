@@ -2,6 +2,7 @@
 events, ties, self loops, repeated seeds, the last partial batch, splits, new epochs), MLPMixer and GraphMixerEncoder within the float
 bar, bit-identity of the native call, the training path's gradients and checkpoint loading."""
 import io
+import warnings
 from types import SimpleNamespace
 
 import numpy as np
@@ -267,3 +268,60 @@ def test_training_path_gradients():
             assert gr.rel_err(p.grad, sd[n].grad) < BAR, n
     with torch.no_grad():  # the same weights through the native inference call
         assert gr.rel_err(enc.eval()(b, node_feat), zr) < BAR
+
+
+def _composed_spy(monkeypatch, module, took):
+    torch_fwd = module._torch_forward
+    monkeypatch.setattr(module, '_torch_forward', lambda *a, **k: took.append('composed') or torch_fwd(*a, **k))
+
+
+@pytest.mark.parametrize('C,path', [(627, ['token']), (628, ['token', 'composed'])])
+def test_mlp_mixer_at_the_edge_of_the_lds_envelope(C, path, monkeypatch):
+    """tgmx_mixer_token keeps a seed's tile in 64 KiB of LDS: 4 * (K C + (K + Ht) * 128) bytes.  K = 20, Ht = 10: C = 627 (16 380 floats) is
+    native, C = 628 answers TGMX_E_UNSUPPORTED and the eval-mode forward is the composed torch path -- it returns, within the bar."""
+    from tgm_amd.nn import MLPMixer
+    from tgm_amd.nn import mlp_mixer as mod
+
+    torch.manual_seed(C)
+    m = MLPMixer(20, C).to(DEV).eval()
+    took = []
+    token_block = mod.token_block
+    monkeypatch.setattr(mod, 'token_block', lambda *a, **k: took.append('token') or token_block(*a, **k))
+    _composed_spy(monkeypatch, m, took)
+    with torch.no_grad():
+        for p in m.parameters():
+            p.add_(0.1 * torch.randn_like(p))
+        x = torch.randn(3, 20, C, device=DEV) * 1.5
+        with warnings.catch_warnings(record=True) as caught:
+            warnings.simplefilter('always')
+            y = m(x)
+    assert took == path
+    said = [w for w in caught if issubclass(w.category, RuntimeWarning) and 'not natively' in str(w.message)]
+    assert len(said) == (1 if 'composed' in path else 0)  # the hand-over is not silent, and the native path says nothing
+    assert y.shape == x.shape and not y.requires_grad
+    sd = {k: v.cpu().double() for k, v in m.state_dict().items()}
+    assert gr.rel_err(y, gr.mixer_forward(sd, '', x.cpu().double())) < BAR
+
+
+@pytest.mark.parametrize('launches', [False, True], ids=['one_call', 'launches'])
+def test_encoder_outside_the_lds_envelope_takes_the_composed_path(launches, monkeypatch):
+    """num_tokens = 64 at edge_dim = 172: 23 296 floats of LDS per seed against 16 384.  The eval-mode encoder returns what the composed
+    path computes (both the one-call forward and its launch-by-launch twin hand over), within the bar against the restatement."""
+    from tgm_amd.nn import GraphMixerEncoder
+
+    dims = dict(num_tokens=64, edge_dim=172, time_dim=8, node_dim=4, embed_dim=6)
+    torch.manual_seed(2)
+    _, batches = sampled_batches(dims, E=600, bs=50)
+    b = batches[-2]
+    assert int((b.nbr_nids[0] != -1).sum()) > 0
+    enc = GraphMixerEncoder(**dims).to(DEV).eval()
+    node_feat = torch.randn(400, dims['node_dim'], device=DEV)
+    took = []
+    _composed_spy(monkeypatch, enc, took)
+    if launches:
+        monkeypatch.setenv('TGMX_GRAPHMIXER_PY', '1')
+    with torch.no_grad(), pytest.warns(RuntimeWarning, match='not natively'):  # the hand-over is not silent
+        z = enc(b, node_feat)
+    assert took == ['composed']
+    assert z.shape == (3 * b.edge_src.numel(), dims['embed_dim']) and not z.requires_grad
+    assert gr.rel_err(z, restated_z(enc, b, node_feat)) < BAR

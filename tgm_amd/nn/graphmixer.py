@@ -12,6 +12,10 @@ the seeds ``edge_src, edge_dst, neg`` and the outputs of ``TimeGapNeighborHook``
 
 Inference (no gradient needed, no active dropout) is ONE native call, ``tgmx_graphmixer_forward``: the launches of ``_forward_launches``
 in the same order (identical results), the argument block cached against the parameters' versions, the scratch kept between batches.
+The native envelope is ``tgmx_mixer_token``'s: a seed's tile of ``4 * (K D + (K + Ht) * 128)`` bytes (K = num_tokens, D = edge_dim,
+Ht = int(token_dim_expansion * K)) fits 64 KiB of LDS.  Outside it (num_tokens = 64 at edge_dim = 172, say) the call answers
+``TGMX_E_UNSUPPORTED`` and inference is the composed torch arithmetic of the training path, under ``torch.no_grad()`` (a
+``RuntimeWarning`` says so, once per module).
 Training (gradients enabled, or train mode with dropout > 0) is NOT native: the reference arithmetic composed from torch ops on the device
 under autograd, with the same parameters.  A native backward is future work.  CPU tensors raise ``NativeLibraryError``.
 """
@@ -28,9 +32,9 @@ from torch import Tensor
 from .. import _native
 from ..constants import PADDED_NODE_ID
 from . import _ops
-from ._fwd_plumbing import cached_block, carve_scratch, fill_mixer_layers, i32, i64, needs_torch, up4
+from ._fwd_plumbing import Unsupported, cached_block, carve_scratch, check_supported, fill_mixer_layers, i32, i64, needs_torch, up4
 from ._paramver import TransientCaches
-from .mlp_mixer import MLPMixer, sgemm_ep, token_block
+from .mlp_mixer import MLPMixer, sgemm_ep, token_block, warn_composed
 from .time_encoding import Time2Vec
 
 
@@ -92,9 +96,14 @@ class GraphMixerEncoder(TransientCaches, nn.Module):
             return self._torch_forward(a)
         for m in self.mlp_mixers:
             m._check_native()
-        if os.environ.get('TGMX_GRAPHMIXER_PY') is not None:  # A/B: the same launches composed from Python, one ctypes call each
-            return self._forward_launches(a)
-        return self._forward_native(a)
+        try:
+            if os.environ.get('TGMX_GRAPHMIXER_PY') is not None:  # A/B: the same launches composed from Python, one ctypes call each
+                return self._forward_launches(a)
+            return self._forward_native(a)
+        except Unsupported as e:  # a seed's [num_tokens, edge_dim] tile does not fit tgmx_mixer_token's LDS: compose
+            warn_composed(self, 'GraphMixerEncoder', str(e))
+            with torch.no_grad():
+                return self._torch_forward(a)
 
     # -- training: torch ops under autograd (not native) ---------------------------------------------------------------------------------
     def _torch_forward(self, a: dict) -> Tensor:
@@ -192,5 +201,5 @@ class GraphMixerEncoder(TransientCaches, nn.Module):
         blk.x0, blk.z, blk.z1, blk.y, blk.h, blk.cat = x0.data_ptr(), z.data_ptr(), z1.data_ptr(), y.data_ptr(), h.data_ptr(), cat.data_ptr()
         blk.ldx0, blk.ldz, blk.ldh, blk.ldcat = d['ldx0'], d['ldz'], d['ldh'], d['ldcat']
         blk.out = out.data_ptr()
-        _native.check(_native.load().tgmx_graphmixer_forward(ctypes.byref(blk), _native.stream_ptr()), 'tgmx_graphmixer_forward')
+        check_supported(_native.load().tgmx_graphmixer_forward(ctypes.byref(blk), _native.stream_ptr()), 'tgmx_graphmixer_forward')
         return out

@@ -1,14 +1,19 @@
 """``FeedForwardNet`` / ``MLPMixer`` (tgm/nn/modules/mlp_mixer.py; same constructors and parameter names: ``token_norm``,
 ``token_feedforward.ffn.{0,3}``, ``channel_norm``, ``channel_feedforward.ffn.{0,3}``) on HIP kernels.
 
-Inference (no gradient needed, and no active dropout) runs natively: ``tgmx_mixer_token`` does the whole token-mixing block of a seed --
-LayerNorm over the K tokens, Linear K -> int(f_t K), exact-erf GELU, Linear -> K, residual -- and also writes the channel LayerNorm of
-its result; the channel FFN is two exact-fp32 MFMA GEMMs with a GELU and a residual epilogue (``tgmx_sgemm_nt_ep``, ``csrc/dense.hip``).
+Inference (no gradient needed, and no active dropout) runs natively inside the token kernel's envelope: ``tgmx_mixer_token`` does the
+whole token-mixing block of a seed -- LayerNorm over the K tokens, Linear K -> Ht = int(f_t K), exact-erf GELU, Linear -> K, residual -- and
+also writes the channel LayerNorm of its result; the channel FFN is two exact-fp32 MFMA GEMMs with a GELU and a residual epilogue
+(``tgmx_sgemm_nt_ep``, ``csrc/dense.hip``).  The envelope: a seed's tile, ``4 * (K C + (K + Ht) * 128)`` bytes, fits 64 KiB of LDS (K = 20,
+Ht = 10: C <= 627).  Outside it the kernel answers ``TGMX_E_UNSUPPORTED`` and inference is the composed torch arithmetic below, under
+``torch.no_grad()`` (a ``RuntimeWarning`` says so, once per module).
 
 Training (gradients enabled, or train mode with dropout > 0) is NOT native: it composes the reference arithmetic from torch ops on the
 device under autograd, with the same parameters.  A native backward is future work.  CPU tensors raise ``NativeLibraryError``.
 """
 from __future__ import annotations
+
+import warnings
 
 import torch
 import torch.nn as nn
@@ -17,7 +22,7 @@ from torch import Tensor
 
 from .. import _native
 from . import _ops
-from ._fwd_plumbing import needs_torch
+from ._fwd_plumbing import Unsupported, check_supported, needs_torch
 
 
 class FeedForwardNet(nn.Module):
@@ -55,12 +60,20 @@ def sgemm_ep(A: Tensor, B: Tensor, out: Tensor, bias=None, act: int = 0, res=Non
     return out
 
 
+def warn_composed(module: nn.Module, who: str, why: str) -> None:
+    """Once per module: inference left the native path."""
+    if not module.__dict__.get('_tgmx_warned'):
+        module.__dict__['_tgmx_warned'] = True
+        warnings.warn(f'tgm_amd {who}: inference runs as torch ops on the device, not natively: {why}', RuntimeWarning, stacklevel=3)
+
+
 def token_block(mixer: 'MLPMixer', x: Tensor, ldx: int, S: int, z1: Tensor, y: Tensor, ldo: int) -> None:
-    """``tgmx_mixer_token`` with ``mixer``'s token FFN and channel LayerNorm (x, z1, y: device pointers' owners, rows of ldx / ldo floats)."""
+    """``tgmx_mixer_token`` with ``mixer``'s token FFN and channel LayerNorm (x, z1, y: device pointers' owners, rows of ldx / ldo floats).
+    Raises ``Unsupported`` (nothing launched, z1 / y untouched) when the seed's tile does not fit the kernel's 64 KiB of LDS."""
     lib = _native.load()
     tn, cn, tf = mixer.token_norm, mixer.channel_norm, mixer.token_feedforward.ffn
     K, C = mixer.num_tokens, mixer.num_channels
-    _native.check(
+    check_supported(
         lib.tgmx_mixer_token(x.data_ptr(), ldx, S, K, C, tn.weight.data_ptr(), tn.bias.data_ptr(), tf[0].weight.data_ptr(), tf[0].bias.data_ptr(),
                              tf[0].out_features, tf[3].weight.data_ptr(), tf[3].bias.data_ptr(), cn.weight.data_ptr(), cn.bias.data_ptr(),
                              float(tn.eps), z1.data_ptr(), y.data_ptr(), ldo, _native.stream_ptr()),
@@ -72,8 +85,9 @@ class MLPMixer(nn.Module):
     r"""MLP-Mixer block (https://openreview.net/forum?id=ayPPc0SyLv1, Eq. 6): token mixing over the K tokens of each channel, then
     channel mixing over the C channels of each token, each as ``x + FFN(LayerNorm(x))``.
 
-    Input / output: [B, K, C] = [batch, num_tokens, num_channels].  Inference is native (see the module docstring); with gradients
-    enabled, or in train mode with dropout > 0, the forward is the reference arithmetic composed from torch ops on the device (NOT native).
+    Input / output: [B, K, C] = [batch, num_tokens, num_channels].  Inference is native inside the token kernel's LDS envelope (see the
+    module docstring; composed outside it); with gradients enabled, or in train mode with dropout > 0, the forward is the reference
+    arithmetic composed from torch ops on the device (NOT native).
     """
 
     def __init__(self, num_tokens: int, num_channels: int, token_dim_expansion_factor: float = 0.5, channel_dim_expansion_factor: float = 4.0,
@@ -117,7 +131,12 @@ class MLPMixer(nn.Module):
         R = B * K
         f32 = dict(dtype=torch.float32, device=x.device)
         z1, y = torch.empty((R, C), **f32), torch.empty((R, C), **f32)
-        token_block(self, x, C, B, z1, y, C)
+        try:
+            token_block(self, x, C, B, z1, y, C)
+        except Unsupported as e:  # the seed's tile does not fit tgmx_mixer_token's LDS: compose
+            warn_composed(self, 'MLPMixer', str(e))
+            with torch.no_grad():
+                return self._torch_forward(x)
         cf = self.channel_feedforward.ffn
         h = torch.empty((R, cf[0].out_features), **f32)
         sgemm_ep(y, cf[0].weight.detach(), h, cf[0].bias.detach(), act=2)
