@@ -189,6 +189,7 @@ T2V_AXES = dict(T=[1, 64, 65, 100], MD=[(1, 0), (100, 172)])
 AGGR_CASES = [(mean, T, 1, 0) for T in T2V_AXES['T'] for mean in (0, 1)] + [(mean, T, 100, 172) for T in (1, 100) for mean in (0, 1)]
 AGGR_ROWS = 23
 AGGR_LOG = 4096
+AGGR_NODES = 40
 UNIX = 1_700_000_000
 # row kinds of aggr_case: name -> row
 AGGR_ROW = dict(empty=0, one=1, src_only=2, dst_only=3, dst_below_src=4, total64=5, total65=6, total130=7, max_first=8, max_last=9,
@@ -214,7 +215,10 @@ def aggr_case(T, M, D, seed=0):
         tw[0] = 1); 16 destination window only, 70 events (second trip with c0 == 0); 17 .. 21 random counts 0 .. 20 per
         window; 22 no events (in the last, ragged group of four).
 
-    d_aggr [R, 2M + D + T] holds NaN outside its Time2Vec columns.  Returns a dict of CPU tensors."""
+    d_aggr [R, 2M + D + T] holds NaN outside its Time2Vec columns.  The forward kernel's further inputs (oracle/tgn_fwd_ref.py) come
+    from a generator of their own, so the tensors above are what they were without them: N = 40 nodes, ``nodes`` [R] distinct node
+    ids in random order (row r is node nodes[r]), ``memory`` [N, M], ``log_other`` [4096] in [0, N), ``log_raw`` [4096, D].
+    Returns a dict of CPU tensors."""
     g = torch.Generator().manual_seed(1000 * seed + 31 * T + 7 * M + D)
     R = AGGR_ROWS
     log_t = UNIX + torch.randint(0, 1_000_000, (AGGR_LOG,), generator=g)
@@ -253,8 +257,13 @@ def aggr_case(T, M, D, seed=0):
     W, toff = 2 * M + D + T, 2 * M + D
     d_aggr = torch.full((R, W), NAN)
     d_aggr[:, toff:toff + T] = torch.randn(R, T, generator=g)
+    g2 = torch.Generator().manual_seed(77_000_003 + 1000 * seed + 31 * T + 7 * M + D)
+    nodes = torch.randperm(AGGR_NODES, generator=g2)[:R].to(torch.int32)
+    memory = torch.randn(AGGR_NODES, M, generator=g2)
+    log_other = torch.randint(0, AGGR_NODES, (AGGR_LOG,), generator=g2).to(torch.int32)
+    log_raw = torch.randn(AGGR_LOG, D, generator=g2)
     return dict(lo_s=lo[0].clone(), cnt_s=cnt[0].clone(), lo_d=lo[1].clone(), cnt_d=cnt[1].clone(), lu=lu, log_t=log_t, tw=tw, tb=tb,
-                d_aggr=d_aggr, R=R, T=T, M=M, D=D, walk=walk)
+                d_aggr=d_aggr, R=R, T=T, M=M, D=D, walk=walk, N=AGGR_NODES, nodes=nodes, memory=memory, log_other=log_other, log_raw=log_raw)
 
 
 def aggr_args(c, mean):
@@ -268,7 +277,8 @@ EDGE_BIG_CASE = (41944, 100, 0)  # E * T = 16384 * 256 + 96: the block cap and a
 def edge_case(E, T, D, seed=0):
     """lu_local has 1 row (E <= 5) or 17, src repeats rows; lu and t are near 1.7e9 with lu[src] - t within +-40 (float32 spacing
     there is 128: 'float first' is off by up to 128).  E >= 5: edge 0 has dt == 0, edge 1 dt = 2^31 - 3, edge 2 dt = -(2^31 - 7).
-    d_attr [E, T + D] holds NaN in its D message columns."""
+    d_attr [E, T + D] holds NaN in its D message columns.  ``msg`` [E, D], the forward kernel's further input, comes from a generator
+    of its own (the tensors above are what they were without it)."""
     g = torch.Generator().manual_seed(1000 * seed + 131 * E + 7 * T + D)
     L = 1 if E <= 5 else 17
     lu = UNIX + torch.randint(0, 1_000_000, (L,), generator=g)
@@ -280,7 +290,8 @@ def edge_case(E, T, D, seed=0):
     tw, tb = time2vec_params(T, g)
     d_attr = torch.full((E, T + D), NAN)
     d_attr[:, :T] = torch.randn(E, T, generator=g)
-    return dict(lu_local=lu, src=src, t=t, tw=tw, tb=tb, d_attr=d_attr, D=D, T=T, E=E)
+    msg = torch.randn(E, D, generator=torch.Generator().manual_seed(77_000_003 + 1000 * seed + 131 * E + 7 * T + D))
+    return dict(lu_local=lu, src=src, t=t, tw=tw, tb=tb, d_attr=d_attr, D=D, T=T, E=E, msg=msg)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
