@@ -56,7 +56,7 @@ int tgmx_version(void);
 /* sizeof of the argument structs as this library was compiled (a binding checks its own mirror against it):
  * 0 tgmx_adj_t, 1 tgmx_recency_step_t, 2 tgmx_tgat_layer_t, 3 tgmx_tgat_model_t, 4 tgmx_tgat_hop_t, 5 tgmx_tgat_layout_t,
  * 6 tgmx_pipeline_t, 7 tgmx_pipeline_out_t, 8 tgmx_dropout_t, 9 tgmx_tgn_memory_fwd_t, 10 tgmx_tconv_fwd_t, 11 tgmx_pipeline_post_t,
- * 12 tgmx_tgn_step_t, ..., 22 tgmx_ctan_fwd_t, 24 tgmx_gclstm_fwd_t, 26 tgmx_roland_fwd_t, 27 tgmx_decoder_fwd_t (23 and 25 are reserved and answer 0: tests/test_ctan_cpu.py and
+ * 12 tgmx_tgn_step_t, ..., 22 tgmx_ctan_fwd_t, 24 tgmx_gclstm_fwd_t, 26 tgmx_roland_fwd_t, 27 tgmx_decoder_fwd_t, 35 tgmx_ctan_bwd_t (23 and 25 are reserved and answer 0: tests/test_ctan_cpu.py and
  * tests/test_gclstm_cpu.py pin them), 28 tgmx_an_batch_t, 29 tgmx_node_analytics_t, 30 tgmx_decoder_train_t, 32 tgmx_gclstm_bwd_t (31 is
  * reserved the same way: tests/test_decoder_train_cpu.py) */
 size_t tgmx_abi_sizeof(int32_t which);
@@ -1339,7 +1339,7 @@ int tgmx_tcomem_query(const tgmx_tcomem_t* tc, const void* src, int32_t src_is64
 /* Moves the pair counts of `from` into `to` (a new, empty table of at least twice the capacity).  *kept (device) = pairs moved. */
 int tgmx_tcomem_rehash(const tgmx_tcomem_t* from, const tgmx_tcomem_t* to, int64_t* kept, tgmx_stream_t stream);
 
-/* ---- CTAN (the reference's tgm/nn/encoder/ctan.py): memory update, wide-head attention, the encoder's inference forward ---- */
+/* ---- CTAN (the reference's tgm/nn/encoder/ctan.py): memory update, wide-head attention, the encoder's forward and its backward ---- */
 
 /* CTANMemory.update_state (ctan.py:128-147) with LastAggregator: over the positions p in [0, 2B) of cat[src, pos_dst] (time t[p mod B]),
  * a node's memory row becomes row p* of cat[src_emb, pos_dst_emb], p* = the LOWEST p among the node's positions with the largest
@@ -1368,7 +1368,10 @@ int tgmx_ctan_attend(const float* q, const float* k, const float* v, const float
  *   / std_delta_t in float32, eproj = edge_attr W_edge^T, the edges grouped by tgt (tgmx_segment_sort);  num_iters times: qkvs = x W4^T + b4
  *   (W4 = [W_query, W_key, W_value, A], A = W - W^T - gamma I; b4 = [b_query, b_key, b_value, bias]: one batched GEMM), then
  *   tgmx_ctan_attend in mode 1 (mode 2 on the last iteration, into out).
- * Every buffer is the caller's.  src / tgt out of [0, U) are clamped and raise TGMX_ST_EDGE_RANGE in *status. */
+ * Every buffer is the caller's.  src / tgt out of [0, U) are clamped and raise TGMX_ST_EDGE_RANGE in *status.
+ * x_save (appended; NULL = the behaviour above, x updated in place): the saving forward of the training path.  [max(num_iters, 1), U, M]:
+ * slot 0 receives enc_x(node_x), iteration `it` reads slot `it` and writes slot `it + 1` (the last one writes `out` only); `x` is then
+ * not touched and may be NULL.  The same kernels in the same order: `out` has the bits of the call without x_save. */
 typedef struct tgmx_ctan_fwd {
   const float* node_x; int64_t U; int32_t in_ch, M;    /* [U, in_ch], in_ch = M + node_dim */
   const int64_t* last_update;                          /* [U] */
@@ -1381,8 +1384,79 @@ typedef struct tgmx_ctan_fwd {
   int64_t* src_ok; int64_t* order; int64_t* seg_lo; int64_t* seg_hi; /* [E], [E], [U], [U] */
   void* sort_ws; size_t sort_ws_bytes; int32_t* status;
   float* out;                                          /* [U, M] */
+  float* x_save;                                       /* [max(num_iters, 1), U, M] or NULL */
 } tgmx_ctan_fwd_t;
 int tgmx_ctan_forward(const tgmx_ctan_fwd_t* args, tgmx_stream_t stream);
+
+/* ---- CTAN training: the backward of tgmx_ctan_forward (csrc/ctan_bwd.hip).  No float atomics, every sum in a fixed order. ---- */
+
+/* The final tanh: gx[r, c] = g[r, c] (1 - out[r, c]^2);  g [U, M] with leading dimension ldg, out and gx [U, M] dense. */
+int tgmx_ctan_out_backward(const float* g, int64_t ldg, const float* out, int64_t U, int32_t M, float* gx, tgmx_stream_t stream);
+
+/* The target pass of one AntiSymmetricConv iteration, C <= 256, one workgroup per target i (lane ownership, blocks of four and the four-wave
+ * split above 16 edges as tgmx_ctan_attend).  q, k, v, h4 [U, C], eproj, order, src, seg_lo, seg_hi: what tgmx_ctan_attend read (h4 = x A^T
+ * + bias, before the attention); seg_lo NULL: no edges at all.  Walk 1 recomputes the row's softmax state (m, l) and phi as the forward
+ * does; then, with z_i = h4_i + phi_i,
+ *   dz_i = epsilon gx_i (1 - tanh^2 z_i),   delta_i = dz_i . phi_i,
+ * and walk 2, per incoming edge e (source j) in ascending edge id:
+ *   alpha_e = exp(scale q_i.(k_j + ep_e) - m) / l,   dalpha_e = dz_i . (v_j + ep_e),   s_e = scale alpha_e (dalpha_e - delta_i),
+ *   dq_i = sum_e s_e (k_j + ep_e)   (merged in wave order),
+ *   d_eproj[e] (+)= s_e q_i + alpha_e dz_i   (d_eproj NULL: not wanted; accumulate != 0 adds to the row: every edge has one target, so
+ *   its owner does a plain read-modify-write),   alpha[e], s[e] and etgt[e] = i.
+ * d4 [U, 4C]: dq_i goes to columns [0, C), dz_i to [3C, 4C) (the source pass fills the two blocks between).  A target without incoming
+ * edges gets dq = 0 and dz from z = h4. */
+int tgmx_ctan_attend_backward(const float* q, const float* k, const float* v, const float* h4, const float* eproj, const int64_t* order,
+                              const int64_t* src, const int64_t* seg_lo, const int64_t* seg_hi, int64_t U, int32_t C, float scale, float epsilon,
+                              const float* gx, float* d4, float* alpha, float* s, int32_t* etgt, float* d_eproj, int32_t accumulate,
+                              tgmx_stream_t stream);
+
+/* The source pass: one workgroup per source j over the edges grouped by source (order_s, sseg_lo, sseg_hi: tgmx_segment_sort on src, each
+ * segment in ascending edge id):
+ *   dk_j = sum_e s[e] q[etgt[e]],   dv_j = sum_e alpha[e] dz[etgt[e]]     (dz = d4's columns [3C, 4C)),
+ * written to d4's columns [C, 2C) and [2C, 3C); zero rows for a source without outgoing edges.  More than 16 edges: split over the four
+ * waves and merged in wave order.  sseg_lo NULL: no edges.  This replaces the float atomics of tgmx_tconv_attend_backward. */
+int tgmx_ctan_source_backward(const float* q, float* d4, const int64_t* order_s, const int32_t* etgt, const int64_t* sseg_lo,
+                              const int64_t* sseg_hi, const float* alpha, const float* s, int64_t U, int32_t C, tgmx_stream_t stream);
+
+/* The time encoder's backward, per edge: rel_e = (float(|last_update[src[e]] - t[e]|) - mean) / std in float32 as the forward computes it,
+ *   gs = -sin(rel_e tw[c] + tb[c]) d_attr[e, c];   part[e, c] = gs rel_e  (d tw),   part[e, T + c] = gs  (d tb);
+ * d_attr [E, T] with leading dimension ldd (the gradient at the time columns of edge_attr), part [E, 2T]; sum the rows with tgmx_colsum.
+ * src[e] in [0, U) (the forward's src_ok). */
+int tgmx_ctan_edge_attr_backward(const int64_t* last_update, const int64_t* src, const int64_t* t, const float* tw, const float* tb,
+                                 const float* d_attr, int64_t ldd, int32_t T, int64_t E, float mean, float std, float* part,
+                                 tgmx_stream_t stream);
+
+/* A = W - W^T - gamma I:  dW[r, c] = dA[r, c] - dA[c, r];  both [M, M] dense, dW must not alias dA. */
+int tgmx_ctan_antisym_grad(const float* dA, int32_t M, float* dW, tgmx_stream_t stream);
+
+/* The backward of tgmx_ctan_forward as ONE call (tgmx_abi_sizeof(35)), M <= 256.  x_save / out / edge_attr / eproj / src_ok / order /
+ * seg_lo / seg_hi: what the saving forward wrote (buffers of that call).  With g = dL/dout:
+ *   gx = g (1 - out^2);  the edges grouped by source once (tgmx_segment_sort on src_ok);
+ *   it = num_iters - 1 .. 0:  qkvs = x_it W4^T + b4 (the forward's GEMM) -> tgmx_ctan_attend_backward -> tgmx_ctan_source_backward ->
+ *     d_W4[b] (+)= d_b^T x_it (one batched tgmx_sgemm_tn), d_b4 (+)= colsum(d4) -> gx <- gx + d4 W4T^T (tgmx_sgemm_nt_ep, res = gx);
+ *   d_W = d_W4[3] - d_W4[3]^T;  d_Wx = gx^T node_x, d_bx = colsum(gx), d_node_x = gx WxT^T;  d_Wedge = d_eproj^T edge_attr;
+ *   d_time = [d tw | d tb] = colsum(tgmx_ctan_edge_attr_backward(d_eproj WeT^T)).
+ * W4T [M, 4M] = W4 viewed as [4M, M], transposed;  WxT [in_ch, M] = W_x^T (only for d_node_x);  WeT [T, M] = W_edge[:, D:]^T (only for
+ * d_time).  A NULL output is not wanted and its work is skipped (d_W needs d_W4).  num_iters = 0 or E = 0: the gradients that no path
+ * reaches are zeroed.  U = 0 returns at once. */
+typedef struct tgmx_ctan_bwd {
+  int64_t U, E; int32_t in_ch, M, D, T, num_iters; float epsilon, mean_delta_t, std_delta_t;
+  const float* g; int64_t ldg;                         /* dL/dout [U, M] */
+  const float* out; const float* x_save;               /* [U, M], [max(num_iters, 1), U, M] */
+  const float* node_x;                                 /* [U, in_ch] (d_Wx) */
+  const int64_t* last_update; const int64_t* t;        /* [U], [E] (d_time) */
+  const float* tw; const float* tb;                    /* [T], [T] (d_time) */
+  const float* W4; const float* b4;                    /* [4, M, M], [4, M]: the forward's */
+  const float* W4T; const float* WxT; const float* WeT; /* [M, 4M], [in_ch, M], [T, M] */
+  const float* edge_attr; const float* eproj;          /* [E, D + T], [E, M] */
+  const int64_t* src_ok; const int64_t* order; const int64_t* seg_lo; const int64_t* seg_hi;
+  float* d_W4; float* d_b4; float* d_W;                /* [4, M, M], [4, M], [M, M] */
+  float* d_Wx; float* d_bx; float* d_node_x;           /* [M, in_ch], [M], [U, in_ch] */
+  float* d_Wedge; float* d_time;                       /* [M, D + T], [2T] */
+  void* workspace; size_t workspace_bytes;
+} tgmx_ctan_bwd_t;
+size_t tgmx_ctan_backward_workspace_bytes(const tgmx_ctan_bwd_t* args);
+int tgmx_ctan_backward(const tgmx_ctan_bwd_t* args, tgmx_stream_t stream);
 
 /* ---- ChebConv / GCLSTM (the reference's tgm/nn/encoder/gclstm.py; ChebConv from its published PyG definition): the scaled Laplacian of a
  * snapshot as a CSR by destination, a gather SpMM over it, and the cell's inference forward as one call ---- */

@@ -554,9 +554,34 @@ class CtanFwd(ctypes.Structure):
         ('src_ok', c_void_p), ('order', c_void_p), ('seg_lo', c_void_p), ('seg_hi', c_void_p),
         ('sort_ws', c_void_p), ('sort_ws_bytes', c_size_t), ('status', c_void_p),
         ('out', c_void_p),
+        ('x_save', c_void_p),
     ]  # fmt: skip
 
 
+class CtanBwd(ctypes.Structure):
+    """tgmx_ctan_bwd_t (include/tgm_amd.h)."""
+
+    _fields_ = [
+        ('U', c_int64), ('E', c_int64), ('in_ch', c_int32), ('M', c_int32), ('D', c_int32), ('T', c_int32), ('num_iters', c_int32),
+        ('epsilon', ctypes.c_float), ('mean_delta_t', ctypes.c_float), ('std_delta_t', ctypes.c_float),
+        ('g', c_void_p), ('ldg', c_int64), ('out', c_void_p), ('x_save', c_void_p), ('node_x', c_void_p),
+        ('last_update', c_void_p), ('t', c_void_p), ('tw', c_void_p), ('tb', c_void_p),
+        ('W4', c_void_p), ('b4', c_void_p), ('W4T', c_void_p), ('WxT', c_void_p), ('WeT', c_void_p),
+        ('edge_attr', c_void_p), ('eproj', c_void_p), ('src_ok', c_void_p), ('order', c_void_p), ('seg_lo', c_void_p), ('seg_hi', c_void_p),
+        ('d_W4', c_void_p), ('d_b4', c_void_p), ('d_W', c_void_p), ('d_Wx', c_void_p), ('d_bx', c_void_p), ('d_node_x', c_void_p),
+        ('d_Wedge', c_void_p), ('d_time', c_void_p),
+        ('workspace', c_void_p), ('workspace_bytes', c_size_t),
+    ]  # fmt: skip
+
+
+SIGNATURES['tgmx_ctan_out_backward'] = (c_int32, [_P, c_int64, _P, c_int64, c_int32, _P, _P])
+SIGNATURES['tgmx_ctan_attend_backward'] = (c_int32, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int64, c_int32, ctypes.c_float, ctypes.c_float, _P, _P, _P, _P, _P, _P,
+                                                     c_int32, _P])  # fmt: skip
+SIGNATURES['tgmx_ctan_source_backward'] = (c_int32, [_P, _P, _P, _P, _P, _P, _P, _P, c_int64, c_int32, _P])
+SIGNATURES['tgmx_ctan_edge_attr_backward'] = (c_int32, [_P, _P, _P, _P, _P, _P, c_int64, c_int32, c_int64, ctypes.c_float, ctypes.c_float, _P, _P])
+SIGNATURES['tgmx_ctan_antisym_grad'] = (c_int32, [_P, c_int32, _P, _P])
+SIGNATURES['tgmx_ctan_backward_workspace_bytes'] = (c_size_t, [ctypes.POINTER(CtanBwd)])
+SIGNATURES['tgmx_ctan_backward'] = (c_int32, [ctypes.POINTER(CtanBwd), _P])
 SIGNATURES['tgmx_ctan_memory_update'] = (c_int32, [_P, c_int32, _P, c_int32, _P, c_int64, _P, _P, c_int64, c_int32, c_int64, _P, _P, _P, _P, _P, _P])
 SIGNATURES['tgmx_ctan_attend'] = (c_int32, [_P, _P, _P, _P, _P, _P, _P, _P, c_int64, c_int32, ctypes.c_float, _P, _P, _P, ctypes.c_float, c_int32, _P])
 SIGNATURES['tgmx_ctan_forward'] = (c_int32, [ctypes.POINTER(CtanFwd), _P])

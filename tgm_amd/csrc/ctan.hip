@@ -9,6 +9,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "ctan_rows.h"
 #include "lanes.h"
 
 namespace tgmx {
@@ -131,121 +132,9 @@ __global__ __launch_bounds__(256) void ctan_edge_attr_kernel(const int64_t* __re
 //   mode 0   h4 += phi                              (what tgmx_tconv_attend leaves: for tests and A/B timing against it)
 //   mode 1   x <- x + eps tanh(h4 + phi)            (AntiSymmetricConv, h4 = x A^T + bias from the batched projection)
 //   mode 2   out = tanh(x + eps tanh(h4 + phi))     (the last iteration, with CTAN's final tanh)
+// (CtanAttendArgs, the row pieces and the walk: ctan_rows.h, shared with the backward.  x_next: mode 1 leaves x alone and writes the new
+// x there -- the saving forward keeps every iteration's x.)
 // ---------------------------------------------------------------------------------------------------------------------------------
-struct CtanAttendArgs {
-  const float *q, *k, *v;  // [U, C]
-  const float* eproj;      // [E, C], original edge order
-  const int64_t* order;    // [E] edge ids stably sorted by target
-  const int64_t* src;      // [E] source of every edge, in [0, U)
-  const int64_t* seg_lo;   // [U]
-  const int64_t* seg_hi;   // [U]
-  float* h4;               // [U, C]
-  float* x;                // [U, C] (modes 1, 2)
-  float* out;              // [U, C] (mode 2)
-  long long U;
-  int C;
-  float scale, eps;
-  int mode;
-};
-
-constexpr int kCtanShort = 16;
-constexpr int kCtanWaves = 4;
-constexpr int kCtanMaxC = 4 * kWave;
-
-template <int V>
-struct CtVec {
-  float f[V];
-};
-// the lane's piece of a row: p points at its first column, nv of its V columns exist (VEC: nv is 0 or V)
-template <int V, bool VEC>
-__device__ __forceinline__ CtVec<V> ct_load(const float* __restrict__ p, const int nv) {
-  CtVec<V> r;
-  if constexpr (VEC && V == 4) {
-    const float4 x = nv ? *reinterpret_cast<const float4*>(p) : make_float4(0.f, 0.f, 0.f, 0.f);
-    r.f[0] = x.x; r.f[1] = x.y; r.f[2] = x.z; r.f[3] = x.w;
-  } else if constexpr (VEC && V == 2) {
-    const float2 x = nv ? *reinterpret_cast<const float2*>(p) : make_float2(0.f, 0.f);
-    r.f[0] = x.x; r.f[1] = x.y;
-  } else {
-#pragma unroll
-    for (int u = 0; u < V; ++u) r.f[u] = u < nv ? p[u] : 0.f;
-  }
-  return r;
-}
-template <int V, bool VEC>
-__device__ __forceinline__ void ct_store(float* __restrict__ p, const int nv, const CtVec<V>& r) {
-  if constexpr (VEC && V == 4) {
-    if (nv) *reinterpret_cast<float4*>(p) = make_float4(r.f[0], r.f[1], r.f[2], r.f[3]);
-  } else if constexpr (VEC && V == 2) {
-    if (nv) *reinterpret_cast<float2*>(p) = make_float2(r.f[0], r.f[1]);
-  } else {
-#pragma unroll
-    for (int u = 0; u < V; ++u)
-      if (u < nv) p[u] = r.f[u];
-  }
-}
-
-template <int V>
-struct CtanWalk {
-  float m, l;
-  CtVec<V> acc;
-};
-
-// the n_here (<= 64) edges whose ids / sources lanes 0 .. n_here - 1 hold, in lane order, four at a time
-template <int V, bool VEC>
-__device__ __forceinline__ void ctan_walk_block(const CtanAttendArgs& a, const CtVec<V> q, const int nv, const int col, const int my_e, const int my_j,
-                                                const int n_here, CtanWalk<V>& st) {
-  const long long C = a.C;
-  const float* __restrict__ kp = a.k + col;
-  const float* __restrict__ vp = a.v + col;
-  const float* __restrict__ ep = a.eproj + col;
-  CtVec<V> kk[4], vv[4], ee[4], kn[4], vn[4], en[4];
-  auto request = [&](int c0, CtVec<V> (&K)[4], CtVec<V> (&Vv)[4], CtVec<V> (&E)[4]) __attribute__((always_inline)) {
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      const int sl = c0 + s < n_here ? c0 + s : n_here - 1;  // (clamped: a position past the block re-reads its last edge, not used below)
-      const long long e = __builtin_amdgcn_readlane(my_e, sl), j = __builtin_amdgcn_readlane(my_j, sl);
-      K[s] = ct_load<V, VEC>(kp + j * C, nv);
-      Vv[s] = ct_load<V, VEC>(vp + j * C, nv);
-      E[s] = ct_load<V, VEC>(ep + e * C, nv);
-    }
-  };
-  request(0, kk, vv, ee);
-  float m = st.m, l = st.l;
-  CtVec<V> acc = st.acc;
-  for (int c0 = 0; c0 < n_here; c0 += 4) {
-    const bool more = c0 + 4 < n_here;
-    if (more) request(c0 + 4, kn, vn, en);
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      if (c0 + s < n_here) {  // wave-uniform
-        float p = q.f[0] * (kk[s].f[0] + ee[s].f[0]);
-#pragma unroll
-        for (int u = 1; u < V; ++u) p = __fmaf_rn(q.f[u], kk[s].f[u] + ee[s].f[u], p);
-        p = lanes::butterfly_sum<1>(p);  // all 64 lanes (lanes past the row carry zeros)
-        const float sc = p * a.scale;
-        const float mn = sc > m ? sc : m;
-        const float corr = expf(m - mn), w = expf(sc - mn);
-#pragma unroll
-        for (int u = 0; u < V; ++u) acc.f[u] = acc.f[u] * corr + w * (vv[s].f[u] + ee[s].f[u]);
-        l = l * corr + w;
-        m = mn;
-      }
-    }
-    if (more) {
-#pragma unroll
-      for (int s = 0; s < 4; ++s) {
-        kk[s] = kn[s];
-        vv[s] = vn[s];
-        ee[s] = en[s];
-      }
-    }
-  }
-  st.m = m;
-  st.l = l;
-  st.acc = acc;
-}
-
 template <int V, bool VEC>
 __global__ __launch_bounds__(256) void ctan_attend_kernel(const CtanAttendArgs a) {
   __shared__ float s_m[kCtanWaves], s_l[kCtanWaves];
@@ -327,24 +216,24 @@ __global__ __launch_bounds__(256) void ctan_attend_kernel(const CtanAttendArgs a
     xv.f[u] = __fmaf_rn(a.eps, tanhf(r.f[u]), xv.f[u]);
     if (a.mode == 2) xv.f[u] = tanhf(xv.f[u]);
   }
-  ct_store<V, VEC>((a.mode == 2 ? a.out : a.x) + i * C + col, nv, xv);
+  ct_store<V, VEC>((a.mode == 2 ? a.out : (a.x_next ? a.x_next : a.x)) + i * C + col, nv, xv);
 }
 
 // the epilogue alone (h4 already holds x A^T + bias + phi): a head wider than kCtanMaxC, whose attention is tgmx_tconv_attend's, or no edges
-__global__ __launch_bounds__(256) void ctan_epilogue_kernel(const float* h4, float* x, float* __restrict__ out, long long total,
-                                                            float eps, int mode) {
+__global__ __launch_bounds__(256) void ctan_epilogue_kernel(const float* h4, const float* x, float* x_next, float* __restrict__ out,
+                                                            long long total, float eps, int mode) {
   const long long step = (long long)gridDim.x * blockDim.x;
   for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < total; p += step) {
     float xv = __fmaf_rn(eps, tanhf(h4[p]), x[p]);
     if (mode == 2) out[p] = tanhf(xv);
-    else x[p] = xv;
+    else x_next[p] = xv;
   }
 }
 
-static int ctan_epilogue(const float* h4, float* x, float* out, long long total, float eps, int mode, hipStream_t st) {
+static int ctan_epilogue(const float* h4, float* x, float* x_next, float* out, long long total, float eps, int mode, hipStream_t st) {
   long long blocks = (total + 255) / 256;
   if (blocks > 16384) blocks = 16384;
-  hipLaunchKernelGGL(ctan_epilogue_kernel, dim3((unsigned)blocks), dim3(256), 0, st, h4, x, out, total, eps, mode);
+  hipLaunchKernelGGL(ctan_epilogue_kernel, dim3((unsigned)blocks), dim3(256), 0, st, h4, x, x_next ? x_next : x, out, total, eps, mode);
   TGMX_CHECK_LAUNCH("ctan_epilogue");
   return TGMX_OK;
 }
@@ -354,6 +243,7 @@ static int ctan_attend_launch(const CtanAttendArgs& a, hipStream_t st) {
   uintptr_t bits = (uintptr_t)a.q | (uintptr_t)a.k | (uintptr_t)a.v | (uintptr_t)a.eproj | (uintptr_t)a.h4;
   if (a.mode) bits |= (uintptr_t)a.x;
   if (a.mode == 2) bits |= (uintptr_t)a.out;
+  if (a.mode == 1 && a.x_next) bits |= (uintptr_t)a.x_next;
   const dim3 grid((unsigned)a.U), block(256);
   if (V == 4 && a.C % 4 == 0 && (bits & 15) == 0) hipLaunchKernelGGL((ctan_attend_kernel<4, true>), grid, block, 0, st, a);
   else if (V == 4) hipLaunchKernelGGL((ctan_attend_kernel<4, false>), grid, block, 0, st, a);
@@ -387,9 +277,9 @@ extern "C" int tgmx_ctan_memory_update(const void* src, int32_t src_is64, const 
   return TGMX_OK;
 }
 
-extern "C" int tgmx_ctan_attend(const float* q, const float* k, const float* v, const float* eproj, const int64_t* order, const int64_t* src,
-                                const int64_t* seg_lo, const int64_t* seg_hi, int64_t U, int32_t C, float scale, float* h4, float* x, float* out,
-                                float epsilon, int32_t mode, tgmx_stream_t stream) {
+static int ctan_attend(const float* q, const float* k, const float* v, const float* eproj, const int64_t* order, const int64_t* src,
+                       const int64_t* seg_lo, const int64_t* seg_hi, int64_t U, int32_t C, float scale, float* h4, float* x, float* x_next, float* out,
+                       float epsilon, int32_t mode, tgmx_stream_t stream) {
   TGMX_REQUIRE(U >= 0 && C > 0 && mode >= 0 && mode <= 2, "ctan_attend: bad sizes");
   if (U == 0) return TGMX_OK;
   TGMX_REQUIRE(q && k && v && eproj && order && src && seg_lo && seg_hi && h4 && (mode == 0 || x) && (mode != 2 || out), "ctan_attend: null pointer");
@@ -397,9 +287,15 @@ extern "C" int tgmx_ctan_attend(const float* q, const float* k, const float* v, 
   if (C > kCtanMaxC) {  // wider than a wave covers with four columns a lane: the generic walk, then the epilogue on its own
     const int rc = tgmx_tconv_attend(q, k, v, eproj, order, src, seg_lo, seg_hi, U, 1, C, scale, h4, nullptr, stream);
     if (rc || mode == 0) return rc;
-    return ctan_epilogue(h4, x, out, (long long)U * C, epsilon, mode, st);
+    return ctan_epilogue(h4, x, x_next, out, (long long)U * C, epsilon, mode, st);
   }
-  return ctan_attend_launch(CtanAttendArgs{q, k, v, eproj, order, src, seg_lo, seg_hi, h4, x, out, U, C, scale, epsilon, mode}, st);
+  return ctan_attend_launch(CtanAttendArgs{q, k, v, eproj, order, src, seg_lo, seg_hi, h4, x, out, U, C, scale, epsilon, mode, x_next}, st);
+}
+
+extern "C" int tgmx_ctan_attend(const float* q, const float* k, const float* v, const float* eproj, const int64_t* order, const int64_t* src,
+                                const int64_t* seg_lo, const int64_t* seg_hi, int64_t U, int32_t C, float scale, float* h4, float* x, float* out,
+                                float epsilon, int32_t mode, tgmx_stream_t stream) {
+  return ctan_attend(q, k, v, eproj, order, src, seg_lo, seg_hi, U, C, scale, h4, x, nullptr, out, epsilon, mode, stream);
 }
 
 extern "C" int tgmx_ctan_forward(const tgmx_ctan_fwd_t* a, tgmx_stream_t stream) {
@@ -408,11 +304,14 @@ extern "C" int tgmx_ctan_forward(const tgmx_ctan_fwd_t* a, tgmx_stream_t stream)
   const int M = a->M, Wd = a->D + a->T;
   TGMX_REQUIRE(U >= 0 && E >= 0 && M > 0 && a->in_ch > 0 && a->T > 0 && a->D >= 0 && a->num_iters >= 0, "ctan_forward: bad sizes");
   if (U == 0) return TGMX_OK;
-  TGMX_REQUIRE(a->node_x && a->W_x && a->b_x && a->W4 && a->b4 && a->x && a->qkvs && a->out, "ctan_forward: null pointer");
+  TGMX_REQUIRE(a->node_x && a->W_x && a->b_x && a->W4 && a->b4 && (a->x || a->x_save) && a->qkvs && a->out, "ctan_forward: null pointer");
+  // x_save: iteration `it` reads slot `it` and writes slot `it + 1` (the same kernels, the same bits); null: one x, updated in place
+  const long long slot = a->x_save ? (long long)U * M : 0;
+  float* x0 = a->x_save ? a->x_save : a->x;
   hipStream_t st = (hipStream_t)stream;
   int rc = 0;
   // x = enc_x(node_x)
-  if ((rc = tgmx_sgemm_nt(a->node_x, a->in_ch, a->W_x, a->in_ch, a->x, M, U, M, a->in_ch, a->b_x, 0, 1, 0, 0, 0, stream))) return rc;
+  if ((rc = tgmx_sgemm_nt(a->node_x, a->in_ch, a->W_x, a->in_ch, x0, M, U, M, a->in_ch, a->b_x, 0, 1, 0, 0, 0, stream))) return rc;
   if (E) {
     // once per call: nothing of this depends on x
     TGMX_REQUIRE(a->last_update && a->src && a->tgt && a->t && (a->D == 0 || a->msg) && a->tw && a->tb && a->W_edge && a->edge_attr && a->eproj &&
@@ -430,13 +329,15 @@ extern "C" int tgmx_ctan_forward(const tgmx_ctan_fwd_t* a, tgmx_stream_t stream)
   const float scale = 1.0f / sqrtf((float)M);
   for (int it = 0; it < a->num_iters; ++it) {
     const int mode = it + 1 == a->num_iters ? 2 : 1;
+    float* x = x0 + it * slot;
+    float* x_next = a->x_save && mode == 1 ? x + slot : nullptr;
     // q | k | v | x A^T + bias: one batched problem over the stacked weights
-    if ((rc = tgmx_sgemm_nt(a->x, M, a->W4, M, a->qkvs, M, U, M, M, a->b4, 0, 4, 0, (long long)M * M, U * M, stream))) return rc;
-    if (E) rc = tgmx_ctan_attend(a->qkvs, a->qkvs + U * M, a->qkvs + 2 * U * M, a->eproj, a->order, a->src_ok, a->seg_lo, a->seg_hi, U, M, scale, h4, a->x,
-                                 a->out, a->epsilon, mode, stream);
-    else rc = ctan_epilogue(h4, a->x, a->out, (long long)U * M, a->epsilon, mode, st);
+    if ((rc = tgmx_sgemm_nt(x, M, a->W4, M, a->qkvs, M, U, M, M, a->b4, 0, 4, 0, (long long)M * M, U * M, stream))) return rc;
+    if (E) rc = ctan_attend(a->qkvs, a->qkvs + U * M, a->qkvs + 2 * U * M, a->eproj, a->order, a->src_ok, a->seg_lo, a->seg_hi, U, M, scale, h4, x, x_next,
+                            a->out, a->epsilon, mode, stream);
+    else rc = ctan_epilogue(h4, x, x_next, a->out, (long long)U * M, a->epsilon, mode, st);
     if (rc) return rc;
   }
-  if (a->num_iters == 0) return ctan_epilogue(a->x, a->x, a->out, (long long)U * M, 0.f, 2, st);  // no iteration: tanh(enc_x(node_x))
+  if (a->num_iters == 0) return ctan_epilogue(x0, x0, nullptr, a->out, (long long)U * M, 0.f, 2, st);  // no iteration: tanh(enc_x(node_x))
   return TGMX_OK;
 }

@@ -9,7 +9,11 @@ Inference (no grad): the whole forward is ONE native call (``tgmx_ctan_forward``
 ``AntiSymmetricConv``'s iterations -- the edge encoding, the ``[E, D+T] x [D+T, M]`` edge projection, the grouping of the edges by target
 -- runs once; an iteration is one batched GEMM over the stacked weights ``[W_query, W_key, W_value, A]`` (``A = W - W^T - gamma I`` in the
 slot TransformerConv's skip projection has in ``tgmx_tconv_forward``) and one attention launch whose epilogue is
-``x <- x + epsilon tanh(phi + x A^T + bias)``.  Training composes the same arithmetic from torch ops on the device (not native).
+``x <- x + epsilon tanh(phi + x A^T + bias)``.
+
+Training (``_ctan_train.py``): under gradients the forward is the same call in its saving form -- the bits of the no-grad output -- and
+``loss.backward()`` is ONE native call (``tgmx_ctan_backward``, csrc/ctan_bwd.hip): a target pass and a source pass per iteration, no float
+atomics.  Outside its envelope (``_ctan_train.in_envelope``; ``TGMX_CTAN_BWD=torch``) the call goes to :meth:`CTAN.forward_composed`.
 
 ``CTANMemory.update_state`` is two launches over the 2B positions of ``cat[src, pos_dst]`` (``tgmx_ctan_memory_update``): no
 ``unique``, no dense score matrix, no read back; out-of-range ids are skipped and reported by :meth:`CTANMemory.check`.
@@ -17,6 +21,7 @@ slot TransformerConv's skip projection has in ``tgmx_tconv_forward``) and one at
 from __future__ import annotations
 
 import math
+from types import SimpleNamespace
 from typing import Callable, Tuple
 
 import torch
@@ -24,7 +29,7 @@ import torch.nn as nn
 from torch import Tensor
 
 from .. import _native
-from . import _ops
+from . import _ctan_train, _ops
 from ._paramver import TransientCaches, param_key, param_list
 from .tgn import LastAggregator, MeanAggregator
 
@@ -114,9 +119,10 @@ class CTAN(TransientCaches, nn.Module):
         phi = _Phi(memory_dim, edge_dim + time_dim)
         self.aconv = AntiSymmetricConv(memory_dim, phi, num_iters=num_iters, epsilon=epsilon, gamma=gamma)
 
-    # ---- training: the same arithmetic from torch ops on the device ------------------------------------------------------------------
+    # ---- the same arithmetic from torch ops on the device ----------------------------------------------------------------------------
     def forward_composed(self, node_x: Tensor, last_update: Tensor, edge_index: Tensor, t: Tensor, msg: Tensor) -> Tensor:
-        """The forward composed from torch ops, with autograd: what the training path runs and what the native forward is timed against."""
+        """The forward composed from torch ops, with autograd: what training runs outside the native envelope and what the native paths are
+        timed and tested against."""
         aconv, phi = self.aconv, self.aconv.phi
         src, tgt = edge_index[0].long(), edge_index[1].long()
         rel_t = (last_update[src] - t).abs()
@@ -139,7 +145,7 @@ class CTAN(TransientCaches, nn.Module):
             x = x + aconv.epsilon * torch.tanh(h + aconv.bias)
         return torch.tanh(x)
 
-    # ---- inference: one native call -------------------------------------------------------------------------------------------------
+    # ---- one native call ------------------------------------------------------------------------------------------------------------
     def _stacked_projections(self) -> Tuple[Tensor, Tensor]:
         """[4, M, M] = [W_query, W_key, W_value, A] and [4, M] = [b_query, b_key, b_value, bias], rebuilt only when a parameter was reallocated or
         modified in place (optimizer step, load_state_dict)."""
@@ -169,9 +175,18 @@ class CTAN(TransientCaches, nn.Module):
             (PyTorch Float Tensor): Embeddings for the batch of node ids.
         """
         _native.require_device(node_x, 'CTAN: node_x')
-        lib = _native.load()
+        _native.load()
         if torch.is_grad_enabled() and (node_x.requires_grad or any(p.requires_grad for p in param_list(self))):
+            if _ctan_train.in_envelope(self, node_x, msg):
+                return _ctan_train.apply(self, node_x, last_update, edge_index, t, msg)
             return self.forward_composed(node_x, last_update, edge_index, t, msg)
+        return self._forward_native(node_x, last_update, edge_index, t, msg)[0]
+
+    def _forward_native(self, node_x: Tensor, last_update: Tensor, edge_index: Tensor, t: Tensor, msg: Tensor, own: bool = False):
+        """``(out, saved)``.  ``own``: the saving forward -- every iteration's x and what is produced once per call (edge_attr, eproj, the
+        clamped sources, the grouping by target) go to tensors that belong to THIS call and come back in ``saved``; the projections' buffer
+        and the sort workspace are dead after the forward and stay in the module's shared scratch."""
+        lib = _native.load()
         aconv, phi = self.aconv, self.aconv.phi
         x_in = _ops._f32c(node_x, 'node_x')
         dev, U, M = x_in.device, x_in.shape[0], aconv.in_channels
@@ -182,7 +197,7 @@ class CTAN(TransientCaches, nn.Module):
             raise ValueError(f'CTAN: node_x has {x_in.shape[1]} columns and msg {D}; expected {self.enc_x.in_features} and {phi.edge_dim - T}')
         out = torch.empty((U, M), dtype=torch.float32, device=dev)
         if U == 0:
-            return out
+            return out, None
         ei = edge_index.to(torch.int64)
         src, tgt = ei[0].contiguous(), ei[1].contiguous()
         lu64, t64 = last_update.to(torch.int64).contiguous(), t.to(torch.int64).contiguous()
@@ -199,6 +214,14 @@ class CTAN(TransientCaches, nn.Module):
         fl = ws['fl'] = _grow(ws.get('fl'), o_qk + 4 * U * M, torch.float32, dev)  # edge_attr | eproj | x | qkvs
         ints = ws['ints'] = _grow(ws.get('ints'), 2 * E + 2 * U, torch.int64, dev)  # src_ok | order | seg_lo | seg_hi
         self._ws = ws
+        saved = None
+        if own:
+            n_it = int(aconv.num_iters)
+            kept = torch.empty(max(o_x, 1), dtype=torch.float32, device=dev)  # edge_attr | eproj
+            kept_i = torch.empty(max(2 * E + 2 * U, 1), dtype=torch.int64, device=dev)
+            x_save = torch.empty((max(n_it, 1), U, M), dtype=torch.float32, device=dev)
+            saved = SimpleNamespace(U=U, E=E, M=M, D=D, T=T, in_ch=x_in.shape[1], num_iters=n_it, node_x=x_in, last_update=lu64, t=t64, W4=W4, b4=b4,
+                                    kept=kept, kept_i=kept_i, x_save=x_save, o_ep=o_ep)
         a = getattr(self, '_fwd_args', None)
         if a is None:
             a = self._fwd_args = _native.CtanFwd()
@@ -209,12 +232,15 @@ class CTAN(TransientCaches, nn.Module):
         a.W_x, a.b_x = self.enc_x.weight.detach().data_ptr(), self.enc_x.bias.detach().data_ptr()
         a.W4, a.b4, a.W_edge = W4.data_ptr(), b4.data_ptr(), phi.lin_edge.weight.detach().data_ptr()
         a.num_iters, a.epsilon, a.mean_delta_t, a.std_delta_t = int(aconv.num_iters), float(aconv.epsilon), float(self.mean_delta_t), float(self.std_delta_t)
-        a.edge_attr, a.eproj, a.x, a.qkvs = f0, f0 + 4 * o_ep, f0 + 4 * o_x, f0 + 4 * o_qk
+        a.x, a.qkvs, a.x_save = f0 + 4 * o_x, f0 + 4 * o_qk, None
+        if own:
+            f0, i0, a.x_save = kept.data_ptr(), kept_i.data_ptr(), x_save.data_ptr()
+        a.edge_attr, a.eproj = f0, f0 + 4 * o_ep
         a.src_ok, a.order, a.seg_lo, a.seg_hi = i0, i0 + 8 * E, i0 + 16 * E, i0 + 8 * (2 * E + U)
         a.sort_ws, a.sort_ws_bytes, a.status = ws['sort'].data_ptr(), ws['sort'].numel(), ws['status'].data_ptr()
         a.out = out.data_ptr()
         _native.check(lib.tgmx_ctan_forward(a, _native.stream_ptr()), 'tgmx_ctan_forward')
-        return out
+        return out, saved
 
     def check(self) -> None:
         """Raise if a forward saw an ``edge_index`` entry outside ``[0, U)`` (such entries are clamped on the device).  Reads the device."""
