@@ -56,7 +56,7 @@ int tgmx_version(void);
 /* sizeof of the argument structs as this library was compiled (a binding checks its own mirror against it):
  * 0 tgmx_adj_t, 1 tgmx_recency_step_t, 2 tgmx_tgat_layer_t, 3 tgmx_tgat_model_t, 4 tgmx_tgat_hop_t, 5 tgmx_tgat_layout_t,
  * 6 tgmx_pipeline_t, 7 tgmx_pipeline_out_t, 8 tgmx_dropout_t, 9 tgmx_tgn_memory_fwd_t, 10 tgmx_tconv_fwd_t, 11 tgmx_pipeline_post_t,
- * 12 tgmx_tgn_step_t, ..., 22 tgmx_ctan_fwd_t, 24 tgmx_gclstm_fwd_t, 26 tgmx_roland_fwd_t, 27 tgmx_decoder_fwd_t, 35 tgmx_ctan_bwd_t (23 and 25 are reserved and answer 0: tests/test_ctan_cpu.py and
+ * 12 tgmx_tgn_step_t, ..., 22 tgmx_ctan_fwd_t, 24 tgmx_gclstm_fwd_t, 26 tgmx_roland_fwd_t, 27 tgmx_decoder_fwd_t, 35 tgmx_ctan_bwd_t, 36 tgmx_graphmixer_bwd_t (23 and 25 are reserved and answer 0: tests/test_ctan_cpu.py and
  * tests/test_gclstm_cpu.py pin them), 28 tgmx_an_batch_t, 29 tgmx_node_analytics_t, 30 tgmx_decoder_train_t, 32 tgmx_gclstm_bwd_t (31 is
  * reserved the same way: tests/test_decoder_train_cpu.py) */
 size_t tgmx_abi_sizeof(int32_t which);
@@ -1044,6 +1044,88 @@ typedef struct tgmx_graphmixer_fwd {
   float* out;                                                                                      /* [S, E] */
 } tgmx_graphmixer_fwd_t;
 int tgmx_graphmixer_forward(const tgmx_graphmixer_fwd_t* args, tgmx_stream_t stream);
+
+/* ---- GraphMixer / MLPMixer training (csrc/mixer_bwd.hip; composed by tgm_amd/nn/_graphmixer_train.py) ---- */
+
+/* 1 when a seed's [K, C] tile with token hidden width Ht fits BOTH token kernels' LDS: the forward's 4 (K C + (K + Ht) 128) bytes and the
+ * backward's 4 (4 K + 2 Ht) 33 bytes (its narrowest pass, 32 channels; it takes 128 or 64 where they fit), 64 KiB each.  The host decides the training path with this at forward time, so a forward never saves
+ * for a backward that would then refuse. */
+int tgmx_mixer_train_supported(int32_t K, int32_t C, int32_t Ht);
+
+/* tgmx_mixer_token with the block's two dropout sites (training): drop_hidden after the GELU, element (s C + c) Ht + j of its stream;
+ * drop_out on the block's output before the residual, element (s C + c) K + k.  NULL (or p = 0) = off; both off is tgmx_mixer_token. */
+int tgmx_mixer_token_train(const float* x, int64_t ldx, int64_t S, int32_t K, int32_t C, const float* tok_g, const float* tok_b,
+                           const float* w1, const float* b1, int32_t Ht, const float* w2, const float* b2, const float* ch_g,
+                           const float* ch_b, float eps, float* z1, float* y, int64_t ldo, const tgmx_dropout_t* drop_hidden,
+                           const tgmx_dropout_t* drop_out, tgmx_stream_t stream);
+
+/* tgmx_graphmixer_forward in its saving form: the same launches in the same order, but layer l reads its input from save_z + l S K ldz
+ * and leaves its token block's output in save_z1 + l S K ldz (args->z receives the last layer's output, args->z1 is not used; x0 and cat
+ * are the caller's to keep).  drop: p, seed and the call's first stream (site s of layer l draws from stream + 4 l + s: 0 token hidden,
+ * 1 token output, 2 channel hidden [S K, Hc], 3 channel output [S K, D]; row0 unused); NULL or p = 0 = off, and the results are then the
+ * bits of tgmx_graphmixer_forward.  With dropout the channel sites are extra launches (tgmx_dropout in place, tgmx_add_cols). */
+int tgmx_graphmixer_forward_train(const tgmx_graphmixer_fwd_t* args, float* save_z, float* save_z1, const tgmx_dropout_t* drop,
+                                  tgmx_stream_t stream);
+
+/* y[r, :] = LayerNorm over the C channels of z1[r, :] (gamma / beta [C], biased variance): what tgmx_mixer_token writes as y, recomputed
+ * from the saved z1 with the same arithmetic. */
+int tgmx_mixer_channel_norm(const float* z1, int64_t ldz, int64_t R, int32_t C, const float* gamma, const float* beta, float eps, float* y,
+                            int64_t ldy, tgmx_stream_t stream);
+
+/* The channel FFN's GELU backward, in place: on entry a = the pre-activations [R, C], dh = the gradient at the (dropped) hidden
+ * activations; on return a = gelu(a) m, dh = dh m gelu'(a) with gelu'(a) = Phi(a) + a phi(a) (exact erf) and m the dropout scale of
+ * element r C + c (drop NULL or p = 0: 1). */
+int tgmx_mixer_gelu_backward(float* a, int64_t lda, float* dh, int64_t ldh, int64_t R, int32_t C, const tgmx_dropout_t* drop,
+                             tgmx_stream_t stream);
+
+/* Backward of tgmx_mixer_tail's link mean: dz[s K + k, :C] = nbr_nids[s, k] != -1 ? dcat[s, :C] / max(1, valid_s) : 0. */
+int tgmx_mixer_tail_backward(const float* dcat, int64_t ldc, const int32_t* nbr_nids, int64_t S, int32_t K, int32_t C, float* dz, int64_t ldz,
+                             tgmx_stream_t stream);
+
+/* Backward of the token block z1 = x + drop_out(W2 drop_hidden(gelu(W1 LN_K(x) + b1)) + b2): one workgroup per seed, one thread per
+ * channel; the column's LayerNorm, pre-activations and GELU are recomputed from x.  dx [S K, ldo] = the gradient at x (residual
+ * included; must not alias dz1).  rows (may be NULL: no parameter gradient wanted) [S C, ldw], ldw >= 4 K + 2 Ht, row s C + c =
+ *   [ do (K) | xn (K) | dxn (K) | dxn xhat (K) | hd (Ht) | da (Ht) | 0 ... ]
+ * with do the dropped output gradient, xn the LayerNorm's output, dxn its gradient, hd the dropped hidden activations, da the gradient at
+ * the pre-activations, so that
+ *   d ffn.3.weight [K, Ht] = do^T hd,  d ffn.3.bias = colsum(do),  d ffn.0.weight [Ht, K] = da^T xn,  d ffn.0.bias = colsum(da),
+ *   d token_norm.bias = colsum(dxn),  d token_norm.weight = colsum(dxn xhat)
+ * (tgmx_sgemm_tn / tgmx_colsum over the S C rows).  Needs 4 (4 K + 2 Ht) (n + 1) bytes of LDS at n = 128, 64 or 32 channels a pass (the
+ * widest that fits 64 KiB is taken), otherwise TGMX_E_UNSUPPORTED. */
+int tgmx_mixer_token_backward(const float* x, int64_t ldx, const float* dz1, int64_t ldd, int64_t S, int32_t K, int32_t C, const float* tok_g,
+                              const float* tok_b, const float* w1, const float* b1, int32_t Ht, const float* w2, float eps, float* dx,
+                              int64_t ldo, float* rows, int64_t ldw, const tgmx_dropout_t* drop_hidden, const tgmx_dropout_t* drop_out,
+                              tgmx_stream_t stream);
+
+/* The backward of tgmx_graphmixer_forward_train as ONE call (tgmx_abi_sizeof(36)), g = dL/dout [S, E].  x0 / save_z / save_z1 / cat:
+ * what that forward wrote; layers: the weights it ran with; ch_w1T [D, Hc], ch_w2T [Hc, D], out_wT [D, E] (the first D columns of out_w):
+ * their transposes (one tgmx_pack2d).  Every gradient pointer may be NULL: not wanted, and the launches that feed only it are skipped;
+ * gradients are written (not accumulated) in the parameters' own layouts.  No gradient reaches node_x, the edge features or the time
+ * encoder.  No float atomics: two runs give the same bits.  Order:
+ *   d out_w = g^T cat (tgmx_sgemm_tn), d out_b = colsum(g), dcat = g out_w[:, :D] (tgmx_sgemm_nt_ep on out_wT), tgmx_mixer_tail_backward -> gz;
+ *   per layer, last first: y = tgmx_mixer_channel_norm(z1), a = y W1^T + b1 (tgmx_sgemm_nt_ep), [p > 0: gt = tgmx_dropout(gz), site 3],
+ *     dh = gt W2 (tgmx_sgemm_nt_ep on ch_w2T), tgmx_mixer_gelu_backward (site 2), d ch_w2 = gt^T hd, d ch_b2 = colsum(gt), d ch_w1 = da^T y,
+ *     d ch_b1 = colsum(da), dy = da W1 (tgmx_sgemm_nt_ep on ch_w1T), tgmx_ln_backward (res = a row of zeros, leading dimension 0),
+ *     d ch_g = colsum(dgx), d ch_b = colsum(dy), dz1 = du + gz (tgmx_add_cols), tgmx_mixer_token_backward (sites 0, 1) -> gz and rows,
+ *     the token block's six gradients from rows (two tgmx_sgemm_tn, four tgmx_colsum; Ht = 0: the two weights and ffn.0.bias are empty);
+ *   d proj_w = gz^T x0 (tgmx_sgemm_tn), d proj_b = colsum(gz).
+ * The chain stops at the lowest layer that still has a gradient wanted at or below it.  drop_p / drop_seed / drop_stream: the forward's. */
+typedef struct tgmx_mixer_layer_grad {
+  float *tok_g, *tok_b, *tok_w1, *tok_b1, *tok_w2, *tok_b2;
+  float *ch_g, *ch_b, *ch_w1, *ch_b1, *ch_w2, *ch_b2;
+} tgmx_mixer_layer_grad_t;
+typedef struct tgmx_graphmixer_bwd {
+  int64_t S; int32_t K, D, T, E, F, num_layers; float eps; float drop_p; uint64_t drop_seed, drop_stream;
+  const float* g; int64_t ldg;
+  const float *x0, *save_z, *save_z1, *cat; const int32_t* nbr_nids; int64_t ldx0, ldz, ldh, ldcat;
+  tgmx_mixer_layer_t layers[TGMX_MIXER_MAX_LAYERS];
+  const float* ch_w1T[TGMX_MIXER_MAX_LAYERS]; const float* ch_w2T[TGMX_MIXER_MAX_LAYERS]; const float* out_wT;
+  float *d_proj_w, *d_proj_b, *d_out_w, *d_out_b;
+  tgmx_mixer_layer_grad_t d_layers[TGMX_MIXER_MAX_LAYERS];
+  void* workspace; size_t workspace_bytes;
+} tgmx_graphmixer_bwd_t;
+size_t tgmx_graphmixer_backward_workspace_bytes(const tgmx_graphmixer_bwd_t* args);
+int tgmx_graphmixer_backward(const tgmx_graphmixer_bwd_t* args, tgmx_stream_t stream);
 
 /* ---- DyGFormer (the reference's tgm/nn/encoder/dygformer.py), inference ---- */
 

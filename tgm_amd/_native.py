@@ -260,6 +260,29 @@ class GraphMixerFwd(ctypes.Structure):
     ]  # fmt: skip
 
 
+class MixerLayerGrad(ctypes.Structure):
+    """tgmx_mixer_layer_grad_t (include/tgm_amd.h)."""
+
+    _fields_ = [(n, c_void_p) for n in ('tok_g', 'tok_b', 'tok_w1', 'tok_b1', 'tok_w2', 'tok_b2', 'ch_g', 'ch_b', 'ch_w1', 'ch_b1', 'ch_w2', 'ch_b2')]
+
+
+class GraphMixerBwd(ctypes.Structure):
+    """tgmx_graphmixer_bwd_t (include/tgm_amd.h)."""
+
+    _fields_ = [
+        ('S', c_int64), ('K', c_int32), ('D', c_int32), ('T', c_int32), ('E', c_int32), ('F', c_int32), ('num_layers', c_int32),
+        ('eps', ctypes.c_float), ('drop_p', ctypes.c_float), ('drop_seed', ctypes.c_uint64), ('drop_stream', ctypes.c_uint64),
+        ('g', c_void_p), ('ldg', c_int64),
+        ('x0', c_void_p), ('save_z', c_void_p), ('save_z1', c_void_p), ('cat', c_void_p), ('nbr_nids', c_void_p),
+        ('ldx0', c_int64), ('ldz', c_int64), ('ldh', c_int64), ('ldcat', c_int64),
+        ('layers', MixerLayer * MIXER_MAX_LAYERS),
+        ('ch_w1T', c_void_p * MIXER_MAX_LAYERS), ('ch_w2T', c_void_p * MIXER_MAX_LAYERS), ('out_wT', c_void_p),
+        ('d_proj_w', c_void_p), ('d_proj_b', c_void_p), ('d_out_w', c_void_p), ('d_out_b', c_void_p),
+        ('d_layers', MixerLayerGrad * MIXER_MAX_LAYERS),
+        ('workspace', c_void_p), ('workspace_bytes', c_size_t),
+    ]  # fmt: skip
+
+
 DYGFORMER_MAX_LAYERS = 8  # TGMX_DYGFORMER_MAX_LAYERS
 DYGFORMER_MAX_SEQ = 2048  # slots per sequence (tgmx_dygformer_cooccurrence keeps both id sequences in LDS)
 MHA_SMALL_MAX_TOKENS = 128  # tgmx_mha_small's envelope
@@ -407,6 +430,16 @@ SIGNATURES['tgmx_mixer_tail'] = (
     [_P, c_int64, c_int64, c_int32, c_int32, _P, _P, c_int64, c_int32, _P, _P, _P, _P, c_int64, _P, c_int64, _P, _P, c_int64, _P],
 )
 SIGNATURES['tgmx_graphmixer_forward'] = (c_int32, [ctypes.POINTER(GraphMixerFwd), _P])
+SIGNATURES['tgmx_mixer_train_supported'] = (c_int32, [c_int32, c_int32, c_int32])
+SIGNATURES['tgmx_mixer_token_train'] = (c_int32, SIGNATURES['tgmx_mixer_token'][1][:-1] + [_P, _P, _P])
+SIGNATURES['tgmx_graphmixer_forward_train'] = (c_int32, [ctypes.POINTER(GraphMixerFwd), _P, _P, _P, _P])
+SIGNATURES['tgmx_mixer_channel_norm'] = (c_int32, [_P, c_int64, c_int64, c_int32, _P, _P, ctypes.c_float, _P, c_int64, _P])
+SIGNATURES['tgmx_mixer_gelu_backward'] = (c_int32, [_P, c_int64, _P, c_int64, c_int64, c_int32, _P, _P])
+SIGNATURES['tgmx_mixer_tail_backward'] = (c_int32, [_P, c_int64, _P, c_int64, c_int32, c_int32, _P, c_int64, _P])
+SIGNATURES['tgmx_mixer_token_backward'] = (c_int32, [_P, c_int64, _P, c_int64, c_int64, c_int32, c_int32, _P, _P, _P, _P, c_int32, _P, ctypes.c_float, _P,
+                                                     c_int64, _P, c_int64, _P, _P, _P])  # fmt: skip
+SIGNATURES['tgmx_graphmixer_backward_workspace_bytes'] = (c_size_t, [ctypes.POINTER(GraphMixerBwd)])
+SIGNATURES['tgmx_graphmixer_backward'] = (c_int32, [ctypes.POINTER(GraphMixerBwd), _P])
 SIGNATURES['tgmx_dygformer_cooccurrence'] = (c_int32, [_P, _P, c_int64, _P, c_int64, c_int32, _P, _P, _P, _P, _P, _P, c_int32, _P, _P, _P, c_int64, _P])
 SIGNATURES['tgmx_dygformer_prologue'] = (
     c_int32,

@@ -332,6 +332,19 @@ struct GemmCall {
 // tgmx_tpnet_forward.
 int mixer_layers_run(bool refine, const tgmx_mixer_layer_t* layers, int num_layers, int64_t S, int32_t K, int32_t C, float eps, float* z, float* z1,
                      float* y, int64_t ldz, float* h, int64_t ldh, tgmx_stream_t stream);
+
+// dynamic LDS of the token kernels, per workgroup (one seed): the forward keeps the seed's [K][C] tile and a chunk's normalised column and
+// hidden activations (csrc/mixer.hip); the backward keeps a chunk's 4 K + 2 Ht per-column values at a pitch of threads + 1 floats, in chunks
+// of 128, 64 or 32 channels -- the widest that fits (csrc/mixer_bwd.hip).  Both must fit kMixerTokMaxLds.
+constexpr int kMixerTokThreads = 128;
+constexpr size_t kMixerTokMaxLds = 64 * 1024;
+inline size_t mixer_token_lds_bytes(int K, int C, int Ht) { return sizeof(float) * ((size_t)K * C + (size_t)(K + Ht) * kMixerTokThreads); }
+inline size_t mixer_token_bwd_lds_bytes(int K, int Ht, int threads) { return sizeof(float) * (size_t)(4 * K + 2 * Ht) * (threads + 1); }
+inline int mixer_token_bwd_threads(int K, int Ht) {  // 0: not even the narrowest chunk fits
+  for (int t = kMixerTokThreads; t >= 32; t >>= 1)
+    if (mixer_token_bwd_lds_bytes(K, Ht, t) <= kMixerTokMaxLds) return t;
+  return 0;
+}
 }  // namespace tgmx
 // two independent GEMMs as one launch (bit for bit what two tgmx_sgemm_nt calls give; falls back to them when either problem would not
 // take the K-split kernel on its own)

@@ -1,7 +1,8 @@
 // GraphMixer (the reference's examples/linkproppred/graphmixer.py) for gfx950: the time-gap neighbour grouping of its hook and the
 // inference forward of its encoder -- Time2Vec prologue, MLPMixer token mixing (with the next channel LayerNorm fused in), the tail
 // (masked mean over the sampled slots, time-gap node encoder, concatenation).  The dense contractions (projection, channel FFNs, output
-// layer) run on the exact-fp32 MFMA GEMM of csrc/dense.hip through tgmx_sgemm_nt_ep (GELU / residual epilogues).
+// layer) run on the exact-fp32 MFMA GEMM of csrc/dense.hip through tgmx_sgemm_nt_ep (GELU / residual epilogues).  The same launches with
+// per-call buffers and the layers' dropout sites are the training forward (tgmx_graphmixer_forward_train); its backward is csrc/mixer_bwd.hip.
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include "common.h"
@@ -83,21 +84,24 @@ __global__ __launch_bounds__(256) void mixer_prologue_kernel(const float* __rest
 // One workgroup per seed.  Pass 1, one thread per channel (chunks of kTokThreads): LayerNorm over the K tokens of the channel's column,
 // the two small Linears with GELU between them, the residual -> z1 tile [K][C] in LDS.  Pass 2, one wave per token: LayerNorm over the
 // C channels of the z1 row -> z1 and y rows in global memory.
-constexpr int kTokThreads = 128;
-constexpr size_t kTokMaxLds = 64 * 1024;
+constexpr int kTokThreads = kMixerTokThreads;
+constexpr size_t kTokMaxLds = kMixerTokMaxLds;
 
 __device__ __forceinline__ float gelu_erf(float v) { return 0.5f * v * (1.f + erff(v * 0.70710678118654752f)); }
 
 // kRefine (TPNet): one correction step on the column mean, mean += sum(x - mean) / K.  The K tokens of an all-pad TPNet sequence are identical,
 // so the column is constant; an error d in its mean leaves the LayerNorm as d / sqrt(eps) = 316 d where the exact answer is 0.  With the
 // correction the mean of K equal values is that value, bit for bit.  GraphMixer keeps the plain mean (its results stay as they were).
-template <bool kRefine>
+// kDrop (training): the counter-based dropout of common.h after the GELU (element (s C + c) Ht + j of stream d0) and on the block's output
+// before the residual (element (s C + c) K + k of stream d1); without it the arithmetic is the inference kernel's, expression for expression.
+template <bool kRefine, bool kDrop>
 __global__ __launch_bounds__(kTokThreads) void mixer_token_kernel(const float* __restrict__ x, long long ldx, int K, int C,
                                                                   const float* __restrict__ tg, const float* __restrict__ tbeta,
                                                                   const float* __restrict__ w1, const float* __restrict__ b1, int Ht,
                                                                   const float* __restrict__ w2, const float* __restrict__ b2,
                                                                   const float* __restrict__ cg, const float* __restrict__ cb, float eps,
-                                                                  float* __restrict__ z1, float* __restrict__ y, long long ldo) {
+                                                                  float* __restrict__ z1, float* __restrict__ y, long long ldo,
+                                                                  const DropoutArgs d0, const DropoutArgs d1) {
   extern __shared__ float lds[];
   float* __restrict__ zt = lds;                         // [K][C]: the seed's z1 tile
   float* __restrict__ xn = lds + (size_t)K * C;         // [K][kTokThreads]: the normalised column of each thread
@@ -127,15 +131,18 @@ __global__ __launch_bounds__(kTokThreads) void mixer_token_kernel(const float* _
       }
       const float rstd = 1.f / sqrtf(var / (float)K + eps);
       for (int k = 0; k < K; ++k) xn[k * kTokThreads + t] = (zt[k * C + c] - mean) * rstd * tg[k] + tbeta[k];
+      [[maybe_unused]] const unsigned long long col = (unsigned long long)s * C + c;
       for (int j = 0; j < Ht; ++j) {
         float a = 0.f;
         for (int k = 0; k < K; ++k) a = __fmaf_rn(w1[j * K + k], xn[k * kTokThreads + t], a);
-        hb[j * kTokThreads + t] = gelu_erf(a + b1[j]);
+        if constexpr (kDrop) hb[j * kTokThreads + t] = gelu_erf(a + b1[j]) * dropout_scale(d0, col * Ht + j);
+        else hb[j * kTokThreads + t] = gelu_erf(a + b1[j]);
       }
       for (int k = 0; k < K; ++k) {
         float a = 0.f;
         for (int j = 0; j < Ht; ++j) a = __fmaf_rn(w2[k * Ht + j], hb[j * kTokThreads + t], a);
-        zt[k * C + c] += a + b2[k];
+        if constexpr (kDrop) zt[k * C + c] += (a + b2[k]) * dropout_scale(d1, col * K + k);
+        else zt[k * C + c] += a + b2[k];
       }
     }
   }
@@ -167,7 +174,7 @@ __global__ __launch_bounds__(kTokThreads) void mixer_token_kernel(const float* _
   }
 }
 
-static size_t token_lds_bytes(int K, int C, int Ht) { return sizeof(float) * ((size_t)K * C + (size_t)(K + Ht) * kTokThreads); }
+static size_t token_lds_bytes(int K, int C, int Ht) { return mixer_token_lds_bytes(K, C, Ht); }
 
 // ---- tail ----------------------------------------------------------------------------------------------------------------------------
 
@@ -280,7 +287,8 @@ extern "C" int tgmx_mixer_prologue(const float* edge_x, const int64_t* seed_t, c
 
 static int mixer_token_run(bool refine, const float* x, int64_t ldx, int64_t S, int32_t K, int32_t C, const float* tok_g, const float* tok_b,
                            const float* w1, const float* b1, int32_t Ht, const float* w2, const float* b2, const float* ch_g, const float* ch_b,
-                           float eps, float* z1, float* y, int64_t ldo, tgmx_stream_t stream) {
+                           float eps, float* z1, float* y, int64_t ldo, tgmx_stream_t stream, const tgmx_dropout_t* drop_hidden = nullptr,
+                           const tgmx_dropout_t* drop_out = nullptr) {
   TGMX_REQUIRE(S >= 0 && K > 0 && C > 0 && Ht >= 0 && ldx >= C && ldo >= C, "mixer_token: bad sizes S=%lld K=%d C=%d Ht=%d", (long long)S, K, C, Ht);
   if (S == 0) return TGMX_OK;
   TGMX_REQUIRE(x && tok_g && tok_b && (Ht == 0 || (w1 && b1 && w2)) && b2 && ch_g && ch_b && z1 && y, "mixer_token: null pointer");
@@ -289,12 +297,18 @@ static int mixer_token_run(bool refine, const float* x, int64_t ldx, int64_t S, 
     set_error("mixer_token: K=%d tokens x C=%d channels (token hidden %d) need %zu bytes of LDS per seed, more than %zu", K, C, Ht, lds, kTokMaxLds);
     return TGMX_E_UNSUPPORTED;
   }
+  const DropoutArgs d0 = make_dropout(drop_hidden), d1 = make_dropout(drop_out);
+  const bool drop = d0.thresh != 0 || d1.thresh != 0;
+  TGMX_REQUIRE(!(refine && drop), "mixer_token: the refined mean has no training form");
   if (refine)
-    hipLaunchKernelGGL(mixer_token_kernel<true>, dim3((unsigned)S), dim3(kTokThreads), lds, (hipStream_t)stream, x, (long long)ldx, K, C, tok_g,
-                       tok_b, w1, b1, Ht, w2, b2, ch_g, ch_b, eps, z1, y, (long long)ldo);
+    hipLaunchKernelGGL((mixer_token_kernel<true, false>), dim3((unsigned)S), dim3(kTokThreads), lds, (hipStream_t)stream, x, (long long)ldx, K, C, tok_g,
+                       tok_b, w1, b1, Ht, w2, b2, ch_g, ch_b, eps, z1, y, (long long)ldo, d0, d1);
+  else if (drop)
+    hipLaunchKernelGGL((mixer_token_kernel<false, true>), dim3((unsigned)S), dim3(kTokThreads), lds, (hipStream_t)stream, x, (long long)ldx, K, C, tok_g,
+                       tok_b, w1, b1, Ht, w2, b2, ch_g, ch_b, eps, z1, y, (long long)ldo, d0, d1);
   else
-    hipLaunchKernelGGL(mixer_token_kernel<false>, dim3((unsigned)S), dim3(kTokThreads), lds, (hipStream_t)stream, x, (long long)ldx, K, C, tok_g,
-                       tok_b, w1, b1, Ht, w2, b2, ch_g, ch_b, eps, z1, y, (long long)ldo);
+    hipLaunchKernelGGL((mixer_token_kernel<false, false>), dim3((unsigned)S), dim3(kTokThreads), lds, (hipStream_t)stream, x, (long long)ldx, K, C, tok_g,
+                       tok_b, w1, b1, Ht, w2, b2, ch_g, ch_b, eps, z1, y, (long long)ldo, d0, d1);
   TGMX_CHECK_LAUNCH("mixer_token");
   return TGMX_OK;
 }
@@ -320,6 +334,13 @@ extern "C" int tgmx_mixer_token(const float* x, int64_t ldx, int64_t S, int32_t 
   return mixer_token_run(false, x, ldx, S, K, C, tok_g, tok_b, w1, b1, Ht, w2, b2, ch_g, ch_b, eps, z1, y, ldo, stream);
 }
 
+extern "C" int tgmx_mixer_token_train(const float* x, int64_t ldx, int64_t S, int32_t K, int32_t C, const float* tok_g, const float* tok_b,
+                                      const float* w1, const float* b1, int32_t Ht, const float* w2, const float* b2, const float* ch_g,
+                                      const float* ch_b, float eps, float* z1, float* y, int64_t ldo, const tgmx_dropout_t* drop_hidden,
+                                      const tgmx_dropout_t* drop_out, tgmx_stream_t stream) {
+  return mixer_token_run(false, x, ldx, S, K, C, tok_g, tok_b, w1, b1, Ht, w2, b2, ch_g, ch_b, eps, z1, y, ldo, stream, drop_hidden, drop_out);
+}
+
 extern "C" int tgmx_tpnet_token_mix(const float* x, int64_t ldx, int64_t S, int32_t K, int32_t C, const float* tok_g, const float* tok_b,
                                     const float* w1, const float* b1, int32_t Ht, const float* w2, const float* b2, const float* ch_g,
                                     const float* ch_b, float eps, float* z1, float* y, int64_t ldo, tgmx_stream_t stream) {
@@ -341,19 +362,66 @@ extern "C" int tgmx_mixer_tail(const float* z, int64_t ldz, int64_t S, int32_t K
   return TGMX_OK;
 }
 
-extern "C" int tgmx_graphmixer_forward(const tgmx_graphmixer_fwd_t* a, tgmx_stream_t stream) {
+// save_z / save_z1 (training, both or neither): layer l reads its input from save_z + l R ldz and leaves its token block's output in
+// save_z1 + l R ldz -- the same launches in the same order as the inference call, writing elsewhere; drop: the sites' common descriptor
+// (stream = the call's first stream; site s of layer l draws from stream + 4 l + s), NULL = off.
+static int graphmixer_forward_run(const tgmx_graphmixer_fwd_t* a, float* save_z, float* save_z1, const tgmx_dropout_t* drop, tgmx_stream_t stream) {
   TGMX_REQUIRE(a && a->num_layers >= 0 && a->num_layers <= TGMX_MIXER_MAX_LAYERS, "graphmixer_forward: bad argument block");
   TGMX_REQUIRE(a->ldx0 % 4 == 0 && a->ldz % 4 == 0 && a->ldh % 4 == 0 && a->ldcat % 4 == 0, "graphmixer_forward: leading dimensions must be multiples of 4");
   TGMX_REQUIRE(a->n_seeds[0] + a->n_seeds[1] + a->n_seeds[2] == a->S, "graphmixer_forward: seed groups do not add up to S");
   const long long S = a->S, R = S * a->K;
   if (S == 0) return TGMX_OK;
-  const int D = a->D, T = a->T;
+  const int D = a->D, T = a->T, L = a->num_layers;
+  const bool save = save_z != nullptr;
+  const bool dropping = drop && drop->p > 0.f;
+  TGMX_REQUIRE(save || !dropping, "graphmixer_forward: dropout is the training form's");
   int rc;
   if ((rc = tgmx_mixer_prologue(a->nbr_edge_x, a->seed_t, a->nbr_t, S, a->K, D, a->tw, a->tb, T, a->x0, a->ldx0, stream))) return rc;
-  if ((rc = tgmx_sgemm_nt_ep(a->x0, a->ldx0, a->proj_w, D + T, a->z, a->ldz, R, D, D + T, a->proj_b, 0, nullptr, 0, stream))) return rc;
-  if ((rc = mixer_layers_run(false, a->layers, a->num_layers, S, a->K, D, a->eps, a->z, a->z1, a->y, a->ldz, a->h, a->ldh, stream))) return rc;
+  float* z_in = save && L > 0 ? save_z : a->z;
+  if ((rc = tgmx_sgemm_nt_ep(a->x0, a->ldx0, a->proj_w, D + T, z_in, a->ldz, R, D, D + T, a->proj_b, 0, nullptr, 0, stream))) return rc;
+  if (!save) {
+    if ((rc = mixer_layers_run(false, a->layers, L, S, a->K, D, a->eps, a->z, a->z1, a->y, a->ldz, a->h, a->ldh, stream))) return rc;
+  } else {
+    const size_t per = (size_t)R * a->ldz;
+    for (int l = 0; l < L; ++l) {
+      const tgmx_mixer_layer_t& ly = a->layers[l];
+      float* z1 = save_z1 + l * per;
+      float* z_out = l + 1 < L ? save_z + (l + 1) * per : a->z;
+      tgmx_dropout_t site[4];
+      for (int s = 0; s < 4; ++s) {
+        site[s].p = dropping ? drop->p : 0.f;
+        site[s].seed = dropping ? drop->seed : 0;
+        site[s].stream = dropping ? drop->stream + 4ull * l + s : 0;
+        site[s].row0 = 0;
+      }
+      if ((rc = mixer_token_run(false, z_in, a->ldz, S, a->K, D, ly.tok_g, ly.tok_b, ly.tok_w1, ly.tok_b1, ly.tok_hidden, ly.tok_w2, ly.tok_b2, ly.ch_g,
+                                ly.ch_b, a->eps, z1, a->y, a->ldz, stream, &site[0], &site[1])))
+        return rc;
+      if ((rc = tgmx_sgemm_nt_ep(a->y, a->ldz, ly.ch_w1, D, a->h, a->ldh, R, ly.ch_hidden, D, ly.ch_b1, 2, nullptr, 0, stream))) return rc;
+      if (!dropping) {
+        if ((rc = tgmx_sgemm_nt_ep(a->h, a->ldh, ly.ch_w2, ly.ch_hidden, z_out, a->ldz, R, D, ly.ch_hidden, ly.ch_b2, 0, z1, a->ldz, stream))) return rc;
+      } else {
+        if ((rc = tgmx_dropout(a->h, a->ldh, R, ly.ch_hidden, &site[2], a->h, a->ldh, stream))) return rc;
+        if ((rc = tgmx_sgemm_nt_ep(a->h, a->ldh, ly.ch_w2, ly.ch_hidden, z_out, a->ldz, R, D, ly.ch_hidden, ly.ch_b2, 0, nullptr, 0, stream))) return rc;
+        if ((rc = tgmx_dropout(z_out, a->ldz, R, D, &site[3], z_out, a->ldz, stream))) return rc;
+        if ((rc = tgmx_add_cols(z_out, a->ldz, z1, a->ldz, R, D, 1, stream))) return rc;
+      }
+      z_in = z_out;
+    }
+  }
   if ((rc = tgmx_mixer_tail(a->z, a->ldz, S, a->K, D, a->nbr_nids, a->node_x, a->num_nodes, a->F, a->tg_nbr, a->tg_lo, a->tg_cnt, a->seeds[0],
                             a->n_seeds[0], a->seeds[1], a->n_seeds[1], a->seeds[2], a->cat, a->ldcat, stream)))
     return rc;
   return tgmx_sgemm_nt_ep(a->cat, a->ldcat, a->out_w, D + a->F, a->out, a->E, S, a->E, D + a->F, a->out_b, 0, nullptr, 0, stream);
+}
+
+extern "C" int tgmx_graphmixer_forward(const tgmx_graphmixer_fwd_t* a, tgmx_stream_t stream) {
+  return graphmixer_forward_run(a, nullptr, nullptr, nullptr, stream);
+}
+
+extern "C" int tgmx_graphmixer_forward_train(const tgmx_graphmixer_fwd_t* a, float* save_z, float* save_z1, const tgmx_dropout_t* drop,
+                                             tgmx_stream_t stream) {
+  TGMX_REQUIRE(a && (a->num_layers == 0 || a->S == 0 || (save_z && save_z1)), "graphmixer_forward_train: the saving buffers are missing");
+  static float none;  // (num_layers == 0: nothing is saved; the pointer only marks the training form)
+  return graphmixer_forward_run(a, save_z ? save_z : &none, save_z1, drop, stream);
 }

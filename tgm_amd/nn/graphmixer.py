@@ -16,8 +16,15 @@ The native envelope is ``tgmx_mixer_token``'s: a seed's tile of ``4 * (K D + (K 
 Ht = int(token_dim_expansion * K)) fits 64 KiB of LDS.  Outside it (num_tokens = 64 at edge_dim = 172, say) the call answers
 ``TGMX_E_UNSUPPORTED`` and inference is the composed torch arithmetic of the training path, under ``torch.no_grad()`` (a
 ``RuntimeWarning`` says so, once per module).
-Training (gradients enabled, or train mode with dropout > 0) is NOT native: the reference arithmetic composed from torch ops on the device
-under autograd, with the same parameters.  A native backward is future work.  CPU tensors raise ``NativeLibraryError``.
+Training (gradients enabled) is native inside the same kind of envelope (``_graphmixer_train.py``): the forward is the inference call in
+its saving form -- the bits of the no-grad output when dropout is off -- and ``loss.backward()`` is ONE native call,
+``tgmx_graphmixer_backward``.  The envelope: float32 ``node_feat`` / edge features on the device that ask for no gradient, no autocast,
+contiguous float32 parameters, the time encoder frozen as the constructor leaves it, at least one seed, and a seed's tile inside both
+token kernels' LDS (the forward's bound above and ``4 * (4 K + 2 Ht) * 33`` bytes for the backward's narrowest pass).  Train mode with dropout > 0 is
+native too: counter-based masks (``tgmx_dropout_t``) seeded from ``torch.initial_seed()``, a fresh stream per forward call and site,
+regenerated -- not stored -- by the backward.  No gradient reaches ``node_feat``, the edge features or the time encoder.  Everything
+else (and ``TGMX_GRAPHMIXER_BWD=torch``) is the reference arithmetic composed from torch ops on the device under autograd, with the
+same parameters.  CPU tensors raise ``NativeLibraryError``.
 """
 from __future__ import annotations
 
@@ -31,7 +38,7 @@ from torch import Tensor
 
 from .. import _native
 from ..constants import PADDED_NODE_ID
-from . import _ops
+from . import _graphmixer_train, _ops
 from ._fwd_plumbing import Unsupported, cached_block, carve_scratch, check_supported, fill_mixer_layers, i32, i64, needs_torch, up4
 from ._paramver import TransientCaches
 from .mlp_mixer import MLPMixer, sgemm_ep, token_block, warn_composed
@@ -93,6 +100,8 @@ class GraphMixerEncoder(TransientCaches, nn.Module):
     def forward(self, batch: Any, node_feat: Tensor) -> Tensor:
         a = self._inputs(batch, node_feat)
         if needs_torch(self, self.dropout, node_feat, a['ex']):
+            if _graphmixer_train.in_envelope(self, node_feat, batch.nbr_edge_x[0], a['S']):
+                return _graphmixer_train.apply(self, a)  # training: the saving forward, one native call for the backward
             return self._torch_forward(a)
         for m in self.mlp_mixers:
             m._check_native()
@@ -105,7 +114,7 @@ class GraphMixerEncoder(TransientCaches, nn.Module):
             with torch.no_grad():
                 return self._torch_forward(a)
 
-    # -- training: torch ops under autograd (not native) ---------------------------------------------------------------------------------
+    # -- training outside the native envelope: torch ops under autograd ------------------------------------------------------------------
     def _torch_forward(self, a: dict) -> Tensor:
         tw = self.time_encoder.w
         dt = (a['seed_t'][:, None] - a['nbr_t']).unsqueeze(-1).float()

@@ -8,8 +8,13 @@ also writes the channel LayerNorm of its result; the channel FFN is two exact-fp
 Ht = 10: C <= 627).  Outside it the kernel answers ``TGMX_E_UNSUPPORTED`` and inference is the composed torch arithmetic below, under
 ``torch.no_grad()`` (a ``RuntimeWarning`` says so, once per module).
 
-Training (gradients enabled, or train mode with dropout > 0) is NOT native: it composes the reference arithmetic from torch ops on the
-device under autograd, with the same parameters.  A native backward is future work.  CPU tensors raise ``NativeLibraryError``.
+Training: ``MLPMixer.forward`` under gradients is native inside the training envelope (``_graphmixer_train.py``: float32 input on the
+parameters' device, no autocast, contiguous float32 parameters, the tile inside both token kernels' LDS -- the forward's bound and
+``4 * (4 K + 2 Ht) * 33`` bytes for the backward's narrowest pass): the forward's launches with the token block's dropout sites in the kernel, and a backward of
+``tgmx_mixer_token_backward`` plus dense GEMMs and reductions, with ``dx`` for an input that asks for it.  Train mode with dropout > 0 draws
+counter-based masks (``tgmx_dropout_t``).  Outside the envelope, with ``TGMX_GRAPHMIXER_BWD=torch``, and for ``FeedForwardNet`` on its own, the
+reference arithmetic is composed from torch ops on the device under autograd, with the same parameters.  CPU tensors raise
+``NativeLibraryError``.
 """
 from __future__ import annotations
 
@@ -86,8 +91,8 @@ class MLPMixer(nn.Module):
     channel mixing over the C channels of each token, each as ``x + FFN(LayerNorm(x))``.
 
     Input / output: [B, K, C] = [batch, num_tokens, num_channels].  Inference is native inside the token kernel's LDS envelope (see the
-    module docstring; composed outside it); with gradients enabled, or in train mode with dropout > 0, the forward is the reference
-    arithmetic composed from torch ops on the device (NOT native).
+    module docstring; composed outside it); with gradients enabled the forward and ``backward()`` are native inside the training envelope
+    (dropout included) and the reference arithmetic composed from torch ops on the device outside it.
     """
 
     def __init__(self, num_tokens: int, num_channels: int, token_dim_expansion_factor: float = 0.5, channel_dim_expansion_factor: float = 4.0,
@@ -104,6 +109,10 @@ class MLPMixer(nn.Module):
         if node_x.dim() != 3 or node_x.shape[1] != self.num_tokens or node_x.shape[2] != self.num_channels:
             raise ValueError(f'MLPMixer expects [B, {self.num_tokens}, {self.num_channels}], got {list(node_x.shape)}')
         if needs_torch(self, self.dropout, node_x):
+            from . import _graphmixer_train  # (imports this module)
+
+            if _graphmixer_train.mixer_in_envelope(self, node_x):
+                return _graphmixer_train.apply_mixer(self, node_x)
             return self._torch_forward(node_x)
         return self._native_forward(node_x)
 
