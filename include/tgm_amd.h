@@ -1197,6 +1197,109 @@ typedef struct tgmx_dygformer_fwd {
 } tgmx_dygformer_fwd_t;
 int tgmx_dygformer_forward(const tgmx_dygformer_fwd_t* args, tgmx_stream_t stream);
 
+/* ---- DyGFormer / TransformerEncoder training (csrc/dygformer_bwd.hip; composed by tgm_amd/nn/_dygformer_train.py) ---- */
+
+/* 1 when T tokens at head dimension dh fit the attention BACKWARD's LDS plan: Q, K, V, dO [Tp, ldk] and two T x T tiles (the dropped
+ * probabilities and dS) all resident, Tp = T rounded up to 16, ldk as the forward's, the tiles' pitches 16 and 18 (mod 32) floats, 160 KiB
+ * at most; T <= 128, dh <= 128.  (64, 100) takes 140.5 KiB -- one workgroup per CU.  (64, 128) and (128, 32) are outside: the training
+ * envelope is narrower than inference's.  The host decides the training path with this at forward time, so a forward never saves for a
+ * backward that would then refuse. */
+int tgmx_mha_small_train_supported(int32_t T, int32_t dh);
+
+/* tgmx_mha_small with dropout on the normalised probabilities before the P V product (nn.MultiheadAttention's): element
+ * ((b H + h) T + i) T + j of drop's stream.  NULL or p = 0: tgmx_mha_small, bit for bit. */
+int tgmx_mha_small_train(const float* qkv, int64_t ldq, int64_t B, int32_t T, int32_t H, int32_t dh, float* out, int64_t ldo,
+                         const tgmx_dropout_t* drop, tgmx_stream_t stream);
+
+/* Backward of tgmx_mha_small_train: qkv as the forward read it, datt [B T, ldo] the gradient at its output, drop the forward's descriptor
+ * -> dqkv [B T, ldq], columns dQ | dK | dV laid out as qkv's (columns [3 H dh, ldq) untouched).  One workgroup per (group, head); the
+ * probabilities are recomputed in LDS with the forward's arithmetic, nothing T x T reaches memory:
+ *   dV = (P o m)^T dO,  dP = (dO V^T) o m,  dS = P o (dP - rowsum(dP o P)),  dQ = scale dS K,  dK = scale dS^T Q
+ * on the exact-fp32 MFMA.  No atomics; every element written once; two runs give the same bits.  Outside
+ * tgmx_mha_small_train_supported: TGMX_E_UNSUPPORTED. */
+int tgmx_mha_small_backward(const float* qkv, int64_t ldq, const float* datt, int64_t ldo, int64_t B, int32_t T, int32_t H, int32_t dh,
+                            float* dqkv, const tgmx_dropout_t* drop, tgmx_stream_t stream);
+
+/* One layer / the whole forward in the saving form: the launches of tgmx_dygformer_layer / tgmx_dygformer_forward in the same order; with
+ * dropout off the bits of those.  Layer: x_in -> x_out (may alias); x1, att and qkv are the caller's to keep.  drop: p, seed and the first
+ * stream; site s of layer l draws from stream + 4 l + s: 0 attention probabilities [B, H, T, T], 1 the attention block's output [R, D]
+ * before the residual, 2 the FFN's hidden activations [R, 4 D], 3 the FFN's output [R, D] before the residual (element = flat index).
+ * With dropout sites 1 - 3 are extra launches (tgmx_dropout in place, tgmx_add_cols).
+ * Forward: save->counts [2 P L, 2], save->x [(num_layers + 1) R ldx] (layer l's input at l R ldx, the last layer's output last),
+ * save->qkv [num_layers R ldq], save->att / save->x1 [num_layers R ldx]; args->ch[], args->mean are kept by the caller too; args->x,
+ * x1, att, qkv are not used.  Outside tgmx_mha_small_train_supported: TGMX_E_UNSUPPORTED, nothing launched. */
+typedef struct tgmx_dygformer_save {
+  int32_t* counts; float *x, *qkv, *att, *x1;
+} tgmx_dygformer_save_t;
+int tgmx_dygformer_layer_train(const tgmx_dygformer_layer_t* layer, int64_t B, int32_t T, int32_t H, int32_t D, float eps, const float* x_in,
+                               float* x_out, float* y, float* x1, float* att, int64_t ldx, float* qkv, int64_t ldq, float* h, int64_t ldh,
+                               const tgmx_dropout_t* drop, tgmx_stream_t stream);
+int tgmx_dygformer_forward_train(const tgmx_dygformer_fwd_t* args, const tgmx_dygformer_save_t* save, const tgmx_dropout_t* drop,
+                                 tgmx_stream_t stream);
+
+/* Patch-mean backward: dx[(2 p + side) Np + t, :D] = dmean[side P + p, :D] / Np. */
+int tgmx_dygformer_mean_backward(const float* dmean, int64_t ldm, int64_t P, int32_t Np, int32_t D, float* dx, int64_t ldx, tgmx_stream_t stream);
+
+/* Time-channel backward: from dtime [2 P L, ldt] (the gradient at the Time2Vec features) and the call's ids and times, rows [2 P L, 2 dT]
+ * = [ -sin(fma(dt, w, b)) dtime dt | -sin(.) dtime ] (pad slots 0; slot 0: dt = 0); their tgmx_colsum is d time_encoder.w.{weight, bias}. */
+int tgmx_dygformer_time_backward(const float* dtime, int64_t ldt, const int32_t* src, const int32_t* dst, const int64_t* edge_time, int64_t P,
+                                 const int32_t* nbr_nids, const int64_t* nbr_t, int64_t S, int32_t k, const int32_t* src_rows,
+                                 const int32_t* dst_rows, const float* tw, const float* tb, int32_t dT, float* rows, tgmx_stream_t stream);
+
+/* Co-occurrence backward: counts as tgmx_dygformer_cooccurrence wrote them, dfeat [n, ldf] the gradient at the encoded features, n = 2 P L.
+ *   onehot [n, up4(L + 1)]: (own == c) + (other == c);  dtable [L + 1, C] = onehot^T dfeat (tgmx_sgemm_tn: a fixed order; pads count 0)
+ *   r = relu(w1 c + b1) [L + 1, C];  d W2 = dtable^T r;  d b2 = colsum(dtable);  dh = (dtable W2) [pre > 0] (tgmx_sgemm_nt_ep on w2T [C, C]);
+ *   d w1 = colsum(dh o c);  d b1 = colsum(dh)
+ * Gradient pointers may be NULL.  workspace: tgmx_dygformer_cooccurrence_backward_workspace_bytes(n, L, C). */
+size_t tgmx_dygformer_cooccurrence_backward_workspace_bytes(int64_t n, int32_t L, int32_t C);
+int tgmx_dygformer_cooccurrence_backward(const int32_t* counts, const float* dfeat, int64_t ldf, int64_t n, int32_t L, int32_t C,
+                                         const float* co_w1, const float* co_b1, const float* co_w2T, float* d_w1, float* d_b1, float* d_w2,
+                                         float* d_b2, void* workspace, size_t workspace_bytes, tgmx_stream_t stream);
+
+/* One layer's backward.  x, qkv, att, x1: what tgmx_dygformer_layer_train read and kept; tr: the transposes in_wT [D, 3 D], out_wT [D, D],
+ * w1T [D, 4 D], w2T [4 D, D]; g [R, ldx]: the gradient at x_out (clobbered); dx [R, ldx]: the gradient at x_in (NULL: not wanted -- the
+ * launches that feed only it are skipped); d: the twelve gradients, each may be NULL.  Order:
+ *   y = LN1(x1), a = y w1^T + b1 (recomputed); [p > 0: g3 = tgmx_dropout(g), site 3]; dh = g3 w2; tgmx_mixer_gelu_backward (site 2);
+ *   d w2 = g3^T hd, d b2 = colsum(g3), d w1 = da^T y, d b1 = colsum(da); dy = da w1; tgmx_ln_backward -> d ln1; dx1 = du + g;
+ *   [p > 0: g1 = tgmx_dropout(dx1), site 1]; d out_w = g1^T att, d out_b = colsum(g1); datt = g1 out_w; tgmx_mha_small_backward (site 0);
+ *   y = LN0(x) (recomputed); d in_w = dqkv^T y, d in_b = colsum(dqkv); dy = dqkv in_w; tgmx_ln_backward -> d ln0; dx = du + dx1. */
+typedef struct tgmx_dygformer_layer_grad {
+  float *ln0_g, *ln0_b, *in_w, *in_b, *out_w, *out_b, *ln1_g, *ln1_b, *w1, *b1, *w2, *b2;
+} tgmx_dygformer_layer_grad_t;
+typedef struct tgmx_dygformer_layer_tr {
+  const float *in_wT, *out_wT, *w1T, *w2T;
+} tgmx_dygformer_layer_tr_t;
+size_t tgmx_dygformer_layer_backward_workspace_bytes(int64_t B, int32_t T, int32_t D, int64_t ldx, int64_t ldq, int64_t ldh);
+int tgmx_dygformer_layer_backward(const tgmx_dygformer_layer_t* layer, const tgmx_dygformer_layer_tr_t* tr,
+                                  const tgmx_dygformer_layer_grad_t* d, int64_t B, int32_t T, int32_t H, int32_t D, float eps, const float* x,
+                                  const float* qkv, const float* att, const float* x1, int64_t ldx, int64_t ldq, int64_t ldh, float* g,
+                                  float* dx, const tgmx_dropout_t* drop, void* workspace, size_t workspace_bytes, tgmx_stream_t stream);
+
+/* The backward of tgmx_dygformer_forward_train as ONE call (tgmx_abi_sizeof(37)), g = dL/dout [2 P, E].  ch / counts / mean / save_*: what
+ * that forward wrote; layers / tr: the weights it ran with and their transposes; out_wT [D, E]; proj_w[c] as the forward took them (padded),
+ * proj_wT[2], proj_wT[3] [patch ldch[c], C]: the transposes of the time and co-occurrence projections; co_w2T [C, C].  Order:
+ *   d out_w = g^T mean, d out_b = colsum(g), dmean = g out_w, tgmx_dygformer_mean_backward; tgmx_dygformer_layer_backward, last layer first;
+ *   d proj_w[c] = dtok[:, c C : (c + 1) C]^T ch[c] (one tgmx_sgemm_tn per slot of a patch, written un-padded in the parameter's
+ *   [C, patch d] layout), d proj_b[c] = colsum; dtime = dtok_time proj_w[2], tgmx_dygformer_time_backward, two tgmx_colsum;
+ *   dfeat = dtok_co proj_w[3], tgmx_dygformer_cooccurrence_backward.
+ * Every gradient pointer may be NULL: not wanted, and the launches that feed only it are skipped (the chain stops at the lowest layer
+ * with a gradient wanted at or below it).  Written, not accumulated.  No gradient reaches node_x or nbr_x.  No float atomics. */
+typedef struct tgmx_dygformer_bwd {
+  int64_t P, S; int32_t k, dN, dE, dT, C, patch, heads, E, num_layers; float eps; float drop_p; uint64_t drop_seed, drop_stream;
+  const int32_t *src, *dst; const int64_t* edge_time; const int32_t* nbr_nids; const int64_t* nbr_t; const int32_t *src_rows, *dst_rows;
+  const float* g; int64_t ldg;
+  const float* ch[4]; int64_t ldch[4]; const int32_t* counts; const float* mean;
+  const float *save_x, *save_qkv, *save_att, *save_x1; int64_t ldx, ldq, ldh;
+  tgmx_dygformer_layer_t layers[TGMX_DYGFORMER_MAX_LAYERS];
+  tgmx_dygformer_layer_tr_t tr[TGMX_DYGFORMER_MAX_LAYERS];
+  const float *out_wT, *proj_wT[4], *tw, *tb, *co_w1, *co_b1, *co_w2T;
+  float *d_tw, *d_tb, *d_co_w1, *d_co_b1, *d_co_w2, *d_co_b2, *d_proj_w[4], *d_proj_b[4], *d_out_w, *d_out_b;
+  tgmx_dygformer_layer_grad_t d_layers[TGMX_DYGFORMER_MAX_LAYERS];
+  void* workspace; size_t workspace_bytes;
+} tgmx_dygformer_bwd_t;
+size_t tgmx_dygformer_backward_workspace_bytes(const tgmx_dygformer_bwd_t* args);
+int tgmx_dygformer_backward(const tgmx_dygformer_bwd_t* args, tgmx_stream_t stream);
+
 /* ---- TPNet (the reference's tgm/nn/encoder/tpnet.py): temporal walk matrices as random projections, pair features, inference ---- */
 
 /* The num_layer + 1 tables P[0 .. levels) of RandomProjectionModule, each [num_nodes, dim] float32, row-major, contiguous. */

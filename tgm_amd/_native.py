@@ -316,6 +316,46 @@ class DyGFormerFwd(ctypes.Structure):
     ]  # fmt: skip
 
 
+class DyGFormerSave(ctypes.Structure):
+    """tgmx_dygformer_save_t (include/tgm_amd.h)."""
+
+    _fields_ = [(n, c_void_p) for n in ('counts', 'x', 'qkv', 'att', 'x1')]
+
+
+class DyGFormerLayerGrad(ctypes.Structure):
+    """tgmx_dygformer_layer_grad_t (include/tgm_amd.h)."""
+
+    _fields_ = DyGFormerLayer._fields_
+
+
+class DyGFormerLayerTr(ctypes.Structure):
+    """tgmx_dygformer_layer_tr_t (include/tgm_amd.h)."""
+
+    _fields_ = [(n, c_void_p) for n in ('in_wT', 'out_wT', 'w1T', 'w2T')]
+
+
+class DyGFormerBwd(ctypes.Structure):
+    """tgmx_dygformer_bwd_t (include/tgm_amd.h)."""
+
+    _fields_ = [
+        ('P', c_int64), ('S', c_int64),
+        ('k', c_int32), ('dN', c_int32), ('dE', c_int32), ('dT', c_int32), ('C', c_int32), ('patch', c_int32), ('heads', c_int32), ('E', c_int32),
+        ('num_layers', c_int32), ('eps', ctypes.c_float), ('drop_p', ctypes.c_float), ('drop_seed', ctypes.c_uint64), ('drop_stream', ctypes.c_uint64),
+        ('src', c_void_p), ('dst', c_void_p), ('edge_time', c_void_p), ('nbr_nids', c_void_p), ('nbr_t', c_void_p), ('src_rows', c_void_p),
+        ('dst_rows', c_void_p),
+        ('g', c_void_p), ('ldg', c_int64),
+        ('ch', c_void_p * 4), ('ldch', c_int64 * 4), ('counts', c_void_p), ('mean', c_void_p),
+        ('save_x', c_void_p), ('save_qkv', c_void_p), ('save_att', c_void_p), ('save_x1', c_void_p), ('ldx', c_int64), ('ldq', c_int64), ('ldh', c_int64),
+        ('layers', DyGFormerLayer * DYGFORMER_MAX_LAYERS),
+        ('tr', DyGFormerLayerTr * DYGFORMER_MAX_LAYERS),
+        ('out_wT', c_void_p), ('proj_wT', c_void_p * 4), ('tw', c_void_p), ('tb', c_void_p), ('co_w1', c_void_p), ('co_b1', c_void_p), ('co_w2T', c_void_p),
+        ('d_tw', c_void_p), ('d_tb', c_void_p), ('d_co_w1', c_void_p), ('d_co_b1', c_void_p), ('d_co_w2', c_void_p), ('d_co_b2', c_void_p),
+        ('d_proj_w', c_void_p * 4), ('d_proj_b', c_void_p * 4), ('d_out_w', c_void_p), ('d_out_b', c_void_p),
+        ('d_layers', DyGFormerLayerGrad * DYGFORMER_MAX_LAYERS),
+        ('workspace', c_void_p), ('workspace_bytes', c_size_t),
+    ]  # fmt: skip
+
+
 class TconvFwd(ctypes.Structure):
     """tgmx_tconv_fwd_t (include/tgm_amd.h)."""
 
@@ -453,6 +493,26 @@ SIGNATURES['tgmx_dygformer_layer'] = (
     [ctypes.POINTER(DyGFormerLayer), c_int64, c_int32, c_int32, c_int32, ctypes.c_float, _P, _P, _P, _P, c_int64, _P, c_int64, _P, c_int64, _P],
 )
 SIGNATURES['tgmx_dygformer_forward'] = (c_int32, [ctypes.POINTER(DyGFormerFwd), _P])
+SIGNATURES['tgmx_mha_small_train_supported'] = (c_int32, [c_int32, c_int32])
+SIGNATURES['tgmx_mha_small_train'] = (c_int32, [_P, c_int64, c_int64, c_int32, c_int32, c_int32, _P, c_int64, _P, _P])
+SIGNATURES['tgmx_mha_small_backward'] = (c_int32, [_P, c_int64, _P, c_int64, c_int64, c_int32, c_int32, c_int32, _P, _P, _P])
+SIGNATURES['tgmx_dygformer_layer_train'] = (
+    c_int32,
+    [ctypes.POINTER(DyGFormerLayer), c_int64, c_int32, c_int32, c_int32, ctypes.c_float, _P, _P, _P, _P, _P, c_int64, _P, c_int64, _P, c_int64, _P, _P],
+)
+SIGNATURES['tgmx_dygformer_forward_train'] = (c_int32, [ctypes.POINTER(DyGFormerFwd), ctypes.POINTER(DyGFormerSave), _P, _P])
+SIGNATURES['tgmx_dygformer_mean_backward'] = (c_int32, [_P, c_int64, c_int64, c_int32, c_int32, _P, c_int64, _P])
+SIGNATURES['tgmx_dygformer_time_backward'] = (c_int32, [_P, c_int64, _P, _P, _P, c_int64, _P, _P, c_int64, c_int32, _P, _P, _P, _P, c_int32, _P, _P])
+SIGNATURES['tgmx_dygformer_cooccurrence_backward_workspace_bytes'] = (c_size_t, [c_int64, c_int32, c_int32])
+SIGNATURES['tgmx_dygformer_cooccurrence_backward'] = (c_int32, [_P, _P, c_int64, c_int64, c_int32, c_int32, _P, _P, _P, _P, _P, _P, _P, _P, c_size_t, _P])
+SIGNATURES['tgmx_dygformer_layer_backward_workspace_bytes'] = (c_size_t, [c_int64, c_int32, c_int32, c_int64, c_int64, c_int64])
+SIGNATURES['tgmx_dygformer_layer_backward'] = (
+    c_int32,
+    [ctypes.POINTER(DyGFormerLayer), ctypes.POINTER(DyGFormerLayerTr), ctypes.POINTER(DyGFormerLayerGrad), c_int64, c_int32, c_int32, c_int32,
+     ctypes.c_float, _P, _P, _P, _P, c_int64, c_int64, c_int64, _P, _P, _P, _P, c_size_t, _P],
+)  # fmt: skip
+SIGNATURES['tgmx_dygformer_backward_workspace_bytes'] = (c_size_t, [ctypes.POINTER(DyGFormerBwd)])
+SIGNATURES['tgmx_dygformer_backward'] = (c_int32, [ctypes.POINTER(DyGFormerBwd), _P])
 
 TPNET_MAX_LEVELS = 8  # TGMX_TPNET_MAX_LEVELS
 TPNET_PAIR_MAX_LEVELS = 4  # tgmx_tpnet_pair_features' envelope (tables per side)

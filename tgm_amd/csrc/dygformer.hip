@@ -1,4 +1,4 @@
-// DyGFormer (the reference's tgm/nn/encoder/dygformer.py) for gfx950, inference: the neighbour co-occurrence count and its encoding, the
+// DyGFormer (the reference's tgm/nn/encoder/dygformer.py) for gfx950, the forward (inference, and the saving form training takes): the neighbour co-occurrence count and its encoding, the
 // prologue that builds the node / edge / time channel inputs straight from the sampler's hop-0 output (through row indices: no gathered
 // copy of nbr_edge_x), LayerNorm over token rows, multi-head self-attention over the 2 Np tokens of one (src, dst) pair on the exact-fp32
 // MFMA, and the per-side patch mean.  The dense contractions (patch projections, in / out projections, FFN, output layer) run on the
@@ -8,14 +8,11 @@
 // slot 0 is the seed itself, slot j > 0 the sampler's slot j - 1 of row src_rows[p] / dst_rows[p] (NULL: rows p and P + p).
 #include "common.h"
 #include "gemm.h"
+#include "mha_small.h"
 
 namespace tgmx {
 
-constexpr int kDygMaxL = 2048;       // co-occurrence: both id sequences in LDS (16 KiB)
-constexpr int kMhaMaxT = 128;        // tokens per pair
-constexpr int kMhaMaxDh = 128;       // head dimension
-constexpr int kMhaJ = kMhaMaxT / 16;  // score tiles per row tile
-constexpr size_t kMhaMaxLds = 160 * 1024;
+constexpr int kDygMaxL = 2048;  // co-occurrence: both id sequences in LDS (16 KiB)
 
 // the sampler row and the seed of sequence q (row < 0: indices out of range, the sequence is treated as all pads)
 struct DygSeqs {
@@ -130,8 +127,9 @@ __global__ __launch_bounds__(256) void dyg_prologue_kernel(DygSeqs sq, const flo
 // probabilities).  Scores live in the MFMA accumulators: lane (c, g) of a 16 x 16 tile holds rows 4 g .. 4 g + 3 of column c, so a row's
 // max / sum is a reduction over the 16 lanes of a group (xor 1, 2, 4, 8) and over the row tile's column tiles.
 // Both leading dimensions are 4 (mod 8) floats: the 16 rows that one MFMA operand load touches fall into 16 different bank quads.
+// drop (training): the normalised probabilities are scaled by the site's mask before the P V product, element ((grp H + h) T + i) T + j.
 __global__ __launch_bounds__(256) void mha_small_kernel(const float* __restrict__ qkv, long long ldq, int T, int H, int dh, float scale,
-                                                       float* __restrict__ out, long long ldo, int ldk, int ldr) {
+                                                       float* __restrict__ out, long long ldo, int ldk, int ldr, const DropoutArgs drop) {
   extern __shared__ float lds[];
   const int Tp = (T + 15) & ~15, nI = Tp >> 4, dh4 = (dh + 3) & ~3, D = H * dh;
   float* __restrict__ kv = lds;
@@ -181,9 +179,17 @@ __global__ __launch_bounds__(256) void mha_small_kernel(const float* __restrict_
 #pragma unroll
       for (int o = 8; o > 0; o >>= 1) s += __shfl_xor(s, o);
       float* __restrict__ po = pr + (i * 16 + 4 * lg + r) * ldr + lc;
+      if (drop.thresh == 0) {
 #pragma unroll
-      for (int j = 0; j < kMhaJ; ++j)
-        if (j < nI) po[j * 16] = acc[j][r] / s;
+        for (int j = 0; j < kMhaJ; ++j)
+          if (j < nI) po[j * 16] = acc[j][r] / s;
+      } else {
+        const int row = i * 16 + 4 * lg + r;
+        const unsigned long long e0 = ((unsigned long long)blockIdx.x * T + row) * T + lc;
+#pragma unroll
+        for (int j = 0; j < kMhaJ; ++j)
+          if (j < nI) po[j * 16] = (row < T && j * 16 + lc < T) ? acc[j][r] / s * dropout_scale(drop, e0 + j * 16) : 0.f;
+      }
     }
   }
   __syncthreads();  // every wave is done with K
@@ -212,8 +218,6 @@ __global__ __launch_bounds__(256) void mha_small_kernel(const float* __restrict_
     }
   }
 }
-
-static int mha_ld(int n4) { return (n4 / 4) % 2 ? n4 : n4 + 4; }  // multiple of 4, 4 (mod 8)
 
 // ---- tail -------------------------------------------------------------------------------------------------------------------------------
 
@@ -281,8 +285,9 @@ extern "C" int tgmx_dygformer_prologue(const float* node_x, int64_t num_nodes, i
   return TGMX_OK;
 }
 
-extern "C" int tgmx_mha_small(const float* qkv, int64_t ldq, int64_t B, int32_t T, int32_t H, int32_t dh, float* out, int64_t ldo,
-                              tgmx_stream_t stream) {
+extern "C" int tgmx_mha_small_train(const float* qkv, int64_t ldq, int64_t B, int32_t T, int32_t H, int32_t dh, float* out, int64_t ldo,
+                                    const tgmx_dropout_t* drop, tgmx_stream_t stream) {
+  TGMX_REQUIRE(!drop || (drop->p >= 0.f && drop->p < 1.f), "mha_small: p must be in [0, 1)");
   TGMX_REQUIRE(B >= 0 && T > 0 && H > 0 && dh > 0 && (long long)H * dh < (1 << 28) && ldq >= 3ll * H * dh && ldo >= (long long)H * dh &&
                    B * H < (1ll << 31),
                "mha_small: bad sizes B=%lld T=%d H=%d dh=%d", (long long)B, T, H, dh);
@@ -303,9 +308,14 @@ extern "C" int tgmx_mha_small(const float* qkv, int64_t ldq, int64_t B, int32_t 
     }
   }
   hipLaunchKernelGGL(mha_small_kernel, dim3((unsigned)(B * H)), dim3(256), lds, (hipStream_t)stream, qkv, (long long)ldq, T, H, dh,
-                     1.f / sqrtf((float)dh), out, (long long)ldo, ldk, ldr);
+                     1.f / sqrtf((float)dh), out, (long long)ldo, ldk, ldr, make_dropout(drop));
   TGMX_CHECK_LAUNCH("mha_small");
   return TGMX_OK;
+}
+
+extern "C" int tgmx_mha_small(const float* qkv, int64_t ldq, int64_t B, int32_t T, int32_t H, int32_t dh, float* out, int64_t ldo,
+                              tgmx_stream_t stream) {
+  return tgmx_mha_small_train(qkv, ldq, B, T, H, dh, out, ldo, nullptr, stream);
 }
 
 extern "C" int tgmx_dygformer_tail(const float* x, int64_t ldx, int64_t P, int32_t Np, int32_t D, float* mean, int64_t ldm, const float* out_w,
@@ -320,24 +330,48 @@ extern "C" int tgmx_dygformer_tail(const float* x, int64_t ldx, int64_t P, int32
   return tgmx_sgemm_nt_ep(mean, ldm, out_w, D, out, E, 2 * P, E, D, out_b, 0, nullptr, 0, stream);
 }
 
-// one transformer layer on x [R, ldx] (in place; y, x1, att [R, ldx], qkv [R, ldq], h [R, ldh] scratch)
-extern "C" int tgmx_dygformer_layer(const tgmx_dygformer_layer_t* ly, int64_t B, int32_t T, int32_t H, int32_t D, float eps, float* x, float* y,
-                                    float* x1, float* att, int64_t ldx, float* qkv, int64_t ldq, float* h, int64_t ldh, tgmx_stream_t stream) {
+// one transformer layer x_in -> x_out [R, ldx] (x_out may be x_in; y, x1, att [R, ldx], qkv [R, ldq], h [R, ldh] scratch).  drop: the
+// layer's four sites draw from stream + 0 .. 3; with dropout the three row sites are extra launches (tgmx_dropout in place, tgmx_add_cols)
+extern "C" int tgmx_dygformer_layer_train(const tgmx_dygformer_layer_t* ly, int64_t B, int32_t T, int32_t H, int32_t D, float eps,
+                                          const float* x_in, float* x_out, float* y, float* x1, float* att, int64_t ldx, float* qkv,
+                                          int64_t ldq, float* h, int64_t ldh, const tgmx_dropout_t* drop, tgmx_stream_t stream) {
   TGMX_REQUIRE(ly && B >= 0 && T > 0 && H > 0 && D > 0 && D % H == 0 && ldx >= D && ldq >= 3ll * D && ldh >= 4ll * D && ldx % 4 == 0 && ldq % 4 == 0 &&
                    ldh % 4 == 0,
                "dygformer_layer: bad sizes B=%lld T=%d H=%d D=%d (leading dimensions: multiples of 4)", (long long)B, T, H, D);
+  TGMX_REQUIRE(!drop || (drop->p >= 0.f && drop->p < 1.f), "dygformer_layer: p must be in [0, 1)");
   const long long R = B * T;
+  const bool dropping = drop && drop->p > 0.f;
+  tgmx_dropout_t site[4];
+  for (int s = 0; s < 4; ++s) site[s] = dropping ? tgmx_dropout_t{drop->p, drop->seed, drop->stream + s, 0} : tgmx_dropout_t{0.f, 0, 0, 0};
   int rc;
-  if ((rc = tgmx_layernorm_rows(x, ldx, R, D, ly->ln0_g, ly->ln0_b, eps, y, ldx, stream))) return rc;
+  if ((rc = tgmx_layernorm_rows(x_in, ldx, R, D, ly->ln0_g, ly->ln0_b, eps, y, ldx, stream))) return rc;
   if ((rc = tgmx_sgemm_nt_ep(y, ldx, ly->in_w, D, qkv, ldq, R, 3 * D, D, ly->in_b, 0, nullptr, 0, stream))) return rc;
-  if ((rc = tgmx_mha_small(qkv, ldq, B, T, H, D / H, att, ldx, stream))) return rc;
-  if ((rc = tgmx_sgemm_nt_ep(att, ldx, ly->out_w, D, x1, ldx, R, D, D, ly->out_b, 0, x, ldx, stream))) return rc;
+  if ((rc = tgmx_mha_small_train(qkv, ldq, B, T, H, D / H, att, ldx, &site[0], stream))) return rc;
+  if (!dropping) {
+    if ((rc = tgmx_sgemm_nt_ep(att, ldx, ly->out_w, D, x1, ldx, R, D, D, ly->out_b, 0, x_in, ldx, stream))) return rc;
+  } else {
+    if ((rc = tgmx_sgemm_nt_ep(att, ldx, ly->out_w, D, x1, ldx, R, D, D, ly->out_b, 0, nullptr, 0, stream))) return rc;
+    if ((rc = tgmx_dropout(x1, ldx, R, D, &site[1], x1, ldx, stream))) return rc;
+    if ((rc = tgmx_add_cols(x1, ldx, x_in, ldx, R, D, 1, stream))) return rc;
+  }
   if ((rc = tgmx_layernorm_rows(x1, ldx, R, D, ly->ln1_g, ly->ln1_b, eps, y, ldx, stream))) return rc;
   if ((rc = tgmx_sgemm_nt_ep(y, ldx, ly->w1, D, h, ldh, R, 4 * D, D, ly->b1, 2, nullptr, 0, stream))) return rc;
-  return tgmx_sgemm_nt_ep(h, ldh, ly->w2, 4 * D, x, ldx, R, D, 4 * D, ly->b2, 0, x1, ldx, stream);
+  if (!dropping) return tgmx_sgemm_nt_ep(h, ldh, ly->w2, 4 * D, x_out, ldx, R, D, 4 * D, ly->b2, 0, x1, ldx, stream);
+  if ((rc = tgmx_dropout(h, ldh, R, 4 * D, &site[2], h, ldh, stream))) return rc;
+  if ((rc = tgmx_sgemm_nt_ep(h, ldh, ly->w2, 4 * D, x_out, ldx, R, D, 4 * D, ly->b2, 0, nullptr, 0, stream))) return rc;
+  if ((rc = tgmx_dropout(x_out, ldx, R, D, &site[3], x_out, ldx, stream))) return rc;
+  return tgmx_add_cols(x_out, ldx, x1, ldx, R, D, 1, stream);
 }
 
-extern "C" int tgmx_dygformer_forward(const tgmx_dygformer_fwd_t* a, tgmx_stream_t stream) {
+// one transformer layer on x [R, ldx] (in place; y, x1, att [R, ldx], qkv [R, ldq], h [R, ldh] scratch)
+extern "C" int tgmx_dygformer_layer(const tgmx_dygformer_layer_t* ly, int64_t B, int32_t T, int32_t H, int32_t D, float eps, float* x, float* y,
+                                    float* x1, float* att, int64_t ldx, float* qkv, int64_t ldq, float* h, int64_t ldh, tgmx_stream_t stream) {
+  return tgmx_dygformer_layer_train(ly, B, T, H, D, eps, x, x, y, x1, att, ldx, qkv, ldq, h, ldh, nullptr, stream);
+}
+
+// save == NULL: inference (every layer in place on a->x, scratch reused).  Otherwise the saving form: counts written, layer l reads its
+// input from save->x + l R ldx and writes save->x + (l + 1) R ldx; qkv, att and x1 of layer l stay in save->{qkv, att, x1} + l R ld.
+static int dyg_forward(const tgmx_dygformer_fwd_t* a, const tgmx_dygformer_save_t* save, const tgmx_dropout_t* drop, tgmx_stream_t stream) {
   TGMX_REQUIRE(a && a->num_layers >= 0 && a->num_layers <= TGMX_DYGFORMER_MAX_LAYERS, "dygformer_forward: bad argument block");
   TGMX_REQUIRE(a->patch > 0 && a->k >= 0 && (a->k + 1) % a->patch == 0 && a->C > 0 && a->heads > 0 && (4 * a->C) % a->heads == 0,
                "dygformer_forward: bad shape k=%d patch=%d C=%d heads=%d", a->k, a->patch, a->C, a->heads);
@@ -348,8 +382,10 @@ extern "C" int tgmx_dygformer_forward(const tgmx_dygformer_fwd_t* a, tgmx_stream
   const int L = a->k + 1, Np = L / a->patch, C = a->C, D = 4 * C;
   const long long R = 2 * P * Np;
   int rc;
+  TGMX_REQUIRE(!save || (save->counts && save->x && (a->num_layers == 0 || (save->qkv && save->att && save->x1))), "dygformer_forward_train: null save buffer");
+  float* x0 = save ? save->x : a->x;
   if ((rc = tgmx_dygformer_cooccurrence(a->src, a->dst, P, a->nbr_nids, a->S, a->k, a->src_rows, a->dst_rows, a->co_w1, a->co_b1, a->co_w2, a->co_b2,
-                                        C, a->table, nullptr, a->ch[3], a->ldch[3], stream)))
+                                        C, a->table, save ? save->counts : nullptr, a->ch[3], a->ldch[3], stream)))
     return rc;
   if ((rc = tgmx_dygformer_prologue(a->node_x, a->num_nodes, a->dN, a->src, a->dst, a->edge_time, P, a->nbr_nids, a->nbr_t, a->nbr_x, a->S, a->k,
                                     a->dE, a->src_rows, a->dst_rows, a->tw, a->tb, a->dT, a->ch[0], a->ldch[0], a->ch[1], a->ldch[1], a->ch[2],
@@ -358,12 +394,38 @@ extern "C" int tgmx_dygformer_forward(const tgmx_dygformer_fwd_t* a, tgmx_stream
   // patching is a view: [2 P L, ld] = [2 P Np, patch ld]; channel c's projection writes columns [c C, (c + 1) C) of the token matrix
   for (int c = 0; c < 4; ++c) {
     const long long Kc = (long long)a->patch * a->ldch[c];
-    if ((rc = tgmx_sgemm_nt_ep(a->ch[c], Kc, a->proj_w[c], Kc, a->x + (long long)c * C, a->ldx, R, C, (int)Kc, a->proj_b[c], 0, nullptr, 0, stream)))
+    if ((rc = tgmx_sgemm_nt_ep(a->ch[c], Kc, a->proj_w[c], Kc, x0 + (long long)c * C, a->ldx, R, C, (int)Kc, a->proj_b[c], 0, nullptr, 0, stream)))
       return rc;
   }
-  for (int l = 0; l < a->num_layers; ++l)
-    if ((rc = tgmx_dygformer_layer(&a->layers[l], P, 2 * Np, a->heads, D, a->eps, a->x, a->y, a->x1, a->att, a->ldx, a->qkv, a->ldq, a->h, a->ldh,
-                                   stream)))
+  if (!save) {
+    for (int l = 0; l < a->num_layers; ++l)
+      if ((rc = tgmx_dygformer_layer(&a->layers[l], P, 2 * Np, a->heads, D, a->eps, a->x, a->y, a->x1, a->att, a->ldx, a->qkv, a->ldq, a->h, a->ldh,
+                                     stream)))
+        return rc;
+    return tgmx_dygformer_tail(a->x, a->ldx, P, Np, D, a->mean, a->ldx, a->out_w, a->out_b, a->E, a->out, stream);
+  }
+  const bool dropping = drop && drop->p > 0.f;
+  for (int l = 0; l < a->num_layers; ++l) {
+    const long long ox = (long long)l * R * a->ldx, oq = (long long)l * R * a->ldq;
+    tgmx_dropout_t d{0.f, 0, 0, 0};
+    if (dropping) d = tgmx_dropout_t{drop->p, drop->seed, drop->stream + 4ull * l, 0};
+    if ((rc = tgmx_dygformer_layer_train(&a->layers[l], P, 2 * Np, a->heads, D, a->eps, save->x + ox, save->x + ox + R * a->ldx, a->y, save->x1 + ox,
+                                         save->att + ox, a->ldx, save->qkv + oq, a->ldq, a->h, a->ldh, &d, stream)))
       return rc;
-  return tgmx_dygformer_tail(a->x, a->ldx, P, Np, D, a->mean, a->ldx, a->out_w, a->out_b, a->E, a->out, stream);
+  }
+  return tgmx_dygformer_tail(save->x + (long long)a->num_layers * R * a->ldx, a->ldx, P, Np, D, a->mean, a->ldx, a->out_w, a->out_b, a->E, a->out, stream);
+}
+
+extern "C" int tgmx_dygformer_forward(const tgmx_dygformer_fwd_t* a, tgmx_stream_t stream) { return dyg_forward(a, nullptr, nullptr, stream); }
+
+extern "C" int tgmx_dygformer_forward_train(const tgmx_dygformer_fwd_t* a, const tgmx_dygformer_save_t* save, const tgmx_dropout_t* drop,
+                                            tgmx_stream_t stream) {
+  TGMX_REQUIRE(save, "dygformer_forward_train: null save block");
+  TGMX_REQUIRE(!drop || (drop->p >= 0.f && drop->p < 1.f), "dygformer_forward_train: p must be in [0, 1)");
+  if (a && a->P > 0 && a->patch > 0 && a->heads > 0 && !tgmx_mha_small_train_supported(2 * ((a->k + 1) / a->patch), 4 * a->C / a->heads)) {
+    set_error("dygformer_forward_train: %d tokens x head dimension %d is outside the attention backward's envelope", 2 * ((a->k + 1) / a->patch),
+              4 * a->C / a->heads);
+    return TGMX_E_UNSUPPORTED;
+  }
+  return dyg_forward(a, save, drop, stream);
 }

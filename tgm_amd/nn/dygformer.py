@@ -16,11 +16,26 @@ the gathered copies of ``nbr_edge_x`` & co. that ``forward`` is handed are never
 
 Inference (no gradient needed, no active dropout) is ONE native call, ``tgmx_dygformer_forward``: the launches of ``_forward_launches``
 in the same order (identical results; ``TGMX_DYGFORMER_PY`` selects the launch-by-launch twin), the argument block cached against the
-parameters' versions, the scratch kept between batches.  Training (gradients enabled, or train mode with dropout > 0) is NOT native: the
-same arithmetic composed from torch ops on the device under autograd, with the same parameters.  A shape outside the native envelope
-(more than 128 tokens per pair, a head dimension above 128, more than 2048 slots per sequence, more than 8 layers) also takes the composed
-path on the device, and so does a device that cannot give the attention kernel its LDS (``TGMX_E_UNSUPPORTED``).  A native backward is
-future work.  CPU tensors raise ``NativeLibraryError``.
+parameters' versions, the scratch kept between batches.
+
+Training (gradients enabled with a parameter that wants one, dropout included) is native too (``_dygformer_train.py``): the forward is the
+same call in its saving form, ``tgmx_dygformer_forward_train`` -- with dropout off (``.train()`` at dropout 0, or ``.eval()``) it returns
+the inference bits -- and ``loss.backward()`` is ONE call, ``tgmx_dygformer_backward``: the attention backward recomputes the
+probabilities in LDS (``tgmx_mha_small_backward``), the dense contractions run on the exact-fp32 GEMMs, every parameter gets its gradient
+(time encoder and co-occurrence encoder included; a frozen one skips its tail).  The four dropout sites of a layer (attention
+probabilities, attention output, FFN hidden, FFN output) are counter-based masks regenerated in the backward.  ``TransformerEncoder`` alone
+trains through the same layer kernels and also returns the gradient of its input.  ``TGMX_DYGFORMER_BWD`` = ``native`` (default), ``py``
+(the backward's launches one ctypes call each, same bits) or ``torch``.
+
+The composed path -- the same arithmetic from torch ops on the device under autograd, with the same parameters -- remains for what is
+outside the training envelope: ``TGMX_DYGFORMER_BWD=torch``, a gradient wanted for ``node_x`` or the edge features, autocast, parameters
+that are not contiguous float32 on one device, a custom time encoder, a layer whose ``nn.Dropout`` or attention ``dropout`` differs from
+the model's ``dropout``, a shape outside ``tgmx_mha_small_train_supported`` (the attention backward keeps Q, K, V, dO and two T x T tiles
+in LDS: 2 x 32 patches at head dimension 100 fit, 64 tokens at head dimension 128 and 128 tokens at head dimension 32 do not), and
+train-mode dropout with gradients disabled.  ``NeighborCooccurrenceEncoder.forward`` alone stays composed under gradients.  A shape outside
+the native inference envelope (more than 128 tokens per pair, a head dimension above 128, more than 2048 slots per sequence, more than 8
+layers) also takes the composed path on the device, and so does a device that cannot give the attention kernels their LDS
+(``TGMX_E_UNSUPPORTED``).  CPU tensors raise ``NativeLibraryError``.
 """
 from __future__ import annotations
 
@@ -35,6 +50,7 @@ from torch import Tensor
 
 from .. import _native
 from ..constants import PADDED_NODE_ID
+from . import _dygformer_train as _train
 from ._fwd_plumbing import Unsupported, cached_block, carve_scratch, check_supported, i32, i64, needs_torch, pair_inputs, up4, weight_keeper
 from ._paramver import TransientCaches
 from .time_encoding import Time2Vec
@@ -137,8 +153,9 @@ def _mha_in_envelope(T: int, D: int, H: int) -> bool:
 class TransformerEncoder(nn.Module):
     r"""One DyGFormer transformer layer on [B, T, d]: ``x1 = x + MHA(LN0(x))`` (self-attention over the T tokens of each batch entry, no
     mask; the residual takes the un-normalised input), ``out = x1 + Linear(GELU(Linear_4x(LN1(x1))))``.  Inference is native
-    (``tgmx_dygformer_layer``: LayerNorm, exact-fp32 MFMA GEMMs, ``tgmx_mha_small``) for T <= 128 and head dimension <= 128; otherwise,
-    and with gradients enabled or active dropout, the same arithmetic composed from torch ops on the device (NOT native)."""
+    (``tgmx_dygformer_layer``: LayerNorm, exact-fp32 MFMA GEMMs, ``tgmx_mha_small``) for T <= 128 and head dimension <= 128, and so is
+    training inside ``_dygformer_train.layer_in_envelope`` (``tgmx_dygformer_layer_train`` / ``tgmx_dygformer_layer_backward``, dropout
+    included); otherwise the same arithmetic composed from torch ops on the device (not native)."""
 
     def __init__(self, attention_dim: int, num_heads: int, dropout: float = 0.1) -> None:
         super().__init__()
@@ -163,6 +180,11 @@ class TransformerEncoder(nn.Module):
         if inputs.dim() != 3 or inputs.shape[2] != self.attention_dim:
             raise ValueError(f'TransformerEncoder expects [B, T, {self.attention_dim}], got {list(inputs.shape)}')
         B, T, D = inputs.shape
+        if _train.layer_in_envelope(self, inputs):
+            try:
+                return _train.apply_layer(self, inputs)
+            except Unsupported:  # the device cannot give the attention kernels their LDS: compose
+                return self._torch_forward(inputs)
         if needs_torch(self, self.dropout_rate, inputs) or not _mha_in_envelope(T, D, self.num_heads) or B * T == 0:
             return self._torch_forward(inputs)
         self._check_native()
@@ -233,6 +255,13 @@ class DyGFormer(TransientCaches, nn.Module):
 
     def _run(self, a: dict) -> Tuple[Tensor, Tensor]:
         grad_inputs = (a['node_x'], a['nbr_x'])
+        if _train.in_envelope(self, a):
+            for t in self.transformers:
+                t._check_native()
+            try:
+                return _train.apply(self, a)
+            except Unsupported:  # the device cannot give the attention kernels their LDS: compose
+                return self._torch_forward(a)
         if needs_torch(self, self.dropout, *grad_inputs) or not self._native_ok(a['L']):
             return self._torch_forward(a)
         for t in self.transformers:
@@ -249,7 +278,7 @@ class DyGFormer(TransientCaches, nn.Module):
                 return self._torch_forward(a)
         return out[:P], out[P:]
 
-    # -- training / outside the native envelope: torch ops under autograd (not native) ---------------------------------------------------
+    # -- outside the native envelopes: torch ops under autograd (not native) -------------------------------------------------------------
     def _torch_forward(self, a: dict) -> Tuple[Tensor, Tensor]:
         P, L, k = a['P'], a['L'], a['L'] - 1
         dev = a['node_x'].device
