@@ -56,7 +56,7 @@ int tgmx_version(void);
 /* sizeof of the argument structs as this library was compiled (a binding checks its own mirror against it):
  * 0 tgmx_adj_t, 1 tgmx_recency_step_t, 2 tgmx_tgat_layer_t, 3 tgmx_tgat_model_t, 4 tgmx_tgat_hop_t, 5 tgmx_tgat_layout_t,
  * 6 tgmx_pipeline_t, 7 tgmx_pipeline_out_t, 8 tgmx_dropout_t, 9 tgmx_tgn_memory_fwd_t, 10 tgmx_tconv_fwd_t, 11 tgmx_pipeline_post_t,
- * 12 tgmx_tgn_step_t, ..., 22 tgmx_ctan_fwd_t, 24 tgmx_gclstm_fwd_t, 26 tgmx_roland_fwd_t, 27 tgmx_decoder_fwd_t, 35 tgmx_ctan_bwd_t, 36 tgmx_graphmixer_bwd_t (23 and 25 are reserved and answer 0: tests/test_ctan_cpu.py and
+ * 12 tgmx_tgn_step_t, ..., 22 tgmx_ctan_fwd_t, 24 tgmx_gclstm_fwd_t, 26 tgmx_roland_fwd_t, 27 tgmx_decoder_fwd_t, 35 tgmx_ctan_bwd_t, 36 tgmx_graphmixer_bwd_t, 37 tgmx_dygformer_bwd_t, 38 tgmx_tpnet_bwd_t (23 and 25 are reserved and answer 0: tests/test_ctan_cpu.py and
  * tests/test_gclstm_cpu.py pin them), 28 tgmx_an_batch_t, 29 tgmx_node_analytics_t, 30 tgmx_decoder_train_t, 32 tgmx_gclstm_bwd_t (31 is
  * reserved the same way: tests/test_decoder_train_cpu.py) */
 size_t tgmx_abi_sizeof(int32_t which);
@@ -1368,6 +1368,82 @@ typedef struct tgmx_tpnet_fwd {
   float* out;                                                                      /* [2 B, E] */
 } tgmx_tpnet_fwd_t;
 int tgmx_tpnet_forward(const tgmx_tpnet_fwd_t* args, tgmx_stream_t stream);
+
+/* ---- TPNet training (csrc/tpnet.hip, csrc/tpnet_bwd.hip; composed by tgm_amd/nn/_tpnet_train.py) ---- */
+
+/* 1 when a sequence's [K, C] tile with token hidden width Ht fits the token forward's LDS (as tgmx_mixer_train_supported) AND
+ * tgmx_tpnet_token_backward's: 4 (4 K + 2 Ht) (n + 1) bytes at n = 128, 64 or 32 channels a pass (the widest within 64 KiB), with the
+ * partial row of 2 K Ht + 3 K + Ht floats held in registers, at most 24 a thread of that pass.  The host decides the training path with
+ * this at forward time. */
+int tgmx_tpnet_train_supported(int32_t K, int32_t C, int32_t Ht);
+
+/* tgmx_tpnet_token_mix with the block's two dropout sites, indexed as tgmx_mixer_token_train's; both off: the bits of tgmx_tpnet_token_mix. */
+int tgmx_tpnet_token_mix_train(const float* x, int64_t ldx, int64_t S, int32_t K, int32_t C, const float* tok_g, const float* tok_b,
+                               const float* w1, const float* b1, int32_t Ht, const float* w2, const float* b2, const float* ch_g,
+                               const float* ch_b, float eps, float* z1, float* y, int64_t ldo, const tgmx_dropout_t* drop_hidden,
+                               const tgmx_dropout_t* drop_out, tgmx_stream_t stream);
+
+/* tgmx_tpnet_forward in its saving form: the same launches in the same order.  args->feat, feat_h, x0 and hp are the caller's to keep (the
+ * backward reads them; pf, y, h, z1 stay scratch); layer l reads its input from save->z + l 2 B k ldz and leaves its token block's output
+ * in save->z1 + l 2 B k ldz (args->z receives the last layer's output); save->lg [2 B k] doubles: per token row lg = log(gap + 1), the
+ * double the forward feeds the cosine, or -1 on a pad slot (no integer's logarithm).  drop: p, seed and the call's first stream over
+ * Q = 2 B sequences, sites as tgmx_graphmixer_forward_train's; NULL or p = 0 = off, and out is then the bits of tgmx_tpnet_forward. */
+typedef struct tgmx_tpnet_save {
+  float *z, *z1;
+  double* lg;
+} tgmx_tpnet_save_t;
+int tgmx_tpnet_forward_train(const tgmx_tpnet_fwd_t* args, const tgmx_tpnet_save_t* save, const tgmx_dropout_t* drop, tgmx_stream_t stream);
+
+/* dz[q k + j, :C] = g[q, :C] / k: the backward of tgmx_tpnet_mean (TPNet's mean is not masked). */
+int tgmx_tpnet_mean_backward(const float* g, int64_t ldg, int64_t Q, int32_t k, int32_t C, float* dz, int64_t ldz, tgmx_stream_t stream);
+
+/* rows [R, 2 dT] = [ -sin(fma(w, lg, b)) d lg | -sin(.) d ] per token row from d = dtime [R, ldt] (the gradient at the time columns of the
+ * token matrix) and the forward's lg [R]; a pad row (lg < 0) is 0.  Evaluated in double, rounded once.  tgmx_colsum of the two halves is
+ * d time_encoder.w.{weight, bias}. */
+int tgmx_tpnet_time_backward(const float* dtime, int64_t ldt, const double* lg, int64_t R, const float* tw, const float* tb, int32_t dT,
+                             float* rows, tgmx_stream_t stream);
+
+/* Backward of TPNet's token block (tgmx_tpnet_token_mix_train): tgmx_mixer_token_backward with the forward's refined column mean (a constant
+ * column gives var = 0 and xhat = 0 exactly), and with the parameter gradients reduced per sequence instead of written per column: row q of
+ * part [Q, ldp] (may be NULL: no parameter gradient wanted; dx has the same bits), ldp >= 2 K Ht + 3 K + Ht, is
+ *   [ do^T hd (K x Ht) | da^T xn (Ht x K) | sum do (K) | sum dxn (K) | sum dxn xhat (K) | sum da (Ht) ]
+ * summed over the sequence's C columns in a fixed order (channels ascending), i.e. the sequence's share of
+ *   [ d ffn.3.weight | d ffn.0.weight | d ffn.3.bias | d token_norm.bias | d token_norm.weight | d ffn.0.bias ];
+ * ONE tgmx_colsum over the Q rows gives all six.  Outside tgmx_tpnet_train_supported: TGMX_E_UNSUPPORTED. */
+int tgmx_tpnet_token_backward(const float* x, int64_t ldx, const float* dz1, int64_t ldd, int64_t Q, int32_t K, int32_t C, const float* tok_g,
+                              const float* tok_b, const float* w1, const float* b1, int32_t Ht, const float* w2, float eps, float* dx,
+                              int64_t ldo, float* part, int64_t ldp, const tgmx_dropout_t* drop_hidden, const tgmx_dropout_t* drop_out,
+                              tgmx_stream_t stream);
+
+/* The backward of tgmx_tpnet_forward_train as ONE call (tgmx_abi_sizeof(38)), g = dL/d[z_src; z_dst] [2 B, E].  It reads what that forward
+ * kept (feat, feat_h, x0, hp, save_z, save_z1, lg) and packed copies of the weights (one tgmx_pack2d) -- none of the caller's input tensors:
+ *   proj_w2T [2 E, E]; w0T_time [dT, 2 E], w0T_pair0 / w0T_pair1 [od, 2 E]: the transposed column slices of proj_w0 that somebody reads;
+ *   rp_w2T [4 od, od]; per layer ch_w1T [E, Hc], ch_w2T [Hc, E].
+ * Every gradient pointer may be NULL: not wanted, and the launches that feed only it are skipped; gradients are written, not accumulated,
+ * in the parameters' own layouts.  d_tok[l]: the six token-block gradients of layer l as ONE buffer of 2 K Ht + 3 K + Ht floats in
+ * tgmx_tpnet_token_backward's column order (d_layers[l].tok_* are not read).  No float atomics: two runs give the same bits.  Order:
+ *   tgmx_tpnet_mean_backward -> gz;  per layer, last first: the channel block (tgmx_graphmixer_backward's launches), then
+ *   tgmx_tpnet_token_backward -> gz, part and one tgmx_colsum(part) -> d_tok[l];
+ *   d proj_w2 = gz^T hp, d proj_b2 = colsum(gz), dhp = gz W2 (tgmx_sgemm_nt_ep on proj_w2T), tgmx_relu_mask by hp, d proj_w0 = dhp^T x0,
+ *   d proj_b0 = colsum(dhp); dtime = dhp w0T_time^T, tgmx_tpnet_time_backward, two tgmx_colsum -> d_tw, d_tb;
+ *   dpf[0:R] = dhp w0T_pair0^T, dpf[R:2R] = dhp w0T_pair1^T; d rp_w2 = dpf^T feat_h, d rp_b2 = colsum(dpf), dfh = dpf W2 (rp_w2T),
+ *   tgmx_relu_mask by feat_h, d rp_w1 = dfh^T feat, d rp_b1 = colsum(dfh).
+ * The chain stops at the lowest stage that still has a gradient wanted at or below it. */
+typedef struct tgmx_tpnet_bwd {
+  int64_t B; int32_t k, dN, dE, dT, E, od, num_layers; float eps; float drop_p; uint64_t drop_seed, drop_stream;
+  const float* g; int64_t ldg;
+  const float *feat, *feat_h, *x0, *hp, *save_z, *save_z1; const double* lg; int64_t ldf, ldfh, ldx0, ldhp, ldz, ldh;
+  const float *tw, *tb;
+  tgmx_mixer_layer_t layers[TGMX_MIXER_MAX_LAYERS];
+  const float* ch_w1T[TGMX_MIXER_MAX_LAYERS]; const float* ch_w2T[TGMX_MIXER_MAX_LAYERS];
+  const float *proj_w2T, *w0T_time, *w0T_pair0, *w0T_pair1, *rp_w2T;
+  float *d_tw, *d_tb, *d_proj_w0, *d_proj_b0, *d_proj_w2, *d_proj_b2, *d_rp_w1, *d_rp_b1, *d_rp_w2, *d_rp_b2;
+  tgmx_mixer_layer_grad_t d_layers[TGMX_MIXER_MAX_LAYERS];
+  float* d_tok[TGMX_MIXER_MAX_LAYERS];
+  void* workspace; size_t workspace_bytes;
+} tgmx_tpnet_bwd_t;
+size_t tgmx_tpnet_backward_workspace_bytes(const tgmx_tpnet_bwd_t* args);
+int tgmx_tpnet_backward(const tgmx_tpnet_bwd_t* args, tgmx_stream_t stream);
 
 /* ---- NCNPredictor (the reference's tgm/nn/decoder/ncnpred.py): the common-neighbour decoder of TNCN, forward ---- */
 

@@ -556,6 +556,43 @@ SIGNATURES['tgmx_tpnet_mean'] = (c_int32, [_P, c_int64, c_int64, c_int32, c_int3
 SIGNATURES['tgmx_tpnet_forward'] = (c_int32, [ctypes.POINTER(TPNetFwd), _P])
 
 
+class TPNetSave(ctypes.Structure):
+    """tgmx_tpnet_save_t (include/tgm_amd.h)."""
+
+    _fields_ = [('z', c_void_p), ('z1', c_void_p), ('lg', c_void_p)]
+
+
+class TPNetBwd(ctypes.Structure):
+    """tgmx_tpnet_bwd_t (include/tgm_amd.h)."""
+
+    _fields_ = [
+        ('B', c_int64), ('k', c_int32), ('dN', c_int32), ('dE', c_int32), ('dT', c_int32), ('E', c_int32), ('od', c_int32), ('num_layers', c_int32),
+        ('eps', ctypes.c_float), ('drop_p', ctypes.c_float), ('drop_seed', ctypes.c_uint64), ('drop_stream', ctypes.c_uint64),
+        ('g', c_void_p), ('ldg', c_int64),
+        ('feat', c_void_p), ('feat_h', c_void_p), ('x0', c_void_p), ('hp', c_void_p), ('save_z', c_void_p), ('save_z1', c_void_p), ('lg', c_void_p),
+        ('ldf', c_int64), ('ldfh', c_int64), ('ldx0', c_int64), ('ldhp', c_int64), ('ldz', c_int64), ('ldh', c_int64),
+        ('tw', c_void_p), ('tb', c_void_p),
+        ('layers', MixerLayer * MIXER_MAX_LAYERS),
+        ('ch_w1T', c_void_p * MIXER_MAX_LAYERS), ('ch_w2T', c_void_p * MIXER_MAX_LAYERS),
+        ('proj_w2T', c_void_p), ('w0T_time', c_void_p), ('w0T_pair0', c_void_p), ('w0T_pair1', c_void_p), ('rp_w2T', c_void_p),
+        ('d_tw', c_void_p), ('d_tb', c_void_p), ('d_proj_w0', c_void_p), ('d_proj_b0', c_void_p), ('d_proj_w2', c_void_p), ('d_proj_b2', c_void_p),
+        ('d_rp_w1', c_void_p), ('d_rp_b1', c_void_p), ('d_rp_w2', c_void_p), ('d_rp_b2', c_void_p),
+        ('d_layers', MixerLayerGrad * MIXER_MAX_LAYERS),
+        ('d_tok', c_void_p * MIXER_MAX_LAYERS),
+        ('workspace', c_void_p), ('workspace_bytes', c_size_t),
+    ]  # fmt: skip
+
+
+SIGNATURES['tgmx_tpnet_train_supported'] = (c_int32, [c_int32, c_int32, c_int32])
+SIGNATURES['tgmx_tpnet_token_mix_train'] = SIGNATURES['tgmx_mixer_token_train']
+SIGNATURES['tgmx_tpnet_forward_train'] = (c_int32, [ctypes.POINTER(TPNetFwd), ctypes.POINTER(TPNetSave), _P, _P])
+SIGNATURES['tgmx_tpnet_mean_backward'] = (c_int32, [_P, c_int64, c_int64, c_int32, c_int32, _P, c_int64, _P])
+SIGNATURES['tgmx_tpnet_time_backward'] = (c_int32, [_P, c_int64, _P, c_int64, _P, _P, c_int32, _P, _P])
+SIGNATURES['tgmx_tpnet_token_backward'] = SIGNATURES['tgmx_mixer_token_backward']
+SIGNATURES['tgmx_tpnet_backward_workspace_bytes'] = (c_size_t, [ctypes.POINTER(TPNetBwd)])
+SIGNATURES['tgmx_tpnet_backward'] = (c_int32, [ctypes.POINTER(TPNetBwd), _P])
+
+
 class NCNFwd(ctypes.Structure):
     """tgmx_ncn_fwd_t (include/tgm_amd.h)."""
 

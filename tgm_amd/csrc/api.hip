@@ -53,6 +53,7 @@ extern "C" size_t tgmx_abi_sizeof(int32_t which) {
     case 35: return sizeof(tgmx_ctan_bwd_t);  // (34 stays 0 for the same reason)
     case 36: return sizeof(tgmx_graphmixer_bwd_t);
     case 37: return sizeof(tgmx_dygformer_bwd_t);
+    case 38: return sizeof(tgmx_tpnet_bwd_t);
     default: return 0;
   }
 }

@@ -332,6 +332,29 @@ struct GemmCall {
 // tgmx_tpnet_forward.
 int mixer_layers_run(bool refine, const tgmx_mixer_layer_t* layers, int num_layers, int64_t S, int32_t K, int32_t C, float eps, float* z, float* z1,
                      float* y, int64_t ldz, float* h, int64_t ldh, tgmx_stream_t stream);
+// its saving form (training): layer l reads save_z + l S K ldz, keeps its token block's output in save_z1 + l S K ldz, the last layer writes
+// z_last; drop: the call's dropout descriptor (site s of layer l: stream + 4 l + s), NULL = off.  tgmx_graphmixer_forward_train's and
+// tgmx_tpnet_forward_train's loop.
+int mixer_layers_run_train(bool refine, const tgmx_mixer_layer_t* layers, int num_layers, int64_t S, int32_t K, int32_t C, float eps, float* save_z,
+                           float* save_z1, float* z_last, float* y, int64_t ldz, float* h, int64_t ldh, const tgmx_dropout_t* drop,
+                           tgmx_stream_t stream);
+
+// The channel block of one MLPMixer layer, backward (csrc/mixer_bwd.hip; tgmx_graphmixer_backward's steps 3a-3d and tgmx_tpnet_backward's):
+// from gz = the gradient at the layer's output and the saved z1, the channel FFN's and channel_norm's wanted gradients, and -- down: somebody
+// reads it -- dz1 = LN_C backward + the residual, left in b.du.  site: the layer's four dropout sites (2 and 3 are read).
+struct MixerChannelBufs {
+  float *abuf, *hbuf;            // [R, ldh]
+  float *y, *dy, *du, *dgx, *gt;  // [R, ldz] (gt: only when dropping)
+  float *zero, *tn_ws, *cs_ws;   // a zeroed row of ldz floats; tgmx_sgemm_tn's and tgmx_colsum's workspaces
+};
+int mixer_channel_backward(const tgmx_mixer_layer_t& ly, const tgmx_mixer_layer_grad_t& d, const float* ch_w1T, const float* ch_w2T, const float* z1,
+                           const float* gz, int64_t R, int32_t D, int64_t ldz, int64_t ldh, float eps, const tgmx_dropout_t* site, bool down,
+                           const MixerChannelBufs& b, tgmx_stream_t stream);
+
+// tgmx_tpnet_token_backward (csrc/tpnet_bwd.hip): the per-sequence partial row is 2 K Ht + 3 K + Ht floats, kept in registers,
+// kTpTokAcc entries a thread, by the workgroup of 128, 64 or 32 threads that mixer_token_bwd_threads picks.
+constexpr int kTpTokAcc = 24;
+inline int tpnet_token_part_floats(int K, int Ht) { return 2 * K * Ht + 3 * K + Ht; }
 
 // dynamic LDS of the token kernels, per workgroup (one seed): the forward keeps the seed's [K][C] tile and a chunk's normalised column and
 // hidden activations (csrc/mixer.hip); the backward keeps a chunk's 4 K + 2 Ht per-column values at a pitch of threads + 1 floats, in chunks

@@ -299,8 +299,10 @@ static int mixer_token_run(bool refine, const float* x, int64_t ldx, int64_t S, 
   }
   const DropoutArgs d0 = make_dropout(drop_hidden), d1 = make_dropout(drop_out);
   const bool drop = d0.thresh != 0 || d1.thresh != 0;
-  TGMX_REQUIRE(!(refine && drop), "mixer_token: the refined mean has no training form");
-  if (refine)
+  if (refine && drop)
+    hipLaunchKernelGGL((mixer_token_kernel<true, true>), dim3((unsigned)S), dim3(kTokThreads), lds, (hipStream_t)stream, x, (long long)ldx, K, C, tok_g,
+                       tok_b, w1, b1, Ht, w2, b2, ch_g, ch_b, eps, z1, y, (long long)ldo, d0, d1);
+  else if (refine)
     hipLaunchKernelGGL((mixer_token_kernel<true, false>), dim3((unsigned)S), dim3(kTokThreads), lds, (hipStream_t)stream, x, (long long)ldx, K, C, tok_g,
                        tok_b, w1, b1, Ht, w2, b2, ch_g, ch_b, eps, z1, y, (long long)ldo, d0, d1);
   else if (drop)
@@ -328,6 +330,46 @@ int tgmx::mixer_layers_run(bool refine, const tgmx_mixer_layer_t* layers, int nu
   return TGMX_OK;
 }
 
+// the saving form of mixer_layers_run (training): layer l reads its input from save_z + l R ldz, leaves its token block's output in
+// save_z1 + l R ldz and writes its output to layer l + 1's input, the last one to z_last.  drop: the sites' common descriptor (site s of
+// layer l draws from stream + 4 l + s), NULL or p = 0 = off -- then the launches are mixer_layers_run's, writing elsewhere.
+int tgmx::mixer_layers_run_train(bool refine, const tgmx_mixer_layer_t* layers, int num_layers, int64_t S, int32_t K, int32_t C, float eps,
+                                 float* save_z, float* save_z1, float* z_last, float* y, int64_t ldz, float* h, int64_t ldh,
+                                 const tgmx_dropout_t* drop, tgmx_stream_t stream) {
+  const long long R = (long long)S * K;
+  const int L = num_layers;
+  const bool dropping = drop && drop->p > 0.f;
+  const size_t per = (size_t)R * ldz;
+  float* z_in = save_z;
+  int rc;
+  for (int l = 0; l < L; ++l) {
+    const tgmx_mixer_layer_t& ly = layers[l];
+    float* z1 = save_z1 + l * per;
+    float* z_out = l + 1 < L ? save_z + (l + 1) * per : z_last;
+    tgmx_dropout_t site[4];
+    for (int s = 0; s < 4; ++s) {
+      site[s].p = dropping ? drop->p : 0.f;
+      site[s].seed = dropping ? drop->seed : 0;
+      site[s].stream = dropping ? drop->stream + 4ull * l + s : 0;
+      site[s].row0 = 0;
+    }
+    if ((rc = mixer_token_run(refine, z_in, ldz, S, K, C, ly.tok_g, ly.tok_b, ly.tok_w1, ly.tok_b1, ly.tok_hidden, ly.tok_w2, ly.tok_b2, ly.ch_g, ly.ch_b,
+                              eps, z1, y, ldz, stream, &site[0], &site[1])))
+      return rc;
+    if ((rc = tgmx_sgemm_nt_ep(y, ldz, ly.ch_w1, C, h, ldh, R, ly.ch_hidden, C, ly.ch_b1, 2, nullptr, 0, stream))) return rc;
+    if (!dropping) {
+      if ((rc = tgmx_sgemm_nt_ep(h, ldh, ly.ch_w2, ly.ch_hidden, z_out, ldz, R, C, ly.ch_hidden, ly.ch_b2, 0, z1, ldz, stream))) return rc;
+    } else {
+      if ((rc = tgmx_dropout(h, ldh, R, ly.ch_hidden, &site[2], h, ldh, stream))) return rc;
+      if ((rc = tgmx_sgemm_nt_ep(h, ldh, ly.ch_w2, ly.ch_hidden, z_out, ldz, R, C, ly.ch_hidden, ly.ch_b2, 0, nullptr, 0, stream))) return rc;
+      if ((rc = tgmx_dropout(z_out, ldz, R, C, &site[3], z_out, ldz, stream))) return rc;
+      if ((rc = tgmx_add_cols(z_out, ldz, z1, ldz, R, C, 1, stream))) return rc;
+    }
+    z_in = z_out;
+  }
+  return TGMX_OK;
+}
+
 extern "C" int tgmx_mixer_token(const float* x, int64_t ldx, int64_t S, int32_t K, int32_t C, const float* tok_g, const float* tok_b,
                                 const float* w1, const float* b1, int32_t Ht, const float* w2, const float* b2, const float* ch_g,
                                 const float* ch_b, float eps, float* z1, float* y, int64_t ldo, tgmx_stream_t stream) {
@@ -345,6 +387,13 @@ extern "C" int tgmx_tpnet_token_mix(const float* x, int64_t ldx, int64_t S, int3
                                     const float* w1, const float* b1, int32_t Ht, const float* w2, const float* b2, const float* ch_g,
                                     const float* ch_b, float eps, float* z1, float* y, int64_t ldo, tgmx_stream_t stream) {
   return mixer_token_run(true, x, ldx, S, K, C, tok_g, tok_b, w1, b1, Ht, w2, b2, ch_g, ch_b, eps, z1, y, ldo, stream);
+}
+
+extern "C" int tgmx_tpnet_token_mix_train(const float* x, int64_t ldx, int64_t S, int32_t K, int32_t C, const float* tok_g, const float* tok_b,
+                                          const float* w1, const float* b1, int32_t Ht, const float* w2, const float* b2, const float* ch_g,
+                                          const float* ch_b, float eps, float* z1, float* y, int64_t ldo, const tgmx_dropout_t* drop_hidden,
+                                          const tgmx_dropout_t* drop_out, tgmx_stream_t stream) {
+  return mixer_token_run(true, x, ldx, S, K, C, tok_g, tok_b, w1, b1, Ht, w2, b2, ch_g, ch_b, eps, z1, y, ldo, stream, drop_hidden, drop_out);
 }
 
 extern "C" int tgmx_mixer_tail(const float* z, int64_t ldz, int64_t S, int32_t K, int32_t C, const int32_t* nbr_nids, const float* node_x,
@@ -382,32 +431,7 @@ static int graphmixer_forward_run(const tgmx_graphmixer_fwd_t* a, float* save_z,
   if (!save) {
     if ((rc = mixer_layers_run(false, a->layers, L, S, a->K, D, a->eps, a->z, a->z1, a->y, a->ldz, a->h, a->ldh, stream))) return rc;
   } else {
-    const size_t per = (size_t)R * a->ldz;
-    for (int l = 0; l < L; ++l) {
-      const tgmx_mixer_layer_t& ly = a->layers[l];
-      float* z1 = save_z1 + l * per;
-      float* z_out = l + 1 < L ? save_z + (l + 1) * per : a->z;
-      tgmx_dropout_t site[4];
-      for (int s = 0; s < 4; ++s) {
-        site[s].p = dropping ? drop->p : 0.f;
-        site[s].seed = dropping ? drop->seed : 0;
-        site[s].stream = dropping ? drop->stream + 4ull * l + s : 0;
-        site[s].row0 = 0;
-      }
-      if ((rc = mixer_token_run(false, z_in, a->ldz, S, a->K, D, ly.tok_g, ly.tok_b, ly.tok_w1, ly.tok_b1, ly.tok_hidden, ly.tok_w2, ly.tok_b2, ly.ch_g,
-                                ly.ch_b, a->eps, z1, a->y, a->ldz, stream, &site[0], &site[1])))
-        return rc;
-      if ((rc = tgmx_sgemm_nt_ep(a->y, a->ldz, ly.ch_w1, D, a->h, a->ldh, R, ly.ch_hidden, D, ly.ch_b1, 2, nullptr, 0, stream))) return rc;
-      if (!dropping) {
-        if ((rc = tgmx_sgemm_nt_ep(a->h, a->ldh, ly.ch_w2, ly.ch_hidden, z_out, a->ldz, R, D, ly.ch_hidden, ly.ch_b2, 0, z1, a->ldz, stream))) return rc;
-      } else {
-        if ((rc = tgmx_dropout(a->h, a->ldh, R, ly.ch_hidden, &site[2], a->h, a->ldh, stream))) return rc;
-        if ((rc = tgmx_sgemm_nt_ep(a->h, a->ldh, ly.ch_w2, ly.ch_hidden, z_out, a->ldz, R, D, ly.ch_hidden, ly.ch_b2, 0, nullptr, 0, stream))) return rc;
-        if ((rc = tgmx_dropout(z_out, a->ldz, R, D, &site[3], z_out, a->ldz, stream))) return rc;
-        if ((rc = tgmx_add_cols(z_out, a->ldz, z1, a->ldz, R, D, 1, stream))) return rc;
-      }
-      z_in = z_out;
-    }
+    if ((rc = mixer_layers_run_train(false, a->layers, L, S, a->K, D, a->eps, save_z, save_z1, a->z, a->y, a->ldz, a->h, a->ldh, drop, stream))) return rc;
   }
   if ((rc = tgmx_mixer_tail(a->z, a->ldz, S, a->K, D, a->nbr_nids, a->node_x, a->num_nodes, a->F, a->tg_nbr, a->tg_lo, a->tg_cnt, a->seeds[0],
                             a->n_seeds[0], a->seeds[1], a->n_seeds[1], a->seeds[2], a->cat, a->ldcat, stream)))

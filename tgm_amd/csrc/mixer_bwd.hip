@@ -249,6 +249,37 @@ extern "C" int tgmx_mixer_channel_norm(const float* z1, int64_t ldz, int64_t R, 
   return TGMX_OK;
 }
 
+// ---- the channel block of a layer (shared with csrc/tpnet_bwd.hip) -------------------------------------------------------------------------------
+int tgmx::mixer_channel_backward(const tgmx_mixer_layer_t& ly, const tgmx_mixer_layer_grad_t& d, const float* ch_w1T, const float* ch_w2T,
+                                 const float* z1, const float* gz, int64_t R, int32_t D, int64_t ldz, int64_t ldh, float eps,
+                                 const tgmx_dropout_t* site, bool down, const MixerChannelBufs& b, tgmx_stream_t stream) {
+  const int hc = ly.ch_hidden;
+  const bool dropping = site[3].p > 0.f;
+  float *abuf = b.abuf, *hbuf = b.hbuf, *y = b.y, *dy = b.dy, *du = b.du, *dgx = b.dgx, *gt = b.gt, *tn_ws = b.tn_ws, *cs_ws = b.cs_ws;
+  int rc;
+  if ((rc = tgmx_mixer_channel_norm(z1, ldz, R, D, ly.ch_g, ly.ch_b, eps, y, ldz, stream))) return rc;
+  if ((rc = tgmx_sgemm_nt_ep(y, ldz, ly.ch_w1, D, abuf, ldh, R, hc, D, ly.ch_b1, 0, nullptr, 0, stream))) return rc;
+  const float* g3 = gz;
+  if (dropping) {
+    if ((rc = tgmx_dropout(gz, ldz, R, D, &site[3], gt, ldz, stream))) return rc;
+    g3 = gt;
+  }
+  if ((rc = tgmx_sgemm_nt_ep(g3, ldz, ch_w2T, D, hbuf, ldh, R, hc, D, nullptr, 0, nullptr, 0, stream))) return rc;
+  if ((rc = tgmx_mixer_gelu_backward(abuf, ldh, hbuf, ldh, R, hc, &site[2], stream))) return rc;
+  if (d.ch_w2 && (rc = tgmx_sgemm_tn(g3, ldz, abuf, ldh, d.ch_w2, hc, R, D, hc, 1, 0, 0, 0, 0, tn_ws, stream))) return rc;
+  if (d.ch_b2 && (rc = tgmx_colsum(g3, ldz, R, D, d.ch_b2, 0, cs_ws, stream))) return rc;
+  if (d.ch_w1 && (rc = tgmx_sgemm_tn(hbuf, ldh, y, ldz, d.ch_w1, D, R, hc, D, 1, 0, 0, 0, 0, tn_ws, stream))) return rc;
+  if (d.ch_b1 && (rc = tgmx_colsum(hbuf, ldh, R, hc, d.ch_b1, 0, cs_ws, stream))) return rc;
+  if (d.ch_g || d.ch_b || down) {
+    if ((rc = tgmx_sgemm_nt_ep(hbuf, ldh, ch_w1T, hc, dy, ldz, R, D, hc, nullptr, 0, nullptr, 0, stream))) return rc;
+    if ((rc = tgmx_ln_backward(dy, ldz, z1, ldz, b.zero, 0, ly.ch_g, D, eps, R, du, ldz, dgx, ldz, stream))) return rc;
+    if (d.ch_g && (rc = tgmx_colsum(dgx, ldz, R, D, d.ch_g, 0, cs_ws, stream))) return rc;
+    if (d.ch_b && (rc = tgmx_colsum(dy, ldz, R, D, d.ch_b, 0, cs_ws, stream))) return rc;
+  }
+  if (!down) return TGMX_OK;
+  return tgmx_add_cols(du, ldz, gz, ldz, R, D, 1, stream);  // dz1 = the LayerNorm's backward + the residual
+}
+
 // ---- the whole backward as one call ---------------------------------------------------------------------------------------------------------
 static bool tok_wanted(const tgmx_mixer_layer_grad_t& d) { return d.tok_g || d.tok_b || d.tok_w1 || d.tok_b1 || d.tok_w2 || d.tok_b2; }
 static bool ch_wanted(const tgmx_mixer_layer_grad_t& d) { return d.ch_g || d.ch_b || d.ch_w1 || d.ch_b1 || d.ch_w2 || d.ch_b2; }
@@ -343,37 +374,18 @@ static int gm_backward_pass(const tgmx_graphmixer_bwd_t* a, bool dry, size_t* ne
     return TGMX_E_LAUNCH;
   }
   const size_t per = (size_t)R * ldz;
+  const MixerChannelBufs cb{abuf, hbuf, y, dy, du, dgx, gt, zero, tn_ws, cs_ws};
   for (int l = L - 1; l >= lowest; --l) {
     const tgmx_mixer_layer_t& ly = a->layers[l];
     const tgmx_mixer_layer_grad_t& d = a->d_layers[l];
-    const int hc = ly.ch_hidden, ht = ly.tok_hidden;
+    const int ht = ly.tok_hidden;
     const float* z_in = a->save_z + l * per;
     const float* z1 = a->save_z1 + l * per;
     const bool tok = tok_wanted(d), down = tok || l > lowest || want_proj;  // somebody reads dz1
     tgmx_dropout_t site[4];
     for (int s = 0; s < 4; ++s) site[s] = tgmx_dropout_t{a->drop_p, a->drop_seed, a->drop_stream + 4ull * l + s, 0};
-    // the channel FFN
-    if ((rc = tgmx_mixer_channel_norm(z1, ldz, R, D, ly.ch_g, ly.ch_b, a->eps, y, ldz, stream))) return rc;
-    if ((rc = tgmx_sgemm_nt_ep(y, ldz, ly.ch_w1, D, abuf, ldh, R, hc, D, ly.ch_b1, 0, nullptr, 0, stream))) return rc;
-    const float* g3 = gz;
-    if (dropping) {
-      if ((rc = tgmx_dropout(gz, ldz, R, D, &site[3], gt, ldz, stream))) return rc;
-      g3 = gt;
-    }
-    if ((rc = tgmx_sgemm_nt_ep(g3, ldz, a->ch_w2T[l], D, hbuf, ldh, R, hc, D, nullptr, 0, nullptr, 0, stream))) return rc;
-    if ((rc = tgmx_mixer_gelu_backward(abuf, ldh, hbuf, ldh, R, hc, &site[2], stream))) return rc;
-    if (d.ch_w2 && (rc = tgmx_sgemm_tn(g3, ldz, abuf, ldh, d.ch_w2, hc, R, D, hc, 1, 0, 0, 0, 0, tn_ws, stream))) return rc;
-    if (d.ch_b2 && (rc = tgmx_colsum(g3, ldz, R, D, d.ch_b2, 0, cs_ws, stream))) return rc;
-    if (d.ch_w1 && (rc = tgmx_sgemm_tn(hbuf, ldh, y, ldz, d.ch_w1, D, R, hc, D, 1, 0, 0, 0, 0, tn_ws, stream))) return rc;
-    if (d.ch_b1 && (rc = tgmx_colsum(hbuf, ldh, R, hc, d.ch_b1, 0, cs_ws, stream))) return rc;
-    if (d.ch_g || d.ch_b || down) {
-      if ((rc = tgmx_sgemm_nt_ep(hbuf, ldh, a->ch_w1T[l], hc, dy, ldz, R, D, hc, nullptr, 0, nullptr, 0, stream))) return rc;
-      if ((rc = tgmx_ln_backward(dy, ldz, z1, ldz, zero, 0, ly.ch_g, D, a->eps, R, du, ldz, dgx, ldz, stream))) return rc;
-      if (d.ch_g && (rc = tgmx_colsum(dgx, ldz, R, D, d.ch_g, 0, cs_ws, stream))) return rc;
-      if (d.ch_b && (rc = tgmx_colsum(dy, ldz, R, D, d.ch_b, 0, cs_ws, stream))) return rc;
-    }
+    if ((rc = mixer_channel_backward(ly, d, a->ch_w1T[l], a->ch_w2T[l], z1, gz, R, D, ldz, ldh, a->eps, site, down, cb, stream))) return rc;
     if (!down) break;
-    if ((rc = tgmx_add_cols(du, ldz, gz, ldz, R, D, 1, stream))) return rc;  // dz1 = the LayerNorm's backward + the residual
     // the token block
     if ((rc = tgmx_mixer_token_backward(z_in, ldz, du, ldz, S, K, D, ly.tok_g, ly.tok_b, ly.tok_w1, ly.tok_b1, ht, ly.tok_w2, a->eps, gz2, ldz,
                                         tok ? rows : nullptr, ldw, &site[0], &site[1], stream)))

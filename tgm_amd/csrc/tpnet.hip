@@ -203,7 +203,7 @@ __global__ __launch_bounds__(kTpThreads) void tpnet_tokens_kernel(const float* _
                                                                  const int32_t* __restrict__ rows,
                                                                  const float* __restrict__ tw, const float* __restrict__ tbias, int dT,
                                                                  const float* __restrict__ pf, long long ldpf, int pfd, float* __restrict__ out,
-                                                                 long long ldo) {
+                                                                 long long ldo, double* __restrict__ lg_out) {
   const int lane = lane_id();
   const long long wave = (long long)blockIdx.x * kTpWaves + threadIdx.x / kWave;
   const long long nwaves = (long long)gridDim.x * kTpWaves;
@@ -220,6 +220,7 @@ __global__ __launch_bounds__(kTpThreads) void tpnet_tokens_kernel(const float* _
     const bool has_x = !pad && id >= 0 && id < num_nodes;
     // the reference takes log of the int64 gap + 1 and feeds Time2Vec; here in double up to the cosine, rounded once
     const double lg = pad ? 0.0 : log((double)(edge_time[p] - nbr_t[slot] + 1));
+    if (lg_out && lane == 0) lg_out[row] = pad ? -1.0 : lg;  // (training: what the time encoder's backward needs of the caller's tensors)
     float* __restrict__ o = out + row * ldo;
     for (int c = lane; c < dN; c += kWave) o[c] = has_x ? node_x[(long long)id * dN + c] : 0.f;
     for (int c = lane; c < dT; c += kWave) o[dN + c] = pad ? 0.f : (float)cos(fma((double)tw[c], lg, (double)tbias[c]));
@@ -321,9 +322,9 @@ extern "C" int tgmx_tpnet_pair_features(const tgmx_tpnet_tables_t* tables, const
   return TGMX_OK;
 }
 
-extern "C" int tgmx_tpnet_tokens(const float* node_x, int64_t num_nodes, int32_t dN, const int64_t* edge_time, int64_t B,
-                                 const int32_t* nbr_nids, const int64_t* nbr_t, const float* nbr_x, int64_t S, int32_t k, int32_t dE,
-                                 const int32_t* rows, const float* tw, const float* tb, int32_t dT, const float* pf, int64_t ldpf, int32_t pf_dim, float* out, int64_t ldo, tgmx_stream_t stream) {
+static int tokens_run(const float* node_x, int64_t num_nodes, int32_t dN, const int64_t* edge_time, int64_t B, const int32_t* nbr_nids,
+                      const int64_t* nbr_t, const float* nbr_x, int64_t S, int32_t k, int32_t dE, const int32_t* rows, const float* tw, const float* tb,
+                      int32_t dT, const float* pf, int64_t ldpf, int32_t pf_dim, float* out, int64_t ldo, double* lg_out, tgmx_stream_t stream) {
   TGMX_REQUIRE(B >= 0 && S >= 0 && k > 0 && dN >= 0 && dE >= 0 && dT >= 0 && pf_dim >= 0 && num_nodes >= 0 && ldpf >= pf_dim &&
                    ldo >= (int64_t)dN + dT + dE + 2 * pf_dim,
                "tpnet_tokens: bad sizes B=%lld k=%d dN=%d dT=%d dE=%d pf_dim=%d ldo=%lld", (long long)B, k, dN, dT, dE, pf_dim, (long long)ldo);
@@ -333,9 +334,15 @@ extern "C" int tgmx_tpnet_tokens(const float* node_x, int64_t num_nodes, int32_t
                "tpnet_tokens: null pointer");
   hipLaunchKernelGGL(tpnet_tokens_kernel, dim3(wave_blocks(2 * B * k)), dim3(kTpThreads), 0, (hipStream_t)stream, node_x, (long long)num_nodes, dN,
                      edge_time, (long long)B, nbr_nids, nbr_t, nbr_x, (long long)S, k, dE, rows, tw, tb, dT, pf, (long long)ldpf, pf_dim,
-                     out, (long long)ldo);
+                     out, (long long)ldo, lg_out);
   TGMX_CHECK_LAUNCH("tpnet_tokens");
   return TGMX_OK;
+}
+
+extern "C" int tgmx_tpnet_tokens(const float* node_x, int64_t num_nodes, int32_t dN, const int64_t* edge_time, int64_t B,
+                                 const int32_t* nbr_nids, const int64_t* nbr_t, const float* nbr_x, int64_t S, int32_t k, int32_t dE,
+                                 const int32_t* rows, const float* tw, const float* tb, int32_t dT, const float* pf, int64_t ldpf, int32_t pf_dim, float* out, int64_t ldo, tgmx_stream_t stream) {
+  return tokens_run(node_x, num_nodes, dN, edge_time, B, nbr_nids, nbr_t, nbr_x, S, k, dE, rows, tw, tb, dT, pf, ldpf, pf_dim, out, ldo, nullptr, stream);
 }
 
 extern "C" int tgmx_tpnet_mean(const float* z, int64_t ldz, int64_t Q, int32_t k, int32_t C, float* out, int64_t ldo, tgmx_stream_t stream) {
@@ -349,7 +356,9 @@ extern "C" int tgmx_tpnet_mean(const float* z, int64_t ldz, int64_t Q, int32_t k
   return TGMX_OK;
 }
 
-extern "C" int tgmx_tpnet_forward(const tgmx_tpnet_fwd_t* a, tgmx_stream_t stream) {
+// save (training, NULL = inference): layer l reads save->z + l R ldz and keeps its token block's output in save->z1 + l R ldz, the token rows'
+// lg go to save->lg -- the same launches in the same order as the inference call, writing elsewhere; drop: the sites' common descriptor.
+static int tpnet_forward_run(const tgmx_tpnet_fwd_t* a, const tgmx_tpnet_save_t* save, const tgmx_dropout_t* drop, tgmx_stream_t stream) {
   TGMX_REQUIRE(a && a->num_layers >= 0 && a->num_layers <= TGMX_MIXER_MAX_LAYERS && a->B >= 0 && a->k > 0, "tpnet_forward: bad argument block");
   TGMX_REQUIRE(a->ldf % 4 == 0 && a->ldfh % 4 == 0 && a->ldx0 % 4 == 0 && a->ldhp % 4 == 0 && a->ldz % 4 == 0 && a->ldh % 4 == 0,
                "tpnet_forward: leading dimensions must be multiples of 4");
@@ -367,12 +376,33 @@ extern "C" int tgmx_tpnet_forward(const tgmx_tpnet_fwd_t* a, tgmx_stream_t strea
     if ((rc = tgmx_sgemm_nt_ep(a->feat, a->ldf, a->rp_w1, od, a->feat_h, a->ldfh, 2 * R, 4 * od, od, a->rp_b1, 1, nullptr, 0, stream))) return rc;
     if ((rc = tgmx_sgemm_nt_ep(a->feat_h, a->ldfh, a->rp_w2, 4 * od, a->pf, a->ldf, 2 * R, od, 4 * od, a->rp_b2, 0, nullptr, 0, stream))) return rc;
   }
-  if ((rc = tgmx_tpnet_tokens(a->node_x, a->num_nodes, a->dN, a->edge_time, B, a->nbr_nids, a->nbr_t, a->nbr_x, a->S, a->k, a->dE, a->rows,
-                              a->tw, a->tb, a->dT, od ? a->pf : nullptr, a->ldf, od, a->x0, a->ldx0, stream)))
+  if ((rc = tokens_run(a->node_x, a->num_nodes, a->dN, a->edge_time, B, a->nbr_nids, a->nbr_t, a->nbr_x, a->S, a->k, a->dE, a->rows, a->tw, a->tb,
+                       a->dT, od ? a->pf : nullptr, a->ldf, od, a->x0, a->ldx0, save ? save->lg : nullptr, stream)))
     return rc;
   if ((rc = tgmx_sgemm_nt_ep(a->x0, a->ldx0, a->proj_w0, W, a->hp, a->ldhp, R, 2 * E, W, a->proj_b0, 1, nullptr, 0, stream))) return rc;
   // (the reference's masked_fill after the projection discards its result: pad tokens stay as projected)
-  if ((rc = tgmx_sgemm_nt_ep(a->hp, a->ldhp, a->proj_w2, 2 * E, a->z, a->ldz, R, E, 2 * E, a->proj_b2, 0, nullptr, 0, stream))) return rc;
-  if ((rc = mixer_layers_run(true, a->layers, a->num_layers, Q, a->k, E, a->eps, a->z, a->z1, a->y, a->ldz, a->h, a->ldh, stream))) return rc;
+  float* z_in = save && a->num_layers > 0 ? save->z : a->z;
+  if ((rc = tgmx_sgemm_nt_ep(a->hp, a->ldhp, a->proj_w2, 2 * E, z_in, a->ldz, R, E, 2 * E, a->proj_b2, 0, nullptr, 0, stream))) return rc;
+  if (!save) {
+    if ((rc = mixer_layers_run(true, a->layers, a->num_layers, Q, a->k, E, a->eps, a->z, a->z1, a->y, a->ldz, a->h, a->ldh, stream))) return rc;
+  } else if ((rc = mixer_layers_run_train(true, a->layers, a->num_layers, Q, a->k, E, a->eps, save->z, save->z1, a->z, a->y, a->ldz, a->h, a->ldh, drop,
+                                          stream))) {
+    return rc;
+  }
   return tgmx_tpnet_mean(a->z, a->ldz, Q, a->k, E, a->out, E, stream);
+}
+
+extern "C" int tgmx_tpnet_forward(const tgmx_tpnet_fwd_t* a, tgmx_stream_t stream) { return tpnet_forward_run(a, nullptr, nullptr, stream); }
+
+extern "C" int tgmx_tpnet_forward_train(const tgmx_tpnet_fwd_t* a, const tgmx_tpnet_save_t* save, const tgmx_dropout_t* drop, tgmx_stream_t stream) {
+  TGMX_REQUIRE(a && save, "tpnet_forward_train: null argument block");
+  TGMX_REQUIRE(a->B <= 0 || (save->lg && (a->num_layers <= 0 || (save->z && save->z1))), "tpnet_forward_train: the saving buffers are missing");
+  TGMX_REQUIRE(!drop || (drop->p >= 0.f && drop->p < 1.f), "tpnet_forward_train: p must be in [0, 1)");
+  for (int l = 0; l < a->num_layers && l < TGMX_MIXER_MAX_LAYERS; ++l)
+    if (a->B > 0 && !tgmx_tpnet_train_supported(a->k, a->E, a->layers[l].tok_hidden)) {
+      set_error("tpnet_forward_train: layer %d's token block (k=%d, E=%d, hidden %d) is outside the token kernels' envelope", l, a->k, a->E,
+                a->layers[l].tok_hidden);
+      return TGMX_E_UNSUPPORTED;
+    }
+  return tpnet_forward_run(a, save, drop, stream);
 }

@@ -380,21 +380,16 @@ class _LayerRun:
     def nt(self, A, lda, B, ldb, C, ldc, M, N, K, bias=None) -> None:
         _native.check(self.lib.tgmx_sgemm_nt_ep(A, lda, B, ldb, C, ldc, M, N, K, bias, 0, None, 0, self.st), 'tgmx_sgemm_nt_ep')
 
-    def layer(self, l: int, gz, want_dx: bool):
-        """Layer ``l`` given gz = the gradient at its output (a tensor [R, ldz] or its pointer): writes the layer's wanted gradients;
-        returns the gradient at its input (a tensor [R, ldz]), or None when nobody reads it (``want_dx`` false, no token gradient wanted)."""
-        a, lib, st, R, SC, ldw = self.a, self.lib, self.st, self.R, self.SC, self.ldw
-        K, D, ldz, ldh = a.K, a.D, a.ldz, a.ldh
+    def channel(self, l: int, gz: int, down: bool) -> Optional[int]:
+        """The channel block of layer ``l`` (``mixer_channel_backward``) given the pointer of gz [R, ldz]: writes the block's wanted gradients;
+        returns the pointer of dz1 [R, ldz] = the LayerNorm's backward + the residual, or None when nobody reads it (``down`` false)."""
+        a, lib, st, R = self.a, self.lib, self.st, self.R
+        D, ldz, ldh = a.D, a.ldz, a.ldh
         ly, d = a.layers[l], a.d_layers[l]
-        hc, ht = ly.ch_hidden, ly.tok_hidden
-        gz = gz.data_ptr() if torch.is_tensor(gz) else gz
-        per = 4 * R * ldz
-        z_in, z1 = a.save_z + l * per, a.save_z1 + l * per
-        tok = _wanted(d, _LAYER_FIELDS[:6])
-        down = tok or want_dx
+        hc = ly.ch_hidden
+        z1 = a.save_z1 + l * 4 * R * ldz
         site = [_native.dropout_desc(a.drop_p, a.drop_seed, a.drop_stream + 4 * l + s) for s in range(4)]
         abuf, hbuf, y = self.buf(R * ldh), self.buf(R * ldh), self.buf(R * ldz)
-        # the channel FFN
         _native.check(lib.tgmx_mixer_channel_norm(z1, ldz, R, D, ly.ch_g, ly.ch_b, a.eps, y, ldz, st), 'tgmx_mixer_channel_norm')
         self.nt(y, ldz, ly.ch_w1, D, abuf, ldh, R, hc, D, ly.ch_b1)
         g3 = gz
@@ -425,6 +420,22 @@ class _LayerRun:
         if not down:
             return None
         _native.check(lib.tgmx_add_cols(du, ldz, gz, ldz, R, D, 1, st), 'tgmx_add_cols')
+        return du
+
+    def layer(self, l: int, gz, want_dx: bool):
+        """Layer ``l`` given gz = the gradient at its output (a tensor [R, ldz] or its pointer): writes the layer's wanted gradients;
+        returns the gradient at its input (a tensor [R, ldz]), or None when nobody reads it (``want_dx`` false, no token gradient wanted)."""
+        a, lib, st, R, SC, ldw = self.a, self.lib, self.st, self.R, self.SC, self.ldw
+        K, D, ldz = a.K, a.D, a.ldz
+        ly, d = a.layers[l], a.d_layers[l]
+        ht = ly.tok_hidden
+        gz = gz.data_ptr() if torch.is_tensor(gz) else gz
+        z_in = a.save_z + l * 4 * R * ldz
+        tok = _wanted(d, _LAYER_FIELDS[:6])
+        site = [_native.dropout_desc(a.drop_p, a.drop_seed, a.drop_stream + 4 * l + s) for s in range(4)]
+        du = self.channel(l, gz, tok or want_dx)
+        if du is None:
+            return None
         # the token block
         dx = torch.empty((R, ldz), dtype=torch.float32, device=self.dev)
         rows = self.buf(SC * ldw) if tok else None

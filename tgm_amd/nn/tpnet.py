@@ -28,8 +28,11 @@ hop 0 of the sampler's batch in place: ``src_rows`` / ``dst_rows`` [B] index its
 one negative per positive as for one-vs-many, so the example's ``repeat_interleave`` / ``repeat`` / ``cat`` copies of ``nbr_edge_x`` & co.
 are never made.  ``forward`` is ``encode_pairs`` with identity rows; the results are identical bit for bit.
 
-Inference (no gradient needed, no active dropout) is ONE native call, ``tgmx_tpnet_forward``.  Training (gradients enabled, or train mode
-with dropout > 0) is NOT native: the same arithmetic composed from torch ops on the device under autograd, with the same parameters.  A
+Inference (no gradient needed, no active dropout) is ONE native call, ``tgmx_tpnet_forward``.  Training (gradients enabled and a parameter
+that wants one) is native too: the saving forward ``tgmx_tpnet_forward_train`` (the bits of the inference call when dropout is off) and
+ONE backward call, ``tgmx_tpnet_backward``, behind a ``torch.autograd.Function`` (``_tpnet_train.py``; ``TGMX_TPNET_BWD=torch`` keeps the
+composed path).  Outside that envelope -- autocast, ``node_x`` or the edge features asking for a gradient, train-mode dropout with no
+parameter to train -- the same arithmetic is composed from torch ops on the device under autograd, with the same parameters.  A
 shape outside the native envelope (more than 4 tables, i.e. ``num_layer > 3``; more than 8 mixer layers; a token block that does not fit
 LDS; a time encoder that is not ``Time2Vec``) also takes the composed path on the device.  CPU tensors raise ``NativeLibraryError``.
 """
@@ -47,7 +50,7 @@ from torch import Tensor
 
 from .. import _native
 from ..constants import PADDED_NODE_ID
-from . import _ops
+from . import _ops, _tpnet_train
 from ._fwd_plumbing import Unsupported, cached_block, carve_scratch, check_supported, fill_mixer_layers, i32, i64, needs_torch, pair_inputs, up4
 from ._paramver import TransientCaches
 from .mlp_mixer import MLPMixer, sgemm_ep
@@ -281,6 +284,11 @@ class TPNet(TransientCaches, nn.Module):
 
     def _run(self, a: dict) -> Tuple[Tensor, Tensor]:
         if needs_torch(self, self.dropout, a['node_x'], a['nbr_x']):
+            if _tpnet_train.in_envelope(self, a):
+                try:
+                    return _tpnet_train.apply(self, a)
+                except Unsupported:  # the token block does not fit the training kernels: compose
+                    pass
             return self._torch_forward(a)
         if not self._native_ok():
             self._warn_composed('its shape is outside the native envelope (num_layer <= 3, at most 8 mixer layers, Time2Vec)')
@@ -358,19 +366,23 @@ class TPNet(TransientCaches, nn.Module):
 
         return cached_block(self, build)
 
-    def _forward_native(self, a: dict, out: Tensor) -> None:
-        blk, _ = self._weights()
-        B, k = a['B'], a['k']
-        d = self._dims()
-        bufs = self._scratch(B, k, out.device)
+    def _bind_inputs(self, blk: '_native.TPNetFwd', a: dict) -> None:
+        """The caller's tensors and the tables of this call."""
         blk.node_x, blk.num_nodes = a['node_x'].data_ptr(), a['node_x'].shape[0]
-        blk.src, blk.dst, blk.edge_time, blk.B = a['src'].data_ptr(), a['dst'].data_ptr(), a['t'].data_ptr(), B
+        blk.src, blk.dst, blk.edge_time, blk.B = a['src'].data_ptr(), a['dst'].data_ptr(), a['t'].data_ptr(), a['B']
         blk.nbr_nids, blk.nbr_t, blk.nbr_x, blk.S = a['nids'].data_ptr(), a['nbr_t'].data_ptr(), a['nbr_x'].data_ptr(), a['nids'].shape[0]
         blk.rows = _native.ptr(a['rows'])
         if self.random_projections is not None:
             blk.tables = self.random_projections._tables()  # read every call: update / reload may have replaced the tensors
         else:
             blk.tables.levels = 0
+
+    def _forward_native(self, a: dict, out: Tensor) -> None:
+        blk, _ = self._weights()
+        B, k = a['B'], a['k']
+        d = self._dims()
+        bufs = self._scratch(B, k, out.device)
+        self._bind_inputs(blk, a)
         blk.feat, blk.feat_h, blk.pf, blk.x0, blk.hp, blk.z, blk.z1, blk.y, blk.h = (b.data_ptr() for b in bufs)
         blk.ldf, blk.ldfh, blk.ldx0, blk.ldhp, blk.ldz, blk.ldh = d['ldf'], d['ldfh'], d['ldx0'], d['ldhp'], d['ldz'], d['ldh']
         blk.out = out.data_ptr()
