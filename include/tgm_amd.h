@@ -2111,6 +2111,51 @@ int tgmx_node_analytics_step(const tgmx_node_analytics_t* st, const tgmx_an_batc
  * {status: TGMX_AN_TABLE_FULL where a claim found no room; entries moved, accumulating}. */
 int tgmx_node_analytics_rehash(const void* from, int64_t from_cap, void* to, int64_t to_cap, int64_t* state, tgmx_stream_t stream);
 
+/* ---- TGBNegativeEdgeSamplerHook and its thgl / tkgl kin (the reference's tgm/hooks/negatives/tgb_sampler.py): the evaluation set of a
+ * split, constant for its life, as a table on the device; a batch of positives is answered without a loop on the host. ----
+ *
+ * The set, flattened by the host: keys [P, 4] int64 (unused fields 0), row p's negatives at pool[indptr[p] .. indptr[p] + rowlen[p]) with
+ * indptr [P + 1] a multiple of four everywhere (a row is read with 16-byte loads) and the gaps filled with -1.  slots [capacity] int32, a
+ * power of two > P, all -1 when new: open addressing, linear probing, a slot holds a row index; after tgmx_tgbneg_build it is read-only.
+ * field[j]: which batch vector key column j is compared with (0 src, 1 dst, 2 time, 3 edge type, -1: the column is 0).  bitmap
+ * [bitmap_words] uint32 over the ids [0, 32 bitmap_words), zeroed when new and left zero by every call (more than
+ * tgmx_tgbneg_limit(1) words: a multiple of tgmx_tgbneg_limit(2)); first_missing: one int32, 2^31 - 1 when new and after every call;
+ * block_counts [num_blocks >= bitmap_words / tgmx_tgbneg_limit(2), rounded up] int32 scratch.  qpad: the longest row rounded up to four. */
+#define TGMX_TGBNEG_DUPLICATE 1
+#define TGMX_TGBNEG_FULL 2
+typedef struct tgmx_tgbneg {
+  const int64_t* keys; const int64_t* indptr; const int32_t* rowlen; const int32_t* pool;
+  int64_t P, pool_ints;
+  int32_t* slots; int64_t capacity;
+  uint32_t* bitmap; int64_t bitmap_words;
+  int32_t* first_missing; int32_t* block_counts; int64_t num_blocks;
+  int32_t qpad; int32_t field[4]; int32_t reserved;
+} tgmx_tgbneg_t;
+
+/* which: 0 = the largest qpad a single wave copies (longer rows take a workgroup per positive), 1 = the largest bitmap_words the
+ * one-workgroup compaction takes (larger bitmaps take count / scan / write), 2 = bitmap words per workgroup of that split. */
+int64_t tgmx_tgbneg_limit(int32_t which);
+
+/* Inserts the P rows (one lane each; a slot is claimed by a 32-bit compare-and-swap, a taken slot's key is read from `keys`).  status: one
+ * int32, accumulating TGMX_TGBNEG_DUPLICATE (two rows with one key) and TGMX_TGBNEG_FULL (no free slot in `capacity` probes). */
+int tgmx_tgbneg_build(const tgmx_tgbneg_t* t, int32_t* status, tgmx_stream_t stream);
+
+/* One batch of B > 0 positives; src / dst / time / etype are int64 where their *_is64 flag is set, else int32 (etype may be NULL when no
+ * key column names it).  Launch 1, one wave (qpad <= limit 0) or one workgroup per positive: a wave-uniform probe, then row b of matrix
+ * [B, qpad] int32 = the key's negatives, -1 behind them, every id marked in the bitmap (an atomicOr only where a plain load shows the bit
+ * clear); a key that is not in the table leaves a row of -1 and folds b into first_missing by atomicMin.  Then the ordered compaction of
+ * the bitmap into neg (ascending ids, at most neg_cap of them written), which clears every word it read: one workgroup, or count / scan /
+ * write.  Its tail writes stats: int64 {ids written to neg, min(time), max(time), lowest missing b or -1}, then the B row lengths as int32
+ * from byte 32 on.  Integer atomics only; the result does not depend on scheduling; nothing is read back. */
+int tgmx_tgbneg_query(const tgmx_tgbneg_t* t, const void* src, int32_t src_is64, const void* dst, int32_t dst_is64, const void* time,
+                      int32_t time_is64, const void* etype, int32_t etype_is64, int64_t B, int32_t* matrix, int32_t* neg, int64_t neg_cap,
+                      int64_t* stats, tgmx_stream_t stream);
+
+/* The same compaction and tail for a matrix [B, qpad] the caller filled (-1 = no id): only bitmap, bitmap_words, first_missing, block_counts,
+ * num_blocks and qpad of `t` are read.  The row lengths in stats are left as they are. */
+int tgmx_tgbneg_unique(const tgmx_tgbneg_t* t, const int32_t* matrix, int64_t B, const void* time, int32_t time_is64, int32_t* neg,
+                       int64_t neg_cap, int64_t* stats, tgmx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -809,6 +809,26 @@ SIGNATURES['tgmx_histneg_workspace_bytes'] = (c_size_t, [c_int64, c_int64])
 SIGNATURES['tgmx_histneg_step'] = (c_int32, [ctypes.POINTER(HistNeg), _P, c_int32, _P, c_int32, _P, c_int64, _P, _P, _P, _P, c_size_t, _P])
 
 
+class TgbNeg(ctypes.Structure):
+    """tgmx_tgbneg_t (include/tgm_amd.h)."""
+
+    _fields_ = [
+        ('keys', c_void_p), ('indptr', c_void_p), ('rowlen', c_void_p), ('pool', c_void_p),
+        ('P', c_int64), ('pool_ints', c_int64),
+        ('slots', c_void_p), ('capacity', c_int64),
+        ('bitmap', c_void_p), ('bitmap_words', c_int64),
+        ('first_missing', c_void_p), ('block_counts', c_void_p), ('num_blocks', c_int64),
+        ('qpad', c_int32), ('field', c_int32 * 4), ('reserved', c_int32),
+    ]  # fmt: skip
+
+
+TGBNEG_DUPLICATE, TGBNEG_FULL = 1, 2  # TGMX_TGBNEG_*
+SIGNATURES['tgmx_tgbneg_limit'] = (c_int64, [c_int32])
+SIGNATURES['tgmx_tgbneg_build'] = (c_int32, [ctypes.POINTER(TgbNeg), _P, _P])
+SIGNATURES['tgmx_tgbneg_query'] = (c_int32, [ctypes.POINTER(TgbNeg), _P, c_int32, _P, c_int32, _P, c_int32, _P, c_int32, c_int64, _P, _P, c_int64, _P, _P])
+SIGNATURES['tgmx_tgbneg_unique'] = (c_int32, [ctypes.POINTER(TgbNeg), _P, c_int64, _P, c_int32, _P, c_int64, _P, _P])
+
+
 DECODER_MAX_LAYERS = 8  # TGMX_DECODER_MAX_LAYERS
 DECODER_MAX_TAIL = 16  # widest last layer the row-dot kernels take
 DECODER_MAX_H = 512  # widest half row of tgmx_decoder_score

@@ -2,7 +2,7 @@
 
 The names and meanings are the reference's (tgm/exceptions.py:1-47), so callers' ``except`` clauses keep working
 unchanged; ``NativeLibraryError`` is ours.  The classes are built from one table (name, what it means) instead of
-ten two-line class statements.
+eleven two-line class statements.
 """
 from typing import Dict, Type
 
@@ -21,6 +21,7 @@ _MEANINGS = (
     ('EventOrderedConversionError', "A time-unit operation was requested on an event-ordered ('r') graph."),
     ('InvalidDiscretizationError', "Iteration / discretization to a finer unit than the graph's own."),
     ('EmptyBatchError', "An empty batch was produced under on_empty='raise'."),
+    ('UndefinedRecipe', 'RecipeRegistry.build was asked for a recipe that is not defined / registered.'),
     ('NativeLibraryError', 'libtgm_amd.so (the HIP kernels) is missing or failed; there is no CPU fallback.'),
 )
 

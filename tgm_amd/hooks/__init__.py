@@ -1,3 +1,5 @@
+import sys as _sys
+
 from .base import BaseDGHook, DGHook, SeedableHook, StatefulHook, StatelessHook
 from .dedup import DeduplicationHook
 from .edge_list import SampledEdgeListHook
@@ -11,6 +13,14 @@ from . import neighbors  # noqa: E402,F401  (the reference's import path: tgm.ho
 from .analytics import BatchAnalyticsHook, NodeAnalyticsHook
 from .device import DeviceTransferHook, PinMemoryHook
 from .node_tracks import EdgeEventsSeenNodesTrackHook
+from . import negatives, tgb_sampler  # noqa: E402
+from .tgb_sampler import TGBNegativeEdgeSamplerHook, TGBTHGNegativeEdgeSamplerHook, TGBTKGNegativeEdgeSamplerHook
+from ..core.neg_batch_list import NegBatchList
+
+# the reference's import path, tgm.hooks.negatives.tgb_sampler (our negatives is one module, not a package)
+negatives.tgb_sampler = tgb_sampler
+_sys.modules[f'{__name__}.negatives.tgb_sampler'] = tgb_sampler
+from .recipe import RecipeRegistry  # noqa: E402  (after the hooks it registers)
 
 __all__ = [
     'BaseDGHook',
@@ -21,15 +31,20 @@ __all__ = [
     'EdgeEventsSeenNodesTrackHook',
     'HistoricalNegativeEdgeSamplerHook',
     'HookManager',
+    'NegBatchList',
     'NeighborSamplerHook',
     'NodeAnalyticsHook',
     'PinMemoryHook',
     'RandomNegativeEdgeSamplerHook',
     'RecencyNeighborHook',
+    'RecipeRegistry',
     'SampledEdgeListHook',
     'SeedableHook',
     'StatefulHook',
     'StatelessHook',
+    'TGBNegativeEdgeSamplerHook',
+    'TGBTHGNegativeEdgeSamplerHook',
+    'TGBTKGNegativeEdgeSamplerHook',
     'TimeGapNeighborHook',
     'hook',
     'list_hooks',

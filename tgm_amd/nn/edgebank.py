@@ -27,6 +27,7 @@ import numpy as np
 import torch
 
 from .. import _native
+from ..core.neg_batch_list import uniform_matrix
 from ._fwd_plumbing import ids as _ids, pow2ceil as _pow2ceil
 
 _EMPTY = -1  # the empty key, all ones, as the int64 the table tensor shows
@@ -196,6 +197,9 @@ class EdgeBankPredictor:
         B = src.numel()
         if dst.numel() != B:
             raise ValueError(f'mismatch shape: src: {B}, dst: {dst.numel()}')
+        as_rows = uniform_matrix(negatives)  # a NegBatchList of equal rows: its matrix, no B-way cat
+        if as_rows is not None:
+            negatives = as_rows
         ragged = not isinstance(negatives, torch.Tensor)
         if ragged:
             negatives = list(negatives)
@@ -230,7 +234,7 @@ class EdgeBankPredictor:
                 'tgmx_edgebank_query',
             )  # fmt: skip
         if not ragged:
-            return pred.view(B, M + 1)
+            return pred.view(B, M + 1) if as_rows is None else list(pred.view(B, M + 1).unbind(0))
         return list(torch.split(pred, [m + 1 for m in sizes]))
 
     # ---- reads from the device ------------------------------------------------------------------------------------------------------------

@@ -31,6 +31,7 @@ import torch.nn as nn
 from torch import Tensor
 
 from .. import _native
+from ..core.neg_batch_list import uniform_matrix
 from ._decoder_head import DecoderHead, build_mlp, linears
 from ._fwd_plumbing import i32, needs_torch
 from .aggregation import Aggregator, ConcatMerge, require_aggregator
@@ -123,6 +124,9 @@ class LinkPredictor(DecoderHead, nn.Module):
         B = src_idx.numel()
         if dst_idx.numel() != B:
             raise ValueError(f'mismatch shape: src_idx: {B}, dst_idx: {dst_idx.numel()}')
+        as_rows = uniform_matrix(negatives)  # a NegBatchList of equal rows: its matrix, no B-way cat
+        if as_rows is not None:
+            negatives = as_rows
         ragged = not isinstance(negatives, Tensor)
         if ragged:
             negatives = [t.reshape(-1) for t in negatives]
@@ -161,7 +165,7 @@ class LinkPredictor(DecoderHead, nn.Module):
                 off = torch.from_numpy(off_host).pin_memory().to(z.device, non_blocking=True)
             flat = self._pairs(z.contiguous(), R, src_idx, dst_idx, neg, off, M, most, B).view(-1)
         if not ragged:
-            return flat.view(B, (M + 1) * out_dim)
+            return flat.view(B, (M + 1) * out_dim) if as_rows is None else list(flat.view(B, (M + 1) * out_dim).unbind(0))
         return list(torch.split(flat, [(m + 1) * out_dim for m in sizes]))
 
     def _pairs(self, z: Tensor, R: int, src_idx: Tensor, dst_idx: Tensor, neg: Optional[Tensor], off: Optional[Tensor], M: int, most: int,
