@@ -58,7 +58,7 @@ int tgmx_version(void);
  * 6 tgmx_pipeline_t, 7 tgmx_pipeline_out_t, 8 tgmx_dropout_t, 9 tgmx_tgn_memory_fwd_t, 10 tgmx_tconv_fwd_t, 11 tgmx_pipeline_post_t,
  * 12 tgmx_tgn_step_t, ..., 22 tgmx_ctan_fwd_t, 24 tgmx_gclstm_fwd_t, 26 tgmx_roland_fwd_t, 27 tgmx_decoder_fwd_t, 35 tgmx_ctan_bwd_t, 36 tgmx_graphmixer_bwd_t, 37 tgmx_dygformer_bwd_t, 38 tgmx_tpnet_bwd_t (23 and 25 are reserved and answer 0: tests/test_ctan_cpu.py and
  * tests/test_gclstm_cpu.py pin them), 28 tgmx_an_batch_t, 29 tgmx_node_analytics_t, 30 tgmx_decoder_train_t, 32 tgmx_gclstm_bwd_t (31 is
- * reserved the same way: tests/test_decoder_train_cpu.py) */
+ * reserved the same way: tests/test_decoder_train_cpu.py), 39 tgmx_gcn_conv_bwd_t, 40 tgmx_tgcn_csr_fwd_t, 41 tgmx_tgcn_csr_bwd_t */
 size_t tgmx_abi_sizeof(int32_t which);
 const char* tgmx_last_error(void);
 
@@ -1884,6 +1884,89 @@ typedef struct tgmx_roland_fwd {
   float* out[2];                                                       /* [N, C] each */
 } tgmx_roland_fwd_t;
 int tgmx_roland_forward(const tgmx_roland_fwd_t* args, tgmx_stream_t stream);
+
+/* ---- GCNConv / TGCN over the sparse adjacency, training included (csrc/gcn_bwd.hip, csrc/tgcn.hip; composed by
+ * tgm_amd/nn/_gcn_sparse_train.py, TGMX_TGCN_BWD = py | torch picks the per-launch or the composed torch path) ---- */
+
+/* Bytes of workspace tgmx_csr_transpose needs for nnz entry slots over N nodes (0: sizes out of range). */
+size_t tgmx_csr_transpose_workspace_bytes(int64_t nnz, int64_t N);
+
+/* The transpose of a CSR in the layout of tgmx_gcn_norm_csr / tgmx_cheb_laplacian: (indptr [N + 1], cols [nnz], vals [nnz]) by row becomes
+ * (indptr_t, cols_t [nnz], vals_t [nnz]) by column index; the diagonal is its own transpose (diag_t, when given and not diag itself, gets
+ * a copy).  nnz: the entry SLOTS (the E the CSR was built from); only the first indptr[N] hold entries (the builders leave dropped edges
+ * behind the rows) and that count is read on the device.  Every entry's row is expanded from indptr by one wave per row, then ONE stable
+ * radix sort of the keys (col << cb | row) carrying the entry position, row pointers by binary search, vals_t[u] = vals[pos[u]]: values
+ * are copied, not recomputed, so the multiset of (row, col, value) is the input's with row and col swapped, bit for bit; within a
+ * transposed row the columns ascend and equal (row, col) entries keep the input's entry order; indptr_t[N] = indptr[N].  No float atomics;
+ * nnz = 0 issues no sort.  Propagating over the result is tgmx_gcn_propagate with no bias and TGMX_GCN_EPI_NONE. */
+int tgmx_csr_transpose(const int32_t* indptr, const int32_t* cols, const float* vals, const float* diag, int64_t N, int64_t nnz,
+                       int32_t* indptr_t, int32_t* cols_t, float* vals_t, float* diag_t, void* workspace, size_t workspace_bytes,
+                       tgmx_stream_t stream);
+
+/* GCNConv's backward as ONE call (tgmx_abi_sizeof(39)); its forward is out = A_hat (x W^T) + b by tgmx_sgemm_nt and tgmx_gcn_propagate.
+ * Order: d_b = colsum(dout) -> the transposed CSR (tgmx_csr_transpose into the workspace, unless indptr_t / cols_t / vals_t hand it in
+ * built: then indptr / cols / vals are not read) -> dY = A_hat^T dout (one tgmx_gcn_propagate) -> d_W = dY^T x (tgmx_sgemm_tn, [C, in]:
+ * lin.weight's layout) -> d_x = dY W (tgmx_sgemm_nt on WT [in, ldwt >= C]).  Every gradient pointer may be NULL: its launches are not
+ * issued.  The adjacency gets no gradient (edge weights are data).  No float atomics: two runs give the same bits. */
+typedef struct tgmx_gcn_conv_bwd {
+  int64_t N; int32_t in_ch, C;
+  const float* x; int64_t ldx;                      /* [N, ldx >= in_ch] (d_W) */
+  const float* WT; int64_t ldwt;                    /* lin.weight transposed (d_x) */
+  const float* dout; int64_t lddo;                  /* [N, lddo >= C] */
+  const int32_t* indptr; const int32_t* cols; const float* vals; const float* diag; int64_t nnz; /* the forward's CSR, nnz entry slots */
+  const int32_t* indptr_t; const int32_t* cols_t; const float* vals_t;                           /* its transpose already built, or NULL */
+  float* d_W; float* d_b; float* d_x;               /* [C, in], [C], [N, in], contiguous */
+  void* workspace; size_t workspace_bytes;          /* tgmx_gcn_conv_backward_csr_workspace_bytes(args) */
+} tgmx_gcn_conv_bwd_t;
+size_t tgmx_gcn_conv_backward_csr_workspace_bytes(const tgmx_gcn_conv_bwd_t* args);
+int tgmx_gcn_conv_backward_csr(const tgmx_gcn_conv_bwd_t* args, tgmx_stream_t stream);
+
+/* The TGCN cell's forward over the sparse adjacency as ONE call (tgmx_abi_sizeof(40)): tgmx_gcn_norm_csr (not with csr_built: indptr / cols
+ * / vals / diag then hold the CSR already and the edge list is not read) -> xw = x W3^T as [N, 3C] (no transposed copy) -> ONE
+ * tgmx_gcn_propagate over the 3C columns with b3 as its bias -> G; per gate u, r, c tgmx_tgcn_concat and its Linear, tgmx_tgcn_output: as
+ * tgmx_tgcn_forward.  save != 0 is the saving form for training: gate g writes cat[g] (else all three use cat[0]); pre[0..2] are kept
+ * either way; both forms give the same bits.  ids int64 where idx64 is set, else int32, read as they are; E: the edge count = the CSR's
+ * entry slots.  prop_ws: tgmx_cheb_propagate_scratch_floats(E, 3 C) floats, or NULL. */
+typedef struct tgmx_tgcn_csr_fwd {
+  const float* x; int64_t ldx; int64_t N; int32_t in_ch, C;
+  const void* src; const void* dst; const float* edge_w; int64_t E; int32_t idx64; float fill; int32_t add_self_loops, csr_built, save;
+  const float* W3; int64_t ldw3; const float* b3;   /* stacked GCN weights [3 C, ldw3 >= in_ch] and biases [3 C] */
+  const float* lin_w[3]; const float* lin_b[3];     /* linear_{u,r,c}: [C, 2 C], [C] */
+  const float* H;                                   /* [N, C] */
+  int32_t* indptr; int32_t* cols; float* vals; float* diag; /* [N + 1], [E], [E], [N] */
+  void* norm_ws; size_t norm_ws_bytes; int32_t* skipped;    /* tgmx_gcn_workspace_bytes(E, N); the counter of skipped edges or NULL */
+  float* prop_ws; size_t prop_ws_floats;
+  float* xw; float* G;                              /* [N, 3 C] each */
+  float* cat[3]; float* pre[3];                     /* [N, 2 C], [N, C] */
+  float* out;                                       /* [N, C] */
+} tgmx_tgcn_csr_fwd_t;
+int tgmx_tgcn_forward_csr(const tgmx_tgcn_csr_fwd_t* args, tgmx_stream_t stream);
+
+/* dG [N, 3C] = [dcat_u[:, :C] | dcat_r[:, :C] | dcat_c[:, :C]]: the left halves of the three gates' input gradients ([N, 2C] each, contiguous)
+ * side by side -- the gradient at G = A_hat (x W3^T) + b3, the operand of the backward's one propagate. */
+int tgmx_tgcn_gather_left(const float* dcat_u, const float* dcat_r, const float* dcat_c, int32_t C, int64_t N, float* dG, tgmx_stream_t stream);
+
+/* The cell's backward over the sparse adjacency as ONE call (tgmx_abi_sizeof(41)): the arithmetic of the dense training path with
+ * A_hat^T dG as one propagate over the transposed CSR.  x / H / cat / pre: what the saving forward read and kept; lin_wT[g] [2C, C] and
+ * W3T [in, ldw3t >= 3C]: the weights transposed; dout [N, C] contiguous.  Order: tgmx_tgcn_gate_backward -> d cat_g = d pre_g W_g
+ * (tgmx_sgemm_nt) with the two tgmx_tgcn_reset_backward calls in between -> d_lw[g] = d pre_g^T cat_g ([C, 2C]), d_lb[g] (tgmx_sgemm_tn,
+ * tgmx_colsum) -> dG [N, 3C] = the left halves of the three d cat side by side (one gather launch) -> d_b3 = colsum(dG) -> the transposed
+ * CSR (as in tgmx_gcn_conv_backward_csr: built once into the workspace unless handed in) -> dY = A_hat^T dG (ONE tgmx_gcn_propagate) ->
+ * d_W3 = dY^T x ([3C, in]: the rows of gate g are conv_g.lin.weight's gradient) -> d_x = dY W3.  d_H [N, C] gets the state's gradient.
+ * Every gradient pointer may be NULL.  The adjacency gets no gradient.  No float atomics: two runs give the same bits. */
+typedef struct tgmx_tgcn_csr_bwd {
+  int64_t N; int32_t in_ch, C;
+  const float* x; int64_t ldx; const float* H;
+  const float* W3T; int64_t ldw3t; const float* lin_wT[3];
+  const float* cat[3]; const float* pre[3];
+  const float* dout;
+  const int32_t* indptr; const int32_t* cols; const float* vals; const float* diag; int64_t nnz;
+  const int32_t* indptr_t; const int32_t* cols_t; const float* vals_t;
+  float* d_W3; float* d_b3; float* d_lw[3]; float* d_lb[3]; float* d_x; float* d_H;
+  void* workspace; size_t workspace_bytes;          /* tgmx_tgcn_backward_csr_workspace_bytes(args) */
+} tgmx_tgcn_csr_bwd_t;
+size_t tgmx_tgcn_backward_csr_workspace_bytes(const tgmx_tgcn_csr_bwd_t* args);
+int tgmx_tgcn_backward_csr(const tgmx_tgcn_csr_bwd_t* args, tgmx_stream_t stream);
 
 /* ---- HistoricalNegativeEdgeSamplerHook (the reference's tgm/hooks/negatives/sampler.py:68-238): per-source history on the device ---- */
 

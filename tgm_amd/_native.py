@@ -793,6 +793,64 @@ SIGNATURES['tgmx_gcn_norm_csr'] = (c_int32, [_P, _P, c_int32, _P, c_int64, c_int
 SIGNATURES['tgmx_gcn_propagate'] = (c_int32, [_P, _P, _P, _P, c_int64, c_int32, _P, c_int64, _P, c_int32, _P, c_int64, ctypes.c_float, _P, _P, c_int64, _P, c_int64, c_int64, _P, c_size_t, _P])
 SIGNATURES['tgmx_roland_forward'] = (c_int32, [ctypes.POINTER(RolandFwd), _P])
 
+
+_CSR = [('indptr', c_void_p), ('cols', c_void_p), ('vals', c_void_p), ('diag', c_void_p)]
+_CSR_T = [('indptr_t', c_void_p), ('cols_t', c_void_p), ('vals_t', c_void_p)]
+
+
+class GcnConvBwd(ctypes.Structure):
+    """tgmx_gcn_conv_bwd_t (include/tgm_amd.h)."""
+
+    _fields_ = [
+        ('N', c_int64), ('in_ch', c_int32), ('C', c_int32),
+        ('x', c_void_p), ('ldx', c_int64), ('WT', c_void_p), ('ldwt', c_int64), ('dout', c_void_p), ('lddo', c_int64),
+        *_CSR, ('nnz', c_int64), *_CSR_T,
+        ('d_W', c_void_p), ('d_b', c_void_p), ('d_x', c_void_p),
+        ('workspace', c_void_p), ('workspace_bytes', c_size_t),
+    ]  # fmt: skip
+
+
+class TgcnCsrFwd(ctypes.Structure):
+    """tgmx_tgcn_csr_fwd_t (include/tgm_amd.h)."""
+
+    _fields_ = [
+        ('x', c_void_p), ('ldx', c_int64), ('N', c_int64), ('in_ch', c_int32), ('C', c_int32),
+        ('src', c_void_p), ('dst', c_void_p), ('edge_w', c_void_p), ('E', c_int64), ('idx64', c_int32), ('fill', ctypes.c_float),
+        ('add_self_loops', c_int32), ('csr_built', c_int32), ('save', c_int32),
+        ('W3', c_void_p), ('ldw3', c_int64), ('b3', c_void_p),
+        ('lin_w', c_void_p * 3), ('lin_b', c_void_p * 3),
+        ('H', c_void_p),
+        *_CSR,
+        ('norm_ws', c_void_p), ('norm_ws_bytes', c_size_t), ('skipped', c_void_p), ('prop_ws', c_void_p), ('prop_ws_floats', c_size_t),
+        ('xw', c_void_p), ('G', c_void_p), ('cat', c_void_p * 3), ('pre', c_void_p * 3),
+        ('out', c_void_p),
+    ]  # fmt: skip
+
+
+class TgcnCsrBwd(ctypes.Structure):
+    """tgmx_tgcn_csr_bwd_t (include/tgm_amd.h)."""
+
+    _fields_ = [
+        ('N', c_int64), ('in_ch', c_int32), ('C', c_int32),
+        ('x', c_void_p), ('ldx', c_int64), ('H', c_void_p),
+        ('W3T', c_void_p), ('ldw3t', c_int64), ('lin_wT', c_void_p * 3),
+        ('cat', c_void_p * 3), ('pre', c_void_p * 3),
+        ('dout', c_void_p),
+        *_CSR, ('nnz', c_int64), *_CSR_T,
+        ('d_W3', c_void_p), ('d_b3', c_void_p), ('d_lw', c_void_p * 3), ('d_lb', c_void_p * 3), ('d_x', c_void_p), ('d_H', c_void_p),
+        ('workspace', c_void_p), ('workspace_bytes', c_size_t),
+    ]  # fmt: skip
+
+
+SIGNATURES['tgmx_csr_transpose_workspace_bytes'] = (c_size_t, [c_int64, c_int64])
+SIGNATURES['tgmx_csr_transpose'] = (c_int32, [_P, _P, _P, _P, c_int64, c_int64, _P, _P, _P, _P, _P, c_size_t, _P])
+SIGNATURES['tgmx_gcn_conv_backward_csr_workspace_bytes'] = (c_size_t, [ctypes.POINTER(GcnConvBwd)])
+SIGNATURES['tgmx_gcn_conv_backward_csr'] = (c_int32, [ctypes.POINTER(GcnConvBwd), _P])
+SIGNATURES['tgmx_tgcn_forward_csr'] = (c_int32, [ctypes.POINTER(TgcnCsrFwd), _P])
+SIGNATURES['tgmx_tgcn_gather_left'] = (c_int32, [_P, _P, _P, c_int32, c_int64, _P, _P])
+SIGNATURES['tgmx_tgcn_backward_csr_workspace_bytes'] = (c_size_t, [ctypes.POINTER(TgcnCsrBwd)])
+SIGNATURES['tgmx_tgcn_backward_csr'] = (c_int32, [ctypes.POINTER(TgcnCsrBwd), _P])
+
 class HistNeg(ctypes.Structure):
     """tgmx_histneg_t (include/tgm_amd.h)."""
 

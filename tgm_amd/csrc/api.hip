@@ -54,6 +54,9 @@ extern "C" size_t tgmx_abi_sizeof(int32_t which) {
     case 36: return sizeof(tgmx_graphmixer_bwd_t);
     case 37: return sizeof(tgmx_dygformer_bwd_t);
     case 38: return sizeof(tgmx_tpnet_bwd_t);
+    case 39: return sizeof(tgmx_gcn_conv_bwd_t);
+    case 40: return sizeof(tgmx_tgcn_csr_fwd_t);
+    case 41: return sizeof(tgmx_tgcn_csr_bwd_t);
     default: return 0;
   }
 }

@@ -221,3 +221,34 @@ extern "C" int tgmx_tgcn_forward(const tgmx_tgcn_fwd_t* a, tgmx_stream_t stream)
   }
   return tgmx_tgcn_output(a->pre[0], a->pre[2], a->H, N * C, a->out, stream);
 }
+
+// the cell's forward over a sparse adjacency as one call: the CSR (built here, or handed in built), XW = X W3^T as [N, 3C] (no transposed
+// copy: the propagate gathers rows), ONE propagate over the 3C columns with b3 as its bias, then the gates as above.  save: every gate keeps
+// its own cat buffer (training); the arithmetic does not depend on it.
+extern "C" int tgmx_tgcn_forward_csr(const tgmx_tgcn_csr_fwd_t* a, tgmx_stream_t stream) {
+  TGMX_REQUIRE(a, "tgcn_forward_csr: null argument block");
+  const int64_t N = a->N;
+  const int C = a->C;
+  TGMX_REQUIRE(N > 0 && N < (1ll << 31) && C > 0 && C < (1 << 27) && a->in_ch > 0 && a->E >= 0 && a->E < (1ll << 31), "tgcn_forward_csr: bad sizes");
+  TGMX_REQUIRE(a->ldx >= a->in_ch && a->ldw3 >= a->in_ch, "tgcn_forward_csr: leading dimension below in_ch");
+  TGMX_REQUIRE(a->x && a->W3 && a->b3 && a->H && a->indptr && a->diag && a->xw && a->G && a->out && (a->E == 0 || (a->cols && a->vals)),
+               "tgcn_forward_csr: null pointer");
+  TGMX_REQUIRE(a->csr_built || (a->norm_ws && (a->E == 0 || (a->src && a->dst))), "tgcn_forward_csr: the edge list or its workspace is missing");
+  for (int g = 0; g < 3; ++g)
+    TGMX_REQUIRE(a->lin_w[g] && a->lin_b[g] && a->pre[g] && a->cat[a->save ? g : 0], "tgcn_forward_csr: null pointer (gate %d)", g);
+  int rc;
+  if (!a->csr_built &&
+      (rc = tgmx_gcn_norm_csr(a->src, a->dst, a->idx64, a->edge_w, a->E, N, a->fill, a->add_self_loops, a->indptr, a->cols, a->vals, a->diag, a->norm_ws,
+                              a->norm_ws_bytes, a->skipped, stream)))
+    return rc;
+  if ((rc = tgmx_sgemm_nt(a->x, a->ldx, a->W3, a->ldw3, a->xw, 3 * C, N, 3 * C, a->in_ch, nullptr, 0, 1, 0, 0, 0, stream))) return rc;
+  if ((rc = tgmx_gcn_propagate(a->indptr, a->cols, a->vals, a->diag, N, 3 * C, a->xw, 3 * C, a->b3, TGMX_GCN_EPI_NONE, nullptr, 0, 0.f, nullptr, nullptr, 0,
+                               a->G, 3 * C, a->E, a->prop_ws, a->prop_ws_floats, stream)))
+    return rc;
+  for (int g = 0; g < 3; ++g) {  // u, r, c
+    float* cat = a->cat[a->save ? g : 0];
+    if ((rc = tgmx_tgcn_concat(a->G + g * C, 3 * C, a->H, g == 2 ? a->pre[1] : nullptr, C, N, cat, stream))) return rc;
+    if ((rc = tgmx_sgemm_nt(cat, 2 * C, a->lin_w[g], 2 * C, a->pre[g], C, N, C, 2 * C, a->lin_b[g], 0, 1, 0, 0, 0, stream))) return rc;
+  }
+  return tgmx_tgcn_output(a->pre[0], a->pre[2], a->H, N * C, a->out, stream);
+}

@@ -120,6 +120,86 @@ def gcn_norm_csr(edge_index: Tensor, edge_weight: Optional[Tensor], N: int, fill
     return indptr, cols, vals.view(torch.float32), diag
 
 
+def csr_transpose(csr: Csr, N: int) -> Csr:
+    """``tgmx_csr_transpose``: the same matrix as rows by column index; values are copied (bit for bit), ``diag`` is the same tensor."""
+    lib = _native.load()
+    indptr, cols, vals, diag = csr
+    E, dev = cols.numel(), indptr.device
+    nbytes = lib.tgmx_csr_transpose_workspace_bytes(E, N)
+    if nbytes == 0:
+        raise ValueError(f'csr_transpose: {E} entries over {N} nodes are out of range')
+    indptr_t = torch.empty(N + 1, dtype=torch.int32, device=dev)
+    cols_t = torch.empty(max(E, 1), dtype=torch.int32, device=dev)[:E]
+    vals_t = torch.empty(max(E, 1), dtype=torch.float32, device=dev)[:E]
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    _native.check(
+        lib.tgmx_csr_transpose(indptr.data_ptr(), cols.data_ptr(), vals.data_ptr(), diag.data_ptr(), N, E, indptr_t.data_ptr(), cols_t.data_ptr(),
+                               vals_t.data_ptr(), None, ws.data_ptr(), nbytes, _native.stream_ptr()),
+        'tgmx_csr_transpose',
+    )  # fmt: skip
+    return indptr_t, cols_t, vals_t, diag
+
+
+class GCNGraph(_Skipped):
+    """One snapshot's normalised adjacency D^-1/2 (A + I) D^-1/2 for ``GCNConv`` / ``TGCN`` on the sparse route: the CSR by destination,
+    its transpose (built lazily, once, on the first backward that needs it, then kept), the scratch the propagate splits hub rows with, and
+    the counter of skipped edges (``check()``).  Pass it in place of ``edge_index`` (``edge_weight`` then ``None``) to every layer of a
+    stack: the snapshot is then sorted once for all layers, and once more for all their backward passes.  Build it with :func:`gcn_graph`.
+    The adjacency carries no gradient: edge weights are data."""
+
+    def __init__(self, csr: Optional[Csr], num_nodes: int, E: int, improved: bool, add_self_loops: bool, device, skipped: Optional[Tensor] = None,
+                 shared: bool = True) -> None:  # fmt: skip
+        self.csr, self.num_nodes, self.E, self.improved, self.add_self_loops, self.device = csr, num_nodes, E, improved, add_self_loops, device
+        self.shared = shared  # False: a module built it for one call; the backward then transposes into its own workspace and keeps nothing
+        self._t: Optional[Csr] = None
+        self._scratch: dict = {}
+        if skipped is not None:
+            self.__dict__['_tgmx_skipped'] = skipped
+
+    @property
+    def skipped(self) -> Tensor:
+        return self._skipped(self.device)
+
+    def transposed(self) -> Csr:
+        if self._t is None:
+            self._t = csr_transpose(self.csr, self.num_nodes)
+        return self._t
+
+    def scratch(self, C: int) -> Optional[Tensor]:
+        """The hub scratch for a propagate over ``C`` channels (``None``: no row of this graph can be a hub)."""
+        if C not in self._scratch:
+            n = _native.load().tgmx_cheb_propagate_scratch_floats(self.E, C)
+            self._scratch[C] = torch.empty(n, dtype=torch.float32, device=self.device) if n else None
+        return self._scratch[C]
+
+    def matches(self, module) -> None:
+        if bool(module.improved) != self.improved or bool(module.add_self_loops) != self.add_self_loops:
+            raise ValueError(f'{type(module).__name__}(improved={module.improved}, add_self_loops={module.add_self_loops}) was handed a GCNGraph built '
+                             f'with improved={self.improved}, add_self_loops={self.add_self_loops}')  # fmt: skip
+
+
+def gcn_csr_buffers(E: int, N: int, device) -> List[Tensor]:
+    """indptr, cols, vals, diag of one snapshot as tensors of their own (a call that saves its CSR for the backward owns them)."""
+    flat = torch.empty(2 * N + 1 + 2 * max(E, 1), dtype=torch.int32, device=device)
+    indptr, cols, vals, diag = flat.split([N + 1, max(E, 1), max(E, 1), N])
+    return [indptr, cols[:E], vals[:E].view(torch.float32), diag.view(torch.float32)]
+
+
+def gcn_graph(edge_index: Tensor, edge_weight: Optional[Tensor] = None, num_nodes: Optional[int] = None, improved: bool = False,
+              add_self_loops: bool = True) -> GCNGraph:  # fmt: skip
+    """The :class:`GCNGraph` of a snapshot (``tgmx_gcn_norm_csr``: one sort).  ``num_nodes`` is required: the rows of ``x``."""
+    if num_nodes is None or isinstance(num_nodes, bool) or not isinstance(num_nodes, int) or num_nodes <= 0:
+        raise ValueError(f'gcn_graph: num_nodes must be a positive int, got {num_nodes!r}')
+    src, _ = _endpoints(edge_index)
+    E, dev = src.numel(), src.device
+    g = GCNGraph(None, num_nodes, E, bool(improved), bool(add_self_loops), dev)
+    nbytes = _native.load().tgmx_gcn_workspace_bytes(E, num_nodes)
+    sizes = csr_scratch_sizes(E, num_nodes, nbytes, 'gcn_graph')
+    ws = torch.empty(sizes[4], dtype=torch.int32, device=dev)
+    g.csr = gcn_norm_csr(edge_index, edge_weight, num_nodes, 2.0 if improved else 1.0, add_self_loops, g.skipped, gcn_csr_buffers(E, num_nodes, dev) + [ws])
+    return g
+
+
 def gcn_propagate(csr: Csr, t: Tensor, out: Tensor, bias: Optional[Tensor] = None, epilogue: str = 'none', prev: Optional[Tensor] = None,
                   tau: Union[float, Tensor] = 0.0, prev_copy: Optional[Tensor] = None, scratch: Optional[Tensor] = None,
                   E: Optional[int] = None) -> Tensor:  # fmt: skip
