@@ -1483,6 +1483,30 @@ typedef struct tgmx_ncn_fwd {
 } tgmx_ncn_fwd_t;
 int tgmx_ncn_forward(const tgmx_ncn_fwd_t* args, tgmx_stream_t stream);
 
+/* ---- NCNPredictor at k = 8 (csrc/ncn8.hip): the two-hop common-neighbour blocks.  tgmx_ncn_cn_emb / tgmx_ncn_forward and the backward
+ * entries below keep refusing k = 8; these three take it.  With A2 = A A, K3 = A2 A, u = -A[i, j], R = A[t], S = A2[t] for the pair (i, j):
+ *   c01[i] = A[j, i]   c10[j] = A[i, j]   c11 = R_i o R_j   sp = c11 A
+ *   c12 = R_i o S_j + R_i o R_i u      c21 = S_i o R_j + R_j o R_j u
+ *   c22 = S_i o S_j + ([R_i > 0] K3[i, i] + [R_j > 0] K3[j, j] - c11) u + sp
+ *   c12, c21, c22: columns i and j set to 0, then c22 = max(c22, 0)
+ *   xs[r] = x[i] * x[j] | (c01 o W) x | (c10 o W) x | (c11 o W) x | (c12 o W) x | (c21 o W) x | (c22 o W) x | sp x       (8 C columns)
+ * Every coefficient is an exact integer (int32 count rows, int64 products), W (tgmx_ncn_cn_emb's float32 argument, the exponential in
+ * float64) multiplies only non-zero counts, the sums run over ascending n in float64 and are rounded once: no float atomics, two runs give
+ * the same bits.  last, the zero row of a pair
+ * with a target outside [0, N) and the columns up to ldxs: as tgmx_ncn_cn_emb.  One workgroup per pair; the count rows live in LDS while
+ * N <= tgmx_ncn8_lds_max_nodes(), else in the workspace (5 N int32 per resident workgroup, zeroed once per call).
+ * workspace: tgmx_ncn8_workspace_bytes(N, B) bytes, host arithmetic only (0: a size out of range).  force_workspace != 0 (tests): the
+ * workspace form whatever N; it needs what tgmx_ncn8_workspace_bytes gives for any N' > max(N, tgmx_ncn8_lds_max_nodes()). */
+int32_t tgmx_ncn8_lds_max_nodes(void);
+size_t tgmx_ncn8_workspace_bytes(int64_t N, int64_t B);
+int tgmx_ncn8_cn_emb(const float* x, int64_t N, int32_t C, const int32_t* indptr, const int32_t* cols, const void* tar, int32_t tar_is64,
+                     int64_t tar_stride, int64_t B, const int64_t* last_update, const int64_t* edge_time, int32_t* last, float* xs,
+                     int64_t ldxs, void* workspace, size_t workspace_bytes, int32_t force_workspace, tgmx_stream_t stream);
+/* The k = 8 inference forward as ONE call: tgmx_ncn_forward's argument block (k = 8, ldxs >= 8 C) and steps, with tgmx_ncn8_cn_emb; the
+ * two Linear layers (8 C integer-weighted inputs, hidden units in the hundreds) run as one float64 kernel, a workgroup per pair, the hidden
+ * row unrounded in LDS, out rounded once (h receives the float32 copy); H > 8192 is refused (TGMX_E_INVALID). */
+int tgmx_ncn8_forward(const tgmx_ncn_fwd_t* args, void* workspace, size_t workspace_bytes, tgmx_stream_t stream);
+
 /* ---- NCNPredictor training (csrc/ncn_bwd.hip): the backward of the common-neighbour stage, and the whole backward as ONE call.  No float
  * atomics anywhere: every sum has one fixed order, two runs give the same bits.  Nothing is read back to the host. ---- */
 

@@ -614,6 +614,11 @@ SIGNATURES['tgmx_ncn_adj_workspace_bytes'] = (c_size_t, [c_int64])
 SIGNATURES['tgmx_ncn_adj_build'] = (c_int32, [_P, c_int32, c_int64, c_int64, c_int64, _P, _P, _P, c_size_t, _P])
 SIGNATURES['tgmx_ncn_cn_emb'] = (c_int32, [_P, c_int64, c_int32, c_int32, _P, _P, _P, c_int32, c_int64, c_int64, _P, _P, _P, _P, c_int64, _P])
 SIGNATURES['tgmx_ncn_forward'] = (c_int32, [ctypes.POINTER(NCNFwd), _P])
+SIGNATURES['tgmx_ncn8_lds_max_nodes'] = (c_int32, [])
+SIGNATURES['tgmx_ncn8_workspace_bytes'] = (c_size_t, [c_int64, c_int64])
+SIGNATURES['tgmx_ncn8_cn_emb'] = (c_int32, [_P, c_int64, c_int32, _P, _P, _P, c_int32, c_int64, c_int64, _P, _P, _P, _P, c_int64, _P, c_size_t, c_int32,
+                                            _P])  # fmt: skip
+SIGNATURES['tgmx_ncn8_forward'] = (c_int32, [ctypes.POINTER(NCNFwd), _P, c_size_t, _P])
 
 
 class NcnBwd(ctypes.Structure):

@@ -65,6 +65,16 @@ __global__ __launch_bounds__(256) void ncn_last_kernel(const void* __restrict__ 
   }
 }
 
+int ncn_last_marks(const void* tar, int tar_is64, long long tar_stride, long long B, long long N, int32_t* last, hipStream_t st) {
+  if (hipMemsetAsync(last, 0xff, (size_t)N * 2 * sizeof(int32_t), st) != hipSuccess) {  // -1: the id occurs nowhere
+    set_error("ncn_cn_emb: clearing the last-occurrence marks failed");
+    return TGMX_E_LAUNCH;
+  }
+  hipLaunchKernelGGL(ncn_last_kernel, dim3(grid_for(2 * B, 256, 4096)), dim3(256), 0, st, tar, tar_is64, tar_stride, B, N, last);
+  TGMX_CHECK_LAUNCH("ncn_cn_emb(last)");
+  return TGMX_OK;
+}
+
 struct CnArgs {
   const float* x;
   long long N;
@@ -207,15 +217,8 @@ extern "C" int tgmx_ncn_cn_emb(const float* x, int64_t N, int32_t C, int32_t k, 
   TGMX_REQUIRE(x && indptr && cols && tar && xs, "ncn_cn_emb: null pointer");
   TGMX_REQUIRE((last_update == nullptr) == (edge_time == nullptr), "ncn_cn_emb: time decay needs last_update and edge_time");
   hipStream_t st = (hipStream_t)stream;
-  if (last) {
-    if (hipMemsetAsync(last, 0xff, (size_t)N * 2 * sizeof(int32_t), st) != hipSuccess) {  // -1: the id occurs nowhere
-      set_error("ncn_cn_emb: clearing the last-occurrence marks failed");
-      return TGMX_E_LAUNCH;
-    }
-    hipLaunchKernelGGL(ncn_last_kernel, dim3(grid_for(2 * B, 256, 4096)), dim3(256), 0, st, tar, tar_is64, (long long)tar_stride, (long long)B,
-                       (long long)N, last);
-    TGMX_CHECK_LAUNCH("ncn_cn_emb(last)");
-  }
+  int rc;
+  if (last && (rc = ncn_last_marks(tar, tar_is64, (long long)tar_stride, (long long)B, (long long)N, last, st))) return rc;
   CnArgs a{x, (long long)N, C, k, indptr, cols, tar, tar_is64, (long long)tar_stride, (long long)B, last_update, edge_time, last, xs, (long long)ldxs};
   hipLaunchKernelGGL(ncn_cn_kernel, dim3(grid_for(B, kNcnWaves, 16384)), dim3(kNcnThreads), 0, st, a);
   TGMX_CHECK_LAUNCH("ncn_cn_emb");

@@ -25,4 +25,8 @@ __device__ __forceinline__ float decay_weight(const int64_t* __restrict__ last_u
   return expf(-(gap / 10000.f));
 }
 
+// last [2 N] int32: the last position at which every id occurs as a source (last[id]) and as a destination (last[N + id]), -1 where it does
+// not; a pair with a target outside [0, N) marks nothing (ncn.hip; the k = 2 / 4 and the k = 8 pair kernels read the same marks)
+int ncn_last_marks(const void* tar, int tar_is64, long long tar_stride, long long B, long long N, int32_t* last, hipStream_t st);
+
 }  // namespace tgmx

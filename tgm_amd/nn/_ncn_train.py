@@ -40,8 +40,9 @@ def _up64(n: int) -> int:
 
 
 def in_envelope(module, x: Tensor) -> bool:
-    """The native training path takes the call: no autocast, contiguous float32 parameters on x's device."""
-    if mode() == 'torch' or torch.is_autocast_enabled():
+    """The native training path takes the call: k = 2 / 4 (there is no native k = 8 backward), no autocast, contiguous float32 parameters on
+    x's device."""
+    if module.k == 8 or mode() == 'torch' or torch.is_autocast_enabled():
         return False
     return all(p.dtype == torch.float32 and p.is_contiguous() and p.device == x.device for p in param_list(module))
 

@@ -9,6 +9,13 @@ sampled subgraph (``A[a, b]`` = how often ``(a, b)`` or ``(b, a)`` occurs in ``e
 
     k = 2:  xs = [x[tar_i] * x[tar_j] | ((R_i o R_j) o W) x]
     k = 4:  xs = [x[tar_i] * x[tar_j] | ((I_i o R_j) o W) x | ((R_i o I_j) o W) x | ((R_i o R_j) o W) x]
+    k = 8:  with A2 = A A, K3 = A2 A, S_i[r] = A2[tar_i[r]] (kept as R_i is), u[r] = -A[tar_i[r], tar_j[r]] where both sides keep row r (else 0):
+            c01 = I_i o R_j    c10 = R_i o I_j    c11 = R_i o R_j    sp = c11 A
+            c12 = R_i o S_j + R_i o R_i u         c21 = S_i o R_j + R_j o R_j u
+            c22 = S_i o S_j + ([R_i > 0] K3[tar_i, tar_i] + [R_j > 0] K3[tar_j, tar_j] - c11) u + sp
+            c12, c21, c22: columns tar_i[r] and tar_j[r] of row r set to 0, then c22 = max(c22, 0)
+            xs = [x[tar_i] * x[tar_j] | (c01 o W) x | (c10 o W) x | (c11 o W) x | (c12 o W) x | (c21 o W) x | (c22 o W) x | sp x]
+            (sp carries no decay and no column mask; every block is zero unless both sides keep row r)
     out = xsmlp(xs).view(-1)
 
 Three quirks of the reference are part of the contract:
@@ -29,7 +36,7 @@ Inference (no gradient needed) is ONE native call, ``tgmx_ncn_forward``: a radix
 per pair intersects two sorted rows and gather-sums ``x`` over the matches in ascending id (deterministic, no float atomics), then the two
 Linear layers on the exact-fp32 GEMM.
 
-Training (autograd has something to track) is native too: ``forward`` is the same ``tgmx_ncn_forward`` call, writing what the backward
+Training (autograd has something to track) is native too at k = 2 / 4: ``forward`` is the same ``tgmx_ncn_forward`` call, writing what the backward
 reads into buffers of the call (so the result is the no-grad call's bit for bit, and the positives' and negatives' calls of one step do
 not share them), and the backward is ONE native call, ``tgmx_ncn_backward`` (``_ncn_train.py``, ``csrc/ncn_bwd.hip``): the two Linear layers
 from the shared blocks, then ``dx`` node by node through two inverted indexes of the pairs and the forward's adjacency -- fixed summation
@@ -38,8 +45,15 @@ only) and ``xslin`` gets ``None``.  Outside that path -- autocast, parameters of
 ``TGMX_NCN_BWD=torch`` -- the same arithmetic is composed from torch ops on the device under autograd, through dense ``[B, N]`` rows (never
 ``[N, N]``).  ``TGMX_NCN_BWD=py`` issues the native backward's launches one ctypes call each (the same bits).
 
-``k = 8`` is accepted by the constructor and not implemented: ``forward`` raises ``NotImplementedError``.  CPU tensors raise
-``NativeLibraryError``.  A pair with a target id outside ``[0, N)`` gives a zero row, and no gradient, on every path.
+``k = 8`` (two-hop common neighbours) has its own native stage, ``tgmx_ncn8_forward`` (``csrc/ncn8.hip``): one workgroup per pair expands the
+two targets' neighbours' rows into integer count rows (in LDS up to 7680 local ids, in a workspace above), forms every coefficient as an
+exact integer and gather-sums ``x`` over ascending ids in float64, rounded once -- nothing ``[N, N]``, no ``[B, N]`` float matrix, the same
+bits every run; the two Linear layers, whose 8 C inputs carry those integer weights, run in float64 too (one kernel, rounded once; ``hidden_dim`` up to 8192, a wider layer is an error).  Inference takes it; with gradients k = 8 is the composed torch path (``[B, N]`` rows and ``index_add_`` over the half-edges;
+the coefficients carry no gradient), a native k = 8 backward does not exist yet.  One behaviour of the reference is NOT reproduced at k = 8:
+it multiplies dense coefficient matrices by ``W``, so a weight that overflows to ``inf`` (``edge_time - last_update`` below about -8.8e5)
+turns the zero counts of that row into NaN; here ``W`` multiplies only non-zero counts, as at k = 2 / 4.  On host tensors k = 8 raises
+``NotImplementedError`` (device only); k = 2 / 4 raise ``NativeLibraryError`` there.  A pair with a target id outside ``[0, N)`` gives a zero
+row, and no gradient, on every path.
 """
 from __future__ import annotations
 
@@ -104,8 +118,8 @@ class NCNPredictor(TransientCaches, nn.Module):
     r"""Temporal Neural Common Neighbor decoder; see the module docstring for the arithmetic, the reference's quirks that are part of the
     contract and for what runs natively.
 
-    Args (the reference's): in_channels, hidden_dim, out_channels, k (2 / 4 / 8: the hops of common-neighbour extraction; 8 is not
-    implemented), cn_time_decay.  ``duplicate_targets``: ``'last'`` (the reference's CPU behaviour) or ``'all'``.
+    Args (the reference's): in_channels, hidden_dim, out_channels, k (2 / 4 / 8: the hops of common-neighbour extraction; 8 adds the
+    two-hop blocks), cn_time_decay.  ``duplicate_targets``: ``'last'`` (the reference's CPU behaviour) or ``'all'``.
     """
 
     def __init__(self, in_channels: int, hidden_dim: int, out_channels: int, k: int = 2, cn_time_decay: bool = False, *,
@@ -129,8 +143,8 @@ class NCNPredictor(TransientCaches, nn.Module):
                 edge_time: Optional[Tensor]) -> dict:  # fmt: skip
         if self.cn_time_decay and (last_update is None or edge_time is None):
             raise RuntimeError('Please provide time_information to perform time decay')
-        if self.k == 8:
-            raise NotImplementedError('tgm_amd NCNPredictor: k = 8 is not implemented (k = 2 and k = 4 are)')
+        if self.k == 8 and x.device.type != 'cuda':
+            raise NotImplementedError(f'tgm_amd NCNPredictor: k = 8 runs on device tensors only (x lives on {x.device})')
         _native.require_device(x, 'x')
         _native.require_device(tar_ei, 'tar_ei')
         if x.dim() != 2 or x.shape[1] != self.in_channels:
@@ -206,7 +220,7 @@ class NCNPredictor(TransientCaches, nn.Module):
         ok = inside(ti) & inside(tj)
         ti, tj = ti.clamp(0, N - 1), tj.clamp(0, N - 1)
 
-        def rows_of(t: Tensor) -> Tuple[Tensor, Tensor]:
+        def rows_of(t: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
             keep = ok
             if self.duplicate_targets == 'last':
                 last = torch.full((N,), -1, dtype=torch.int64, device=dev).scatter_reduce(0, t, torch.where(ok, ar, -1), 'amax')
@@ -216,14 +230,45 @@ class NCNPredictor(TransientCaches, nn.Module):
                 R.index_add_(1, hcol, (hrow[None, :] == t[:, None]).float())  # [B, 2 E] -> [B, N]: counts, exact in float32
             I = torch.zeros((B, N), dtype=torch.float32, device=dev)
             I[ar, t] = 1.0
-            return R * keep[:, None], I * keep[:, None]
+            return R * keep[:, None], I * keep[:, None], keep
 
-        Ri, Ii = rows_of(ti)
-        Rj, Ij = rows_of(tj)
+        Ri, Ii, ki = rows_of(ti)
+        Rj, Ij, kj = rows_of(tj)
         W = torch.exp(-((a['et'][:, None] - a['lu'][None, :]).to(torch.float32) / 10000)) if self.cn_time_decay else None
+        xij = x[ti] * x[tj] * ok[:, None]
+        if self.k == 8:
+            return torch.cat([xij] + self._torch_cn8(x, ti, tj, ki & kj, Ri, Rj, Ii, Ij, W, hrow, hcol), dim=-1)
         blocks = [(Ri * Rj)] if self.k == 2 else [Ii * Rj, Ri * Ij, Ri * Rj]
         cn = [(b * W if W is not None else b) @ x for b in blocks]
-        return torch.cat([x[ti] * x[tj] * ok[:, None]] + cn, dim=-1)
+        return torch.cat([xij] + cn, dim=-1)
+
+    @staticmethod
+    def _torch_cn8(x: Tensor, ti: Tensor, tj: Tensor, both: Tensor, Ri: Tensor, Rj: Tensor, Ii: Tensor, Ij: Tensor, W: Optional[Tensor], hrow: Tensor,
+                   hcol: Tensor) -> list:  # fmt: skip
+        """The seven k = 8 blocks from [B, N] rows of exact float32 counts (never [N, N]); only ``... @ x`` carries a gradient."""
+        B, N = Ri.shape
+        ar = torch.arange(B, device=x.device)
+
+        def hop(M: Tensor) -> Tensor:  # M A: every half-edge (a -> b) adds column a of M onto column b (a slot behind the last row: column N, zeros)
+            out = torch.zeros_like(M)
+            if hrow.numel():
+                out.index_add_(1, hcol, torch.cat([M, M.new_zeros((B, 1))], dim=1)[:, hrow])
+            return out
+
+        Si, Sj = hop(Ri), hop(Rj)
+        u = -(Ri[ar, tj] * both)[:, None]
+        k3i, k3j = (Ri * Si).sum(dim=1, keepdim=True), (Rj * Sj).sum(dim=1, keepdim=True)  # K3[t, t] = sum over m of A[t, m] A2[t, m]
+        c11 = Ri * Rj
+        sp = hop(c11)
+        cols = torch.ones_like(Ri)  # the column masks: tar_i[r] and tar_j[r] of row r
+        cols[ar, ti] = 0.0
+        cols[ar, tj] = 0.0
+        c12 = (Ri * Sj + Ri * Ri * u) * cols
+        c21 = (Si * Rj + Rj * Rj * u) * cols
+        c22 = ((Si * Sj + ((Ri > 0) * k3i + (Rj > 0) * k3j - c11) * u + sp) * cols).clamp(min=0.0)
+        # W multiplies only non-zero counts, as on the native path (an infinite weight leaves the zeros alone)
+        wt = (lambda b: b) if W is None else (lambda b: torch.where(b != 0, b * W, b))
+        return [wt(b) @ x for b in (Ii * Rj, Ri * Ij, c11, c12, c21, c22)] + [sp @ x]
 
     # -- inference ------------------------------------------------------------------------------------------------------------------------
     def _weights(self) -> tuple:
@@ -236,8 +281,9 @@ class NCNPredictor(TransientCaches, nn.Module):
 
         return cached_block(self, build)
 
-    def _native_xs(self, a: dict, mlp: bool) -> Tuple[Tensor, Optional[Tensor]]:
-        """(xs [B, ldxs] scratch view, out [B, out_channels] or None): ``tgmx_ncn_forward``, or its first two stages for ``get_cn_emb``."""
+    def _native_xs(self, a: dict, mlp: bool, force_workspace: bool = False) -> Tuple[Tensor, Optional[Tensor]]:
+        """(xs [B, ldxs] scratch view, out [B, out_channels] or None): ``tgmx_ncn_forward`` (k = 8: ``tgmx_ncn8_forward``), or its first two
+        stages for ``get_cn_emb``.  ``force_workspace`` (tests; k = 8 without the MLP): the count rows in the workspace whatever N."""
         blk, _ = self._weights()
         lib = _native.load()
         x, N, B, C = a['x'], a['N'], a['B'], self.in_channels
@@ -247,8 +293,15 @@ class NCNPredictor(TransientCaches, nn.Module):
         E = adj.num_edges if adj is not None else a['ei'].shape[1]
         need = 0 if adj is not None else _adj_ws_bytes(E)
         own = 0 if adj is not None else (N + 1) + max(2 * E, 1)
-        # floats and int32 share the scratch buffer: xs, h, last [2 N], then (without a prepared adjacency) indptr, cols, the sort's workspace
-        xs, h, last, ints, ws = carve_scratch(self, [B * ldxs, B * ldh, 2 * N, own, (need + 3) // 4], dev)
+        need8 = 0
+        if self.k == 8:
+            # host arithmetic only; a few bytes while the count rows fit LDS
+            need8 = int(lib.tgmx_ncn8_workspace_bytes(max(N, int(lib.tgmx_ncn8_lds_max_nodes())) + 1 if force_workspace else N, B))
+            if need8 == 0:
+                raise ValueError(f'NCNPredictor: N = {N}, B = {B} are more than the k = 8 stage indexes (< 2^31)')
+        # floats and int32 share the scratch buffer: xs, h, last [2 N], then (without a prepared adjacency) indptr, cols, the sort's workspace,
+        # and the k = 8 stage's count rows where they do not fit LDS
+        xs, h, last, ints, ws, ws8 = carve_scratch(self, [B * ldxs, B * ldh, 2 * N, own, (need + 3) // 4, (need8 + 3) // 4], dev)
         blk.x, blk.N = x.data_ptr(), N
         blk.decay, blk.dup_all = int(self.cn_time_decay), int(self.duplicate_targets == 'all')
         if adj is not None:
@@ -266,11 +319,19 @@ class NCNPredictor(TransientCaches, nn.Module):
         if mlp:
             out = torch.empty((B, self.out_channels), dtype=torch.float32, device=dev)
             blk.out = out.data_ptr()
-            _native.check(lib.tgmx_ncn_forward(ctypes.byref(blk), _native.stream_ptr()), 'tgmx_ncn_forward')
+            if self.k == 8:
+                _native.check(lib.tgmx_ncn8_forward(ctypes.byref(blk), ws8.data_ptr(), need8, _native.stream_ptr()), 'tgmx_ncn8_forward')
+            else:
+                _native.check(lib.tgmx_ncn_forward(ctypes.byref(blk), _native.stream_ptr()), 'tgmx_ncn_forward')
             return xs[: B * ldxs].view(B, ldxs), out
         if adj is None:
             _native.check(lib.tgmx_ncn_adj_build(blk.edge_index, blk.ei_is64, blk.ei_stride, E, N, blk.indptr, blk.cols, blk.adj_ws, need,
                                                  _native.stream_ptr()), 'tgmx_ncn_adj_build')  # fmt: skip
+        if self.k == 8:
+            _native.check(lib.tgmx_ncn8_cn_emb(blk.x, N, C, blk.indptr, blk.cols, blk.tar, blk.tar_is64, blk.tar_stride, B, blk.last_update if self.cn_time_decay else 0,
+                                               blk.edge_time if self.cn_time_decay else 0, 0 if blk.dup_all else blk.last, blk.xs, ldxs, ws8.data_ptr(), need8,
+                                               int(force_workspace), _native.stream_ptr()), 'tgmx_ncn8_cn_emb')  # fmt: skip
+            return xs[: B * ldxs].view(B, ldxs), None
         _native.check(lib.tgmx_ncn_cn_emb(blk.x, N, C, self.k, blk.indptr, blk.cols, blk.tar, blk.tar_is64, blk.tar_stride, B, blk.last_update if self.cn_time_decay else 0,
                                           blk.edge_time if self.cn_time_decay else 0, 0 if blk.dup_all else blk.last, blk.xs, ldxs, _native.stream_ptr()),
                       'tgmx_ncn_cn_emb')  # fmt: skip
