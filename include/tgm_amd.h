@@ -1483,8 +1483,8 @@ typedef struct tgmx_ncn_fwd {
 } tgmx_ncn_fwd_t;
 int tgmx_ncn_forward(const tgmx_ncn_fwd_t* args, tgmx_stream_t stream);
 
-/* ---- NCNPredictor at k = 8 (csrc/ncn8.hip): the two-hop common-neighbour blocks.  tgmx_ncn_cn_emb / tgmx_ncn_forward and the backward
- * entries below keep refusing k = 8; these three take it.  With A2 = A A, K3 = A2 A, u = -A[i, j], R = A[t], S = A2[t] for the pair (i, j):
+/* ---- NCNPredictor at k = 8 (csrc/ncn8.hip): the two-hop common-neighbour blocks.  tgmx_ncn_cn_emb / tgmx_ncn_forward and tgmx_ncn_dx /
+ * tgmx_ncn_backward below keep refusing k = 8; these three take it (its backward: the tgmx_ncn8_* entries behind tgmx_ncn_backward).  With A2 = A A, K3 = A2 A, u = -A[i, j], R = A[t], S = A2[t] for the pair (i, j):
  *   c01[i] = A[j, i]   c10[j] = A[i, j]   c11 = R_i o R_j   sp = c11 A
  *   c12 = R_i o S_j + R_i o R_i u      c21 = S_i o R_j + R_j o R_j u
  *   c22 = S_i o S_j + ([R_i > 0] K3[i, i] + [R_j > 0] K3[j, j] - c11) u + sp
@@ -1544,6 +1544,42 @@ typedef struct tgmx_ncn_bwd {
 } tgmx_ncn_bwd_t;
 size_t tgmx_ncn_backward_workspace_bytes(const tgmx_ncn_bwd_t* args);
 int tgmx_ncn_backward(const tgmx_ncn_bwd_t* args, tgmx_stream_t stream);
+
+/* ---- NCNPredictor training at k = 8 (csrc/ncn8_bwd.hip).  tgmx_ncn_dx / tgmx_ncn_backward above keep refusing k = 8; these take it.  With
+ * g_b[r] the C-wide block b = 0 .. 7 of dxs[r] and T[8 r + b, n] the coefficient tgmx_ncn8_cn_emb applied to x[n] in block b of pair r (the
+ * count times W[r, n] on blocks 1-6, where the count is non-zero; the bare count on block 7; row 8 r zero; rows 8 r + 1 .. 8 r + 7 zero for a
+ * pair that is not active under the forward's rule, or has a target outside [0, N)):
+ *   dx[n] = sum over in-range r, tar_i[r] = n of g_0[r] * x[tar_j[r]] + sum over in-range r, tar_j[r] = n of g_0[r] * x[tar_i[r]] + (T^T dxs)[n]
+ * dxs [B, 8 C] is read as an [8 B, C] matrix, so it must be contiguous (lddxs = 8 C).  T is never formed whole: slabs of P pairs
+ * ([8 P, ldT], ldT = N rounded up to 64), in ascending pair order, each multiplied by tgmx_sgemm_tn (accumulate) onto what the pair term
+ * stored.  P = tgmx_ncn8_backward_slab_pairs(N, B, slab_pairs): slab_pairs > 0 forces min(slab_pairs, B) (tests); 0 is the budget rule
+ * min(B, max(1, 256 MiB / (32 ldT))).  No float atomics; the order of dx's sum is fixed by (sizes, P): two runs give the same bits, two
+ * slab sizes agree only within rounding.  Nothing [B, N] outlives the call.  2 N, 2 B < 2^31.  Every workspace function is host arithmetic
+ * only (0: a size out of range). */
+int64_t tgmx_ncn8_backward_slab_pairs(int64_t N, int64_t B, int64_t slab_pairs);
+/* Rows 8 s .. 8 s + 7 of T [8 P, ldT] for the pairs first + s, s < P (first + P <= B; ldT >= N, a multiple of 64): one workgroup per pair
+ * builds the forward's int32 count rows (LDS, or the workspace above tgmx_ncn8_lds_max_nodes() ids / with force_workspace) and stores every
+ * one of the 8 ldT floats, zeros included -- the slab needs no clearing.  Each entry is (double)count * W rounded once, W exactly the
+ * forward's.  workspace: tgmx_ncn8_workspace_bytes(N, P), as tgmx_ncn8_cn_emb (force_workspace likewise).  last: as tgmx_ncn_dx. */
+int tgmx_ncn8_coef(int64_t N, const int32_t* indptr, const int32_t* cols, const void* tar, int32_t tar_is64, int64_t tar_stride, int64_t B,
+                   const int64_t* last_update, const int64_t* edge_time, const int32_t* last, int64_t first, int64_t P, float* T, int64_t ldT,
+                   void* workspace, size_t workspace_bytes, int32_t force_workspace, tgmx_stream_t stream);
+/* The first two sums: a wave per node through two inverted indexes of the pairs (tgmx_ncn_dx's: ONE radix sort of 2 B keys), ascending r,
+ * one fmaf per term; a pair with tar_i = tar_j is in both lists.  EVERY row of dx [N, C] is stored.  lddxs >= C (only block 0 is read). */
+size_t tgmx_ncn8_dx_pairs_workspace_bytes(int64_t N, int64_t B);
+int tgmx_ncn8_dx_pairs(const float* x, int64_t N, int32_t C, const void* tar, int32_t tar_is64, int64_t tar_stride, int64_t B,
+                       const float* dxs, int64_t lddxs, float* dx, void* workspace, size_t workspace_bytes, tgmx_stream_t stream);
+/* dx as above: the pair term, then per slab tgmx_ncn8_coef's launch and the product.  lddxs must be 8 C. */
+size_t tgmx_ncn8_dx_workspace_bytes(int64_t N, int64_t B, int32_t C, int64_t slab_pairs, int32_t force_workspace);
+int tgmx_ncn8_dx(const float* x, int64_t N, int32_t C, const int32_t* indptr, const int32_t* cols, const void* tar, int32_t tar_is64,
+                 int64_t tar_stride, int64_t B, const int64_t* last_update, const int64_t* edge_time, const int32_t* last, const float* dxs,
+                 int64_t lddxs, float* dx, int64_t slab_pairs, void* workspace, size_t workspace_bytes, int32_t force_workspace,
+                 tgmx_stream_t stream);
+/* The k = 8 backward as ONE call: tgmx_ncn_backward's argument block (fwd: the block tgmx_ncn8_forward ran with, k = 8, H <= 8192; the ReLU
+ * mask is read from the float32 h its MLP kernel stored) and its two-Linear-layer launches, exactly (the same function), then tgmx_ncn8_dx
+ * (the count rows in LDS or the workspace by N).  A NULL gradient pointer skips its launches; B = 0 zeroes the gradients asked for. */
+size_t tgmx_ncn8_backward_workspace_bytes(const tgmx_ncn_bwd_t* args, int64_t slab_pairs);
+int tgmx_ncn8_backward(const tgmx_ncn_bwd_t* args, int64_t slab_pairs, tgmx_stream_t stream);
 
 /* ---- EdgeBankPredictor (the reference's tgm/nn/modules/edgebank.py): the edge memory as a device hash table ---- */
 

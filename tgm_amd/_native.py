@@ -637,6 +637,16 @@ SIGNATURES['tgmx_ncn_dx'] = (c_int32, [_P, c_int64, c_int32, c_int32, _P, _P, c_
                                        _P, c_size_t, _P])  # fmt: skip
 SIGNATURES['tgmx_ncn_backward_workspace_bytes'] = (c_size_t, [ctypes.POINTER(NcnBwd)])
 SIGNATURES['tgmx_ncn_backward'] = (c_int32, [ctypes.POINTER(NcnBwd), _P])
+SIGNATURES['tgmx_ncn8_backward_slab_pairs'] = (c_int64, [c_int64, c_int64, c_int64])
+SIGNATURES['tgmx_ncn8_coef'] = (c_int32, [c_int64, _P, _P, _P, c_int32, c_int64, c_int64, _P, _P, _P, c_int64, c_int64, _P, c_int64, _P, c_size_t,
+                                          c_int32, _P])  # fmt: skip
+SIGNATURES['tgmx_ncn8_dx_pairs_workspace_bytes'] = (c_size_t, [c_int64, c_int64])
+SIGNATURES['tgmx_ncn8_dx_pairs'] = (c_int32, [_P, c_int64, c_int32, _P, c_int32, c_int64, c_int64, _P, c_int64, _P, _P, c_size_t, _P])
+SIGNATURES['tgmx_ncn8_dx_workspace_bytes'] = (c_size_t, [c_int64, c_int64, c_int32, c_int64, c_int32])
+SIGNATURES['tgmx_ncn8_dx'] = (c_int32, [_P, c_int64, c_int32, _P, _P, _P, c_int32, c_int64, c_int64, _P, _P, _P, _P, c_int64, _P, c_int64, _P,
+                                        c_size_t, c_int32, _P])  # fmt: skip
+SIGNATURES['tgmx_ncn8_backward_workspace_bytes'] = (c_size_t, [ctypes.POINTER(NcnBwd), c_int64])
+SIGNATURES['tgmx_ncn8_backward'] = (c_int32, [ctypes.POINTER(NcnBwd), c_int64, _P])
 
 
 class EdgeBank(ctypes.Structure):

@@ -245,16 +245,8 @@ __global__ __launch_bounds__(kNcnBwdThreads) void ncn_bwd_join_kernel(DxArgs a) 
 
 static size_t ncn_bwd_chunks(long long E) { return 2 * E > kNcnBwdLongRow ? (size_t)((2 * E + kNcnBwdChunk - 1) / kNcnBwdChunk) : 0; }
 
-struct DxWorkspace {
-  unsigned long long *k_in, *k_out;
-  char* temp;
-  size_t temp_bytes;
-  int32_t *bt_ptr, *bt_r;
-  float* scratch;
-  size_t total;
-};
-static int dx_carve(void* workspace, long long N, long long E, long long B, int C, DxWorkspace& w) {
-  WorkspaceCarver c(workspace);
+// ---- the two inverted indexes of the pairs (ncn_rows.h; ncn8_bwd.hip builds the same) ----
+int ncn_pair_index_carve(WorkspaceCarver& c, long long N, long long B, NcnPairIndex& w) {
   const size_t n = (size_t)(B > 0 ? 2 * B : 1);
   w.k_in = c.take<unsigned long long>(n);
   w.k_out = c.take<unsigned long long>(n);
@@ -262,8 +254,36 @@ static int dx_carve(void* workspace, long long N, long long E, long long B, int 
   if (rocprim::radix_sort_keys(nullptr, w.temp_bytes, (const unsigned long long*)nullptr, (unsigned long long*)nullptr, n, 0u, 64u) != hipSuccess)
     return TGMX_E_LAUNCH;
   w.temp = c.take<char>(w.temp_bytes);
-  w.bt_ptr = c.take<int32_t>((size_t)(2 * N + 1));
-  w.bt_r = c.take<int32_t>(n);
+  w.ptr = c.take<int32_t>((size_t)(2 * N + 1));
+  w.r = c.take<int32_t>(n);
+  return TGMX_OK;
+}
+
+int ncn_pair_index_build(const void* tar, int tar_is64, long long tar_stride, long long B, long long N, const NcnPairIndex& w, const char* who,
+                         hipStream_t st) {
+  const int cb = col_bits(2 * N > B ? 2 * N : B);
+  const long long n = 2 * B;
+  hipLaunchKernelGGL(ncn_bwd_keys_kernel, dim3(grid_for(n, 256, 4096)), dim3(256), 0, st, tar, tar_is64 ? 1 : 0, tar_stride, B, N, cb, w.k_in);
+  TGMX_CHECK_LAUNCH(who);  // (the keys)
+  size_t temp_bytes = w.temp_bytes;
+  if (rocprim::radix_sort_keys(w.temp, temp_bytes, (const unsigned long long*)w.k_in, w.k_out, (size_t)n, 0u, (unsigned)(2 * cb + 1), st) !=
+      hipSuccess) {
+    set_error("%s: radix sort of the pair keys failed", who);
+    return TGMX_E_LAUNCH;
+  }
+  csr_rows_launch(w.k_out, n, 2 * N, cb, w.ptr, w.r, NoEntryValue{}, st);
+  TGMX_CHECK_LAUNCH(who);  // (the rows)
+  return TGMX_OK;
+}
+
+struct DxWorkspace {
+  NcnPairIndex bt;
+  float* scratch;
+  size_t total;
+};
+static int dx_carve(void* workspace, long long N, long long E, long long B, int C, DxWorkspace& w) {
+  WorkspaceCarver c(workspace);
+  if (ncn_pair_index_carve(c, N, B, w.bt) != TGMX_OK) return TGMX_E_LAUNCH;
   w.scratch = c.take<float>(ncn_bwd_chunks(E) * 2 * (size_t)C);
   w.total = c.total();
   return TGMX_OK;
@@ -306,21 +326,11 @@ extern "C" int tgmx_ncn_dx(const float* x, int64_t N, int32_t C, int32_t k, cons
     set_error("ncn_dx: workspace too small (%zu bytes)", workspace_bytes);
     return TGMX_E_INVALID;
   }
-  const int cb = col_bits(2 * N > B ? 2 * N : B);
-  const long long n = 2 * B;
-  hipLaunchKernelGGL(ncn_bwd_keys_kernel, dim3(grid_for(n, 256, 4096)), dim3(256), 0, st, tar, tar_is64 ? 1 : 0, (long long)tar_stride, (long long)B,
-                     (long long)N, cb, w.k_in);
-  TGMX_CHECK_LAUNCH("ncn_dx(keys)");
-  if (rocprim::radix_sort_keys(w.temp, w.temp_bytes, (const unsigned long long*)w.k_in, w.k_out, (size_t)n, 0u, (unsigned)(2 * cb + 1), st) !=
-      hipSuccess) {
-    set_error("ncn_dx: radix sort failed");
-    return TGMX_E_LAUNCH;
-  }
-  csr_rows_launch(w.k_out, n, 2 * (long long)N, cb, w.bt_ptr, w.bt_r, NoEntryValue{}, st);
-  TGMX_CHECK_LAUNCH("ncn_dx(rows)");
+  int rc;
+  if ((rc = ncn_pair_index_build(tar, tar_is64, (long long)tar_stride, (long long)B, (long long)N, w.bt, "ncn_dx", st))) return rc;
   const size_t chunks = ncn_bwd_chunks(E);
   DxArgs a{x, (long long)N, C, k, indptr, cols, tar, tar_is64 ? 1 : 0, (long long)tar_stride, (long long)B, last_update, edge_time, last, dxs,
-           (long long)lddxs, w.bt_ptr, w.bt_r, dx, chunks ? kNcnBwdLongRow : 0x7fffffff, chunks ? w.scratch : nullptr};
+           (long long)lddxs, w.bt.ptr, w.bt.r, dx, chunks ? kNcnBwdLongRow : 0x7fffffff, chunks ? w.scratch : nullptr};
   hipLaunchKernelGGL(ncn_bwd_node_kernel, dim3(grid_for(N, kNcnBwdWaves, 16384)), dim3(kNcnBwdThreads), 0, st, a);
   TGMX_CHECK_LAUNCH("ncn_dx(nodes)");
   if (chunks) {
@@ -342,17 +352,17 @@ static int ncn_bwd_check(const tgmx_ncn_bwd_t* t, const char* who) {
   return TGMX_OK;
 }
 
-// One walk over the backward; dry: only the workspace is laid out (*need = its bytes), nothing is launched
-static int ncn_backward_pass(const tgmx_ncn_bwd_t* t, bool dry, size_t* need, tgmx_stream_t stream) {
-  const tgmx_ncn_fwd_t& a = t->fwd;
-  const int H = a.H, O = a.out_ch, K = a.k * a.C;
-  const int64_t B = a.B;
-  int rc;
 #define RUN(call)                         \
   do {                                    \
     if (!dry && (rc = (call))) return rc; \
   } while (0)
-  WorkspaceCarver ws(dry ? nullptr : t->workspace);
+
+// the two Linear layers (ncn_rows.h): k = 2 / 4 and k = 8 run the same launches
+int tgmx::ncn_mlp_backward(const tgmx_ncn_bwd_t* t, WorkspaceCarver& ws, bool dry, float** dxs_out, tgmx_stream_t stream) {
+  const tgmx_ncn_fwd_t& a = t->fwd;
+  const int H = a.H, O = a.out_ch, K = a.k * a.C;
+  const int64_t B = a.B;
+  int rc;
   const bool want_dpre = t->d_x || t->d_w1 || t->d_b1;
   const bool tail = ncn_tail_route(O, H);
   float* dpre = ws.take<float>(want_dpre ? (size_t)B * H : 0);
@@ -391,18 +401,43 @@ static int ncn_backward_pass(const tgmx_ncn_bwd_t* t, bool dry, size_t* need, tg
   // the first layer, in the parameters' own layouts
   if (t->d_w1 && (rc = tn(dpre, H, a.xs, a.ldxs, t->d_w1, K, H, K))) return rc;
   if (t->d_b1 && (rc = colsum(dpre, H, H, t->d_b1))) return rc;
+  if (t->d_x) RUN(tgmx_sgemm_nt(dpre, H, w1t, H, dxs, K, B, K, H, nullptr, 0, 1, 0, 0, 0, stream));
+  *dxs_out = dxs;
+  return TGMX_OK;
+}
+
+int tgmx::ncn_backward_empty(const tgmx_ncn_bwd_t* t, const char* who, tgmx_stream_t stream) {
+  const tgmx_ncn_fwd_t& a = t->fwd;
+  const int K = a.k * a.C;
+  hipStream_t st = (hipStream_t)stream;
+  const struct { float* p; size_t n; } z[5] = {{t->d_x, (size_t)a.N * a.C}, {t->d_w1, (size_t)a.H * K}, {t->d_b1, (size_t)a.H},
+                                              {t->d_w2, (size_t)a.out_ch * a.H}, {t->d_b2, (size_t)a.out_ch}};
+  for (const auto& e : z)
+    if (e.p && hipMemsetAsync(e.p, 0, e.n * sizeof(float), st) != hipSuccess) {
+      set_error("%s: clearing a gradient failed", who);
+      return TGMX_E_LAUNCH;
+    }
+  return TGMX_OK;
+}
+
+// One walk over the backward; dry: only the workspace is laid out (*need = its bytes), nothing is launched
+static int ncn_backward_pass(const tgmx_ncn_bwd_t* t, bool dry, size_t* need, tgmx_stream_t stream) {
+  const tgmx_ncn_fwd_t& a = t->fwd;
+  int rc;
+  WorkspaceCarver ws(dry ? nullptr : t->workspace);
+  float* dxs = nullptr;
+  if ((rc = ncn_mlp_backward(t, ws, dry, &dxs, stream))) return rc;
   if (t->d_x) {
-    RUN(tgmx_sgemm_nt(dpre, H, w1t, H, dxs, K, B, K, H, nullptr, 0, 1, 0, 0, 0, stream));
-    const size_t bytes = tgmx_ncn_dx_workspace_bytes(a.N, a.E, B, a.C);
+    const size_t bytes = tgmx_ncn_dx_workspace_bytes(a.N, a.E, a.B, a.C);
     if (bytes == 0) return TGMX_E_INVALID;
     char* dws = ws.take<char>(bytes);
-    RUN(tgmx_ncn_dx(a.x, a.N, a.C, a.k, a.indptr, a.cols, a.E, a.tar, a.tar_is64, a.tar_stride, B, a.decay ? a.last_update : nullptr,
-                    a.decay ? a.edge_time : nullptr, a.dup_all ? nullptr : a.last, dxs, K, t->d_x, dws, bytes, stream));
+    RUN(tgmx_ncn_dx(a.x, a.N, a.C, a.k, a.indptr, a.cols, a.E, a.tar, a.tar_is64, a.tar_stride, a.B, a.decay ? a.last_update : nullptr,
+                    a.decay ? a.edge_time : nullptr, a.dup_all ? nullptr : a.last, dxs, (int64_t)a.k * a.C, t->d_x, dws, bytes, stream));
   }
-#undef RUN
   *need = ws.total();
   return TGMX_OK;
 }
+#undef RUN
 
 extern "C" size_t tgmx_ncn_backward_workspace_bytes(const tgmx_ncn_bwd_t* t) {
   size_t need = 0;
@@ -414,18 +449,7 @@ extern "C" int tgmx_ncn_backward(const tgmx_ncn_bwd_t* t, tgmx_stream_t stream) 
   int rc;
   if ((rc = ncn_bwd_check(t, "ncn_backward"))) return rc;
   const tgmx_ncn_fwd_t& a = t->fwd;
-  const int K = a.k * a.C;
-  if (a.B == 0) {  // no pair: every gradient asked for is zero
-    hipStream_t st = (hipStream_t)stream;
-    const struct { float* p; size_t n; } z[5] = {{t->d_x, (size_t)a.N * a.C}, {t->d_w1, (size_t)a.H * K}, {t->d_b1, (size_t)a.H},
-                                                {t->d_w2, (size_t)a.out_ch * a.H}, {t->d_b2, (size_t)a.out_ch}};
-    for (const auto& e : z)
-      if (e.p && hipMemsetAsync(e.p, 0, e.n * sizeof(float), st) != hipSuccess) {
-        set_error("ncn_backward: clearing a gradient failed");
-        return TGMX_E_LAUNCH;
-      }
-    return TGMX_OK;
-  }
+  if (a.B == 0) return ncn_backward_empty(t, "ncn_backward", stream);  // no pair: every gradient asked for is zero
   TGMX_REQUIRE(t->dout && t->lddout >= a.out_ch, "ncn_backward: no upstream gradient");
   TGMX_REQUIRE(a.x && a.tar && a.w1 && a.w2 && a.xs && a.h && a.indptr && (a.dup_all || a.last) && (!a.decay || (a.last_update && a.edge_time)),
                "ncn_backward: null pointer");

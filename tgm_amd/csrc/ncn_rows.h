@@ -2,6 +2,7 @@
 // one definition, so the backward's W[r, n] and A[a, b] are the forward's, bit for bit.
 #pragma once
 #include "common.h"
+#include "edge_csr.h"
 
 namespace tgmx {
 
@@ -28,5 +29,25 @@ __device__ __forceinline__ float decay_weight(const int64_t* __restrict__ last_u
 // last [2 N] int32: the last position at which every id occurs as a source (last[id]) and as a destination (last[N + id]), -1 where it does
 // not; a pair with a target outside [0, N) marks nothing (ncn.hip; the k = 2 / 4 and the k = 8 pair kernels read the same marks)
 int ncn_last_marks(const void* tar, int tar_is64, long long tar_stride, long long B, long long N, int32_t* last, hipStream_t st);
+
+// ---- what the k = 2 / 4 backward (ncn_bwd.hip) and the k = 8 backward (ncn8_bwd.hip) share; defined in ncn_bwd.hip ----
+// Two inverted indexes of the pairs, by tar_i (rows [0, N)) and by tar_j (rows [N, 2 N)): ptr [2 N + 1], r [2 B] ascending within a row.
+// edge_csr.h's builder over the keys ((side N + target) << cb | r): ONE radix sort of 2 B keys.  A pair with a target outside [0, N) is in
+// neither list.  carve() takes the regions from the caller's carver (the same calls over no workspace give the size); build() launches.
+struct NcnPairIndex {
+  unsigned long long *k_in, *k_out;
+  char* temp;
+  size_t temp_bytes;
+  int32_t *ptr, *r;
+};
+int ncn_pair_index_carve(WorkspaceCarver& c, long long N, long long B, NcnPairIndex& w);
+int ncn_pair_index_build(const void* tar, int tar_is64, long long tar_stride, long long B, long long N, const NcnPairIndex& w, const char* who,
+                         hipStream_t st);  // who: the entry point named in an error
+
+// The two Linear layers' part of the backward, for every k: the weights transposed (one tgmx_pack2d), the last layer, d_w1 = dpre^T xs, d_b1,
+// and -- only when d_x is asked for -- dxs [B, k C] = dpre W1 (contiguous), returned in *dxs.  Its buffers are taken from `ws`; dry: only that.
+int ncn_mlp_backward(const tgmx_ncn_bwd_t* t, WorkspaceCarver& ws, bool dry, float** dxs, tgmx_stream_t stream);
+// B = 0: every gradient asked for is zeroed
+int ncn_backward_empty(const tgmx_ncn_bwd_t* t, const char* who, tgmx_stream_t stream);
 
 }  // namespace tgmx

@@ -40,9 +40,11 @@ def _up64(n: int) -> int:
 
 
 def in_envelope(module, x: Tensor) -> bool:
-    """The native training path takes the call: k = 2 / 4 (there is no native k = 8 backward), no autocast, contiguous float32 parameters on
-    x's device."""
-    if module.k == 8 or mode() == 'torch' or torch.is_autocast_enabled():
+    """The native training path takes the call: no autocast, contiguous float32 parameters on x's device; k = 8 is device-only and takes
+    ``hidden_dim`` up to 8192 (what ``tgmx_ncn8_forward`` takes)."""
+    if mode() == 'torch' or torch.is_autocast_enabled():
+        return False
+    if module.k == 8 and (not x.is_cuda or module.hidden_dim > 8192):
         return False
     return all(p.dtype == torch.float32 and p.is_contiguous() and p.device == x.device for p in param_list(module))
 
@@ -58,7 +60,7 @@ class NcnFunction(torch.autograd.Function):
         adj = a['adj']
         E = adj.num_edges if adj is not None else a['ei'].shape[1]
         ldxs, ldh = up4(k * C), up4(H)
-        c = SimpleNamespace(a=a, adj=adj, N=N, B=B, E=E, weights=(w1, b1, w2, b2))
+        c = SimpleNamespace(a=a, adj=adj, N=N, B=B, E=E, weights=(w1, b1, w2, b2), slab=int(mod._slab_pairs))
         # floats: xs, h;  int32: last [2 N], then (without a prepared adjacency) indptr [N + 1] and cols [2 E] -- all owned by this call
         sizes = [_up64(B * ldxs), _up64(B * ldh)]
         c.acts = torch.empty(sum(sizes), dtype=torch.float32, device=dev)
@@ -73,14 +75,22 @@ class NcnFunction(torch.autograd.Function):
         blk.C, blk.k, blk.H, blk.out_ch = C, k, H, O
         blk.x, blk.N = x.data_ptr(), N
         blk.decay, blk.dup_all = int(mod.cn_time_decay), int(mod.duplicate_targets == 'all')
+        lib = _native.load()
+        need, need8 = 0, 0
+        if adj is None:
+            from .ncn import _adj_ws_bytes
+
+            need = _adj_ws_bytes(E)
+        if k == 8:
+            need8 = int(lib.tgmx_ncn8_workspace_bytes(N, B))  # host arithmetic only; a few bytes while the count rows fit LDS
+            if need8 == 0:
+                raise ValueError(f'NCNPredictor: N = {N}, B = {B} are more than the k = 8 stage indexes (< 2^31)')
+        # (the sort's workspace and the k = 8 forward's count rows: nothing reads them after the call, so they stay in the module's scratch)
+        ws, ws8 = carve_scratch(mod, [(need + 3) // 4, (need8 + 3) // 4], dev)
         if adj is not None:
             blk.edge_index, blk.E, blk.have_adj = None, E, 1
             blk.indptr, blk.cols = adj.indptr.data_ptr(), adj.cols.data_ptr()
         else:
-            from .ncn import _adj_ws_bytes
-
-            need = _adj_ws_bytes(E)
-            ws = carve_scratch(mod, [(need + 3) // 4], dev)[0]  # (the sort's workspace: nothing reads it after the build)
             blk.edge_index, blk.ei_stride, blk.E, blk.ei_is64, blk.have_adj = a['ei'].data_ptr(), a['ei_stride'], E, a['ei_is64'], 0
             blk.indptr, blk.cols = indptr.data_ptr(), cols.data_ptr()
             blk.adj_ws, blk.adj_ws_bytes = ws.data_ptr(), need
@@ -90,7 +100,10 @@ class NcnFunction(torch.autograd.Function):
         blk.last = last.data_ptr()
         blk.xs, blk.h, blk.ldxs, blk.ldh = xs.data_ptr(), h.data_ptr(), ldxs, ldh
         blk.out = c.out.data_ptr()
-        _native.check(_native.load().tgmx_ncn_forward(ctypes.byref(blk), _native.stream_ptr()), 'tgmx_ncn_forward')
+        if k == 8:
+            _native.check(lib.tgmx_ncn8_forward(ctypes.byref(blk), ws8.data_ptr(), need8, _native.stream_ptr()), 'tgmx_ncn8_forward')
+        else:
+            _native.check(lib.tgmx_ncn_forward(ctypes.byref(blk), _native.stream_ptr()), 'tgmx_ncn_forward')
         blk.adj_ws, blk.adj_ws_bytes = None, 0  # (the module's scratch: not the call's to keep)
         ctx.c = c
         return c.out.view(-1)
@@ -114,15 +127,19 @@ class NcnFunction(torch.autograd.Function):
         t.d_x = _native.ptr(dx)
         t.d_w1, t.d_b1, t.d_w2, t.d_b2 = (v.data_ptr() if need else None for v, need in zip(views, need_p))
         if mode() == 'py':
-            backward_per_launch(t, dev, [g for g in (dx, *(v for v, need in zip(views, need_p) if need)) if g is not None])
+            backward_per_launch(t, dev, [g for g in (dx, *(v for v, need in zip(views, need_p) if need)) if g is not None], c.slab)
         else:
             lib = _native.load()
-            need = int(lib.tgmx_ncn_backward_workspace_bytes(ctypes.byref(t)))
+            k8 = blk.k == 8  # (the k = 8 entries take the slab size behind the block)
+            need = int(lib.tgmx_ncn8_backward_workspace_bytes(ctypes.byref(t), c.slab) if k8 else lib.tgmx_ncn_backward_workspace_bytes(ctypes.byref(t)))
             if need == 0:
-                _native.check(-1, 'tgmx_ncn_backward_workspace_bytes')
+                _native.check(-1, 'tgmx_ncn8_backward_workspace_bytes' if k8 else 'tgmx_ncn_backward_workspace_bytes')
             ws = torch.empty(need, dtype=torch.uint8, device=dev)
             t.workspace, t.workspace_bytes = ws.data_ptr(), need
-            _native.check(lib.tgmx_ncn_backward(ctypes.byref(t), _native.stream_ptr()), 'tgmx_ncn_backward')
+            if k8:
+                _native.check(lib.tgmx_ncn8_backward(ctypes.byref(t), c.slab, _native.stream_ptr()), 'tgmx_ncn8_backward')
+            else:
+                _native.check(lib.tgmx_ncn_backward(ctypes.byref(t), _native.stream_ptr()), 'tgmx_ncn_backward')
             t.workspace, t.workspace_bytes = None, 0
         return (None, None, dx, *(v if need else None for v, need in zip(views, need_p)))
 
@@ -138,9 +155,9 @@ def _tail_route(out_ch: int, H: int) -> bool:
     return out_ch <= _native.DECODER_MAX_TAIL and out_ch * H * 4 <= 48 * 1024
 
 
-def backward_per_launch(t, dev, grads=()) -> None:
-    """What ``tgmx_ncn_backward`` composes, in its order with its kernels; every buffer of the native call's workspace is a tensor here
-    (``grads``: the tensors behind the block's gradient pointers)."""
+def backward_per_launch(t, dev, grads=(), slab_pairs: int = 0) -> None:
+    """What ``tgmx_ncn_backward`` (k = 8: ``tgmx_ncn8_backward`` with ``slab_pairs``) composes, in its order with its kernels; every buffer of
+    the native call's workspace is a tensor here (``grads``: the tensors behind the block's gradient pointers)."""
     lib, st = _native.load(), _native.stream_ptr()
     a = t.fwd
     B, H, O, K = a.B, a.H, a.out_ch, a.k * a.C
@@ -200,9 +217,23 @@ def backward_per_launch(t, dev, grads=()) -> None:
         colsum(dpre, H, H, t.d_b1)
     if t.d_x:
         nt(dpre, H, w1t, H, dxs, K, K, H)
+        lu, et, last = a.last_update if a.decay else None, a.edge_time if a.decay else None, None if a.dup_all else a.last
+        if a.k == 8:  # tgmx_ncn8_dx: the pair term, then every slab's coefficient rows and their product onto dx
+            N, C = a.N, a.C
+            nbytes = int(lib.tgmx_ncn8_dx_pairs_workspace_bytes(N, B))
+            _native.check(lib.tgmx_ncn8_dx_pairs(a.x, N, C, a.tar, a.tar_is64, a.tar_stride, B, dxs, K, t.d_x, buf(nbytes, torch.uint8), nbytes, st),
+                          'tgmx_ncn8_dx_pairs')  # fmt: skip
+            P, ldT = int(lib.tgmx_ncn8_backward_slab_pairs(N, B, slab_pairs)), _up64(N)
+            T, rows_bytes = buf(8 * P * ldT), int(lib.tgmx_ncn8_workspace_bytes(N, P))
+            rows, part = buf(rows_bytes, torch.uint8), buf(lib.tgmx_sgemm_tn_workspace_bytes(8 * P, N, C, 1) // 4)
+            for first in range(0, B, P):
+                p = min(P, B - first)
+                _native.check(lib.tgmx_ncn8_coef(N, a.indptr, a.cols, a.tar, a.tar_is64, a.tar_stride, B, lu, et, last, first, p, T, ldT, rows, rows_bytes,
+                                                 0, st), 'tgmx_ncn8_coef')  # fmt: skip
+                _native.check(lib.tgmx_sgemm_tn(T, ldT, dxs + 4 * K * first, C, t.d_x, C, 8 * p, N, C, 1, 0, 0, 0, 1, part, st), 'tgmx_sgemm_tn')
+            return
         nbytes = int(lib.tgmx_ncn_dx_workspace_bytes(a.N, a.E, B, a.C))
-        _native.check(lib.tgmx_ncn_dx(a.x, a.N, a.C, a.k, a.indptr, a.cols, a.E, a.tar, a.tar_is64, a.tar_stride, B, a.last_update if a.decay else None,
-                                      a.edge_time if a.decay else None, None if a.dup_all else a.last, dxs, K, t.d_x, buf(nbytes, torch.uint8), nbytes,
+        _native.check(lib.tgmx_ncn_dx(a.x, a.N, a.C, a.k, a.indptr, a.cols, a.E, a.tar, a.tar_is64, a.tar_stride, B, lu, et, last, dxs, K, t.d_x, buf(nbytes, torch.uint8), nbytes,
                                       st), 'tgmx_ncn_dx')  # fmt: skip
 
 

@@ -36,7 +36,7 @@ Inference (no gradient needed) is ONE native call, ``tgmx_ncn_forward``: a radix
 per pair intersects two sorted rows and gather-sums ``x`` over the matches in ascending id (deterministic, no float atomics), then the two
 Linear layers on the exact-fp32 GEMM.
 
-Training (autograd has something to track) is native too at k = 2 / 4: ``forward`` is the same ``tgmx_ncn_forward`` call, writing what the backward
+Training (autograd has something to track) is native too: ``forward`` is the same ``tgmx_ncn_forward`` call, writing what the backward
 reads into buffers of the call (so the result is the no-grad call's bit for bit, and the positives' and negatives' calls of one step do
 not share them), and the backward is ONE native call, ``tgmx_ncn_backward`` (``_ncn_train.py``, ``csrc/ncn_bwd.hip``): the two Linear layers
 from the shared blocks, then ``dx`` node by node through two inverted indexes of the pairs and the forward's adjacency -- fixed summation
@@ -48,8 +48,13 @@ only) and ``xslin`` gets ``None``.  Outside that path -- autocast, parameters of
 ``k = 8`` (two-hop common neighbours) has its own native stage, ``tgmx_ncn8_forward`` (``csrc/ncn8.hip``): one workgroup per pair expands the
 two targets' neighbours' rows into integer count rows (in LDS up to 7680 local ids, in a workspace above), forms every coefficient as an
 exact integer and gather-sums ``x`` over ascending ids in float64, rounded once -- nothing ``[N, N]``, no ``[B, N]`` float matrix, the same
-bits every run; the two Linear layers, whose 8 C inputs carry those integer weights, run in float64 too (one kernel, rounded once; ``hidden_dim`` up to 8192, a wider layer is an error).  Inference takes it; with gradients k = 8 is the composed torch path (``[B, N]`` rows and ``index_add_`` over the half-edges;
-the coefficients carry no gradient), a native k = 8 backward does not exist yet.  One behaviour of the reference is NOT reproduced at k = 8:
+bits every run; the two Linear layers, whose 8 C inputs carry those integer weights, run in float64 too (one kernel, rounded once; ``hidden_dim``
+up to 8192, a wider layer is an error).  Training at k = 8 is the same call, and its backward is ONE native call as well,
+``tgmx_ncn8_backward`` (``csrc/ncn8_bwd.hip``): the two Linear layers exactly as at k = 2 / 4, then ``dx`` = a node-centred pair term plus
+``T^T dxs``, where the coefficient rows ``T`` are rebuilt slab by slab from the forward's count rows (the coefficients carry no gradient)
+and multiplied by the exact-fp32 GEMM -- a fixed order, no float atomics, nothing ``[B, N]`` kept.  Only the composed path (autocast, another
+dtype, ``get_cn_emb`` under gradients, ``TGMX_NCN_BWD=torch``, ``hidden_dim`` > 8192) goes through ``[B, N]`` float rows and ``index_add_``
+over the half-edges.  One behaviour of the reference is NOT reproduced at k = 8:
 it multiplies dense coefficient matrices by ``W``, so a weight that overflows to ``inf`` (``edge_time - last_update`` below about -8.8e5)
 turns the zero counts of that row into NaN; here ``W`` multiplies only non-zero counts, as at k = 2 / 4.  On host tensors k = 8 raises
 ``NotImplementedError`` (device only); k = 2 / 4 raise ``NativeLibraryError`` there.  A pair with a target id outside ``[0, N)`` gives a zero
@@ -137,6 +142,7 @@ class NCNPredictor(TransientCaches, nn.Module):
         self.in_channels, self.hidden_dim, self.out_channels = in_channels, hidden_dim, out_channels
 
     adjacency = staticmethod(adjacency)
+    _slab_pairs = 0  # pairs per coefficient slab of the k = 8 backward; 0: tgmx_ncn8_backward's budget rule (tests force small slabs)
 
     # -- inputs ------------------------------------------------------------------------------------------------------------------------
     def _inputs(self, x: Tensor, edge_index: Union[Tensor, PreparedAdjacency], tar_ei: Tensor, last_update: Optional[Tensor],

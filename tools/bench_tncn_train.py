@@ -1,9 +1,9 @@
 #!/usr/bin/env python
 """The decoder's share of a TNCN training step at the example's shape (examples/linkproppred/tncn.py's train(): a wiki-shaped stream, batch
 size 200, one hop of 10 neighbours, every width 100, time decay on): ``NCNPredictor`` on the positives and on the negatives, BCE with
-logits, and the backward down to ``z.grad`` and the parameters' gradients.  Per step, in microseconds, for k = 2 and k = 4:
+logits, and the backward down to ``z.grad`` and the parameters' gradients.  Per step, in microseconds, for every k of --k (default 2 4):
 
-  native  tgmx_ncn_forward twice (activations kept by each call), tgmx_ncn_backward twice
+  native  tgmx_ncn_forward twice (activations kept by each call), tgmx_ncn_backward twice (k = 8: tgmx_ncn8_forward / tgmx_ncn8_backward)
   torch   TGMX_NCN_BWD=torch: the composed torch path through dense [B, N] rows, what the decoder did before it had a backward
 
 The decoder's inputs -- z, the sampled edge list, the local targets, last_update -- come from the last full batch of the stream, through
@@ -11,8 +11,9 @@ the sampler, TGNMemory and GraphAttentionEmbedding (not timed).  Every step ends
 that whatever a variant caches against the parameters' versions is rebuilt once per step, inside the timing.  A timed window repeats the
 step until it lasts at least --window-s seconds; the variants take turns (one window each, three rounds, after a warm-up window each) and
 each figure is the median of its three windows; the whole schedule runs twice (``runs``).  These are call rates through Python: the
-launches themselves are not traced.  Prints one JSON line; --out appends it.
-    python tools/bench_tncn_train.py [--out profiles/rNN_bench_tncn_train.jsonl]"""
+launches themselves are not traced.  ``peak_mib``: the most device memory one step of each variant holds above what is allocated before it
+(the composed path's [B, N] rows and [B, 2 E] intermediates are part of its cost).  Prints one JSON line; --out appends it.
+    python tools/bench_tncn_train.py [--k 8] [--out profiles/rNN_bench_tncn_train.jsonl]"""
 import argparse
 import json
 import math
@@ -33,6 +34,7 @@ from tgm_amd.synth import make_stream  # noqa: E402
 ap = argparse.ArgumentParser()
 ap.add_argument('--window-s', type=float, default=0.15, help='least duration of a timed window')
 ap.add_argument('--edges', type=int, default=8_000, help='length of the stream; the last full batch is timed')
+ap.add_argument('--k', type=int, nargs='+', default=[2, 4], choices=[2, 4, 8], help='the decoder variants to time')
 ap.add_argument('--out', type=str, default=None, help='append the JSON line to this file')
 args = ap.parse_args()
 dev = torch.device('cuda', 0)
@@ -107,7 +109,7 @@ line = {'bench': 'tncn_train_example_shape', 'device': torch.cuda.get_device_nam
 ones, zeros = torch.ones(B, device=dev), torch.zeros(B, device=dev)
 for run in range(2):
     res = {}
-    for k in (2, 4):
+    for k in args.k:
         torch.manual_seed(k)
         dec = NCNPredictor(DIM, DIM, 1, k=k, cn_time_decay=True).to(dev).train()
         opt = torch.optim.SGD(dec.parameters(), lr=1e-3)
@@ -125,8 +127,14 @@ for run in range(2):
         # the two variants' gradients on the same, freshly drawn parameters (lr = 0: these steps change nothing)
         for group in opt.param_groups:
             group['lr'] = 0.0
-        for fn in fns:
+        for name, fn in zip(('native', 'torch'), fns):
+            torch.cuda.synchronize()
+            torch.cuda.empty_cache()  # (so that the blocks the other variant, or an earlier schedule, left cached do not hide this one's peak)
+            held = torch.cuda.memory_allocated()
+            torch.cuda.reset_peak_memory_stats()
             fn()
+            torch.cuda.synchronize()
+            res[f'k{k}_{name}_peak_mib'] = round((torch.cuda.max_memory_allocated() - held) / 2**20, 1)
         rel = lambda a, b: float(((a - b).abs() / b.abs().clamp(min=1)).max())
         res[f'k{k}_max_rel_diff'] = max(rel(a, t) for a, t in zip(grads['native'], grads['torch']))
         for group in opt.param_groups:
