@@ -58,7 +58,8 @@ int tgmx_version(void);
  * 6 tgmx_pipeline_t, 7 tgmx_pipeline_out_t, 8 tgmx_dropout_t, 9 tgmx_tgn_memory_fwd_t, 10 tgmx_tconv_fwd_t, 11 tgmx_pipeline_post_t,
  * 12 tgmx_tgn_step_t, ..., 22 tgmx_ctan_fwd_t, 24 tgmx_gclstm_fwd_t, 26 tgmx_roland_fwd_t, 27 tgmx_decoder_fwd_t, 35 tgmx_ctan_bwd_t, 36 tgmx_graphmixer_bwd_t, 37 tgmx_dygformer_bwd_t, 38 tgmx_tpnet_bwd_t (23 and 25 are reserved and answer 0: tests/test_ctan_cpu.py and
  * tests/test_gclstm_cpu.py pin them), 28 tgmx_an_batch_t, 29 tgmx_node_analytics_t, 30 tgmx_decoder_train_t, 32 tgmx_gclstm_bwd_t (31 is
- * reserved the same way: tests/test_decoder_train_cpu.py), 39 tgmx_gcn_conv_bwd_t, 40 tgmx_tgcn_csr_fwd_t, 41 tgmx_tgcn_csr_bwd_t */
+ * reserved the same way: tests/test_decoder_train_cpu.py), 39 tgmx_gcn_conv_bwd_t, 40 tgmx_tgcn_csr_fwd_t, 41 tgmx_tgcn_csr_bwd_t,
+ * 43 tgmx_tconv_bwd_t (42 is reserved the same way: tests/test_gcn_sparse_cpu.py) */
 size_t tgmx_abi_sizeof(int32_t which);
 const char* tgmx_last_error(void);
 
@@ -984,6 +985,52 @@ int tgmx_tconv_attend_backward(const float* q, const float* k, const float* v, c
                                const int64_t* src, const int64_t* seg_lo, const int64_t* seg_hi, int64_t U, int32_t H,
                                int32_t C, float scale, const float* dout, float* dq, float* dk, float* dv, float* de,
                                const tgmx_dropout_t* drop /* the forward's, NULL = off */, tgmx_stream_t stream);
+
+/* ---- TransformerConv training, wide heads (csrc/tconv_bwd.hip): a deterministic attention backward and the layer's backward as one call.
+ * The envelope is C <= 256, H <= 8, H C <= 512 (any C inside it): tgmx_tconv_train_supported answers 1 inside, 0 outside, and the entry
+ * points below return TGMX_E_UNSUPPORTED outside. ---- */
+int tgmx_tconv_train_supported(int32_t H, int32_t C);
+
+/* tgmx_tconv_attend_backward without float atomics: the same tensors (dq, dk, dv [U, H*C], de [E, H*C], every element written exactly once:
+ * no zero-initialisation) plus a workspace.  `order` must hold every target's segment in ascending edge id (tgmx_segment_sort on the
+ * targets).  Three steps: the target pass (one workgroup of four waves per target, all heads in one walk: softmax state, then per edge
+ * alpha, ds, ad = alpha mk, the de row, dq in registers, (ds, ad)[e, h] and the edge's target into the workspace), the edges grouped by
+ * source (tgmx_segment_sort on src), the source pass (dk[j] = sum ds q[target], dv[j] = sum ad dout[target] in ascending edge id, sources
+ * with more than 16 edges over four waves merged in wave order).  Two calls give the same bits. */
+size_t tgmx_tconv_attend_backward_det_workspace_bytes(int64_t U, int64_t E, int32_t H);
+int tgmx_tconv_attend_backward_det(const float* q, const float* k, const float* v, const float* eproj, const int64_t* order,
+                                   const int64_t* src, const int64_t* seg_lo, const int64_t* seg_hi, int64_t U, int64_t E, int32_t H,
+                                   int32_t C, float scale, const float* dout, float* dq, float* dk, float* dv, float* de,
+                                   const tgmx_dropout_t* drop /* the forward's, NULL = off */, void* workspace, size_t workspace_bytes,
+                                   tgmx_stream_t stream);
+
+/* tgmx_tconv_forward for training: the same launches with the forward's dropout on the attention coefficients (NULL or p = 0: off, and
+ * the result has tgmx_tconv_forward's bits).  edge_attr, qkvs, eproj land in the caller's buffers; the autograd node keeps them. */
+int tgmx_tconv_forward_train(const tgmx_tconv_fwd_t* args, const tgmx_dropout_t* drop, tgmx_stream_t stream);
+
+/* The backward of tgmx_tconv_forward_train as ONE call (tgmx_abi_sizeof(43)).  x, qkvs (its q | k | v blocks), eproj, edge_attr: what the
+ * forward read and wrote.  With g = dL/dout [U, H*C]:
+ *   the edges grouped by tgt and by src (two tgmx_segment_sort; the forward's counting grouping leaves its segments in no fixed order) ->
+ *   the deterministic attention backward -> d4 [U, 4 H*C] = dq | dk | dv | g, de [E, H*C];
+ *   d_Wedge = de^T edge_attr (tgmx_sgemm_tn);  d_time = [d tw | d tb] = colsum(tgmx_tconv_edge_attr_backward(de WeT^T));
+ *   d_W4[b] = d4_b^T x (one batched tgmx_sgemm_tn), d_b4 = colsum(d4), d_x = d4 W4T^T (one tgmx_sgemm_nt, K = 4 H*C).
+ * W4T [in_ch, 4 H*C] = W4 viewed as [4 H*C, in_ch], transposed (only for d_x);  WeT [T, H*C] = W_edge[:, :T]^T (only for d_time).  A NULL
+ * output is not wanted and its work is skipped.  E = 0: d_Wedge / d_time are zeroed, d4 = 0 | 0 | 0 | g.  U = 0 returns at once. */
+typedef struct tgmx_tconv_bwd {
+  int64_t U, E; int32_t in_ch, H, C, D, T, reserved0;
+  const float* g; int64_t ldg;                          /* dL/dout [U, H*C] */
+  const float* x; const float* qkvs;                    /* [U, in_ch], [4, U, H*C] */
+  const float* eproj; const float* edge_attr;           /* [E, H*C], [E, T + D] */
+  const int64_t* src; const int64_t* tgt; const int64_t* t; const int64_t* last_update_local;
+  const float* tw; const float* tb;                     /* [T], [T] (d_time) */
+  const float* W4T; const float* WeT;                   /* [in_ch, 4 H*C], [T, H*C] */
+  tgmx_dropout_t drop;                                  /* the forward's; p = 0: off */
+  float* d_W4; float* d_b4; float* d_x;                 /* [4, H*C, in_ch], [4, H*C], [U, in_ch] */
+  float* d_Wedge; float* d_time;                        /* [H*C, T + D], [2T] */
+  void* workspace; size_t workspace_bytes;
+} tgmx_tconv_bwd_t;
+size_t tgmx_tconv_backward_workspace_bytes(const tgmx_tconv_bwd_t* args);
+int tgmx_tconv_backward(const tgmx_tconv_bwd_t* args, tgmx_stream_t stream);
 
 /* ---- GraphMixer (the reference's examples/linkproppred/graphmixer.py: MLPMixer link encoder + time-gap node encoder), inference ---- */
 

@@ -438,6 +438,28 @@ SIGNATURES['tgmx_discretize_workspace_bytes'] = (c_size_t, [c_int64])
 SIGNATURES['tgmx_discretize_keep'] = (c_int32, [_P, _P, _P, c_int64, ctypes.c_double, _P, _P, _P, _P, c_size_t, _P])
 SIGNATURES['tgmx_tgn_memory_forward'] = (c_int32, [ctypes.POINTER(TgnMemoryFwd), _P])
 SIGNATURES['tgmx_tconv_forward'] = (c_int32, [ctypes.POINTER(TconvFwd), _P])
+
+
+class TconvBwd(ctypes.Structure):
+    """tgmx_tconv_bwd_t (include/tgm_amd.h)."""
+
+    _fields_ = [
+        ('U', c_int64), ('E', c_int64), ('in_ch', c_int32), ('H', c_int32), ('C', c_int32), ('D', c_int32), ('T', c_int32), ('reserved0', c_int32),
+        ('g', c_void_p), ('ldg', c_int64), ('x', c_void_p), ('qkvs', c_void_p), ('eproj', c_void_p), ('edge_attr', c_void_p),
+        ('src', c_void_p), ('tgt', c_void_p), ('t', c_void_p), ('last_update_local', c_void_p), ('tw', c_void_p), ('tb', c_void_p),
+        ('W4T', c_void_p), ('WeT', c_void_p), ('drop', Dropout),
+        ('d_W4', c_void_p), ('d_b4', c_void_p), ('d_x', c_void_p), ('d_Wedge', c_void_p), ('d_time', c_void_p),
+        ('workspace', c_void_p), ('workspace_bytes', c_size_t),
+    ]  # fmt: skip
+
+
+SIGNATURES['tgmx_tconv_train_supported'] = (c_int32, [c_int32, c_int32])
+SIGNATURES['tgmx_tconv_attend_backward_det_workspace_bytes'] = (c_size_t, [c_int64, c_int64, c_int32])
+SIGNATURES['tgmx_tconv_attend_backward_det'] = (c_int32, [_P, _P, _P, _P, _P, _P, _P, _P, c_int64, c_int64, c_int32, c_int32, ctypes.c_float, _P, _P, _P, _P, _P,
+                                                          _P, _P, c_size_t, _P])  # fmt: skip
+SIGNATURES['tgmx_tconv_forward_train'] = (c_int32, [ctypes.POINTER(TconvFwd), _P, _P])
+SIGNATURES['tgmx_tconv_backward_workspace_bytes'] = (c_size_t, [ctypes.POINTER(TconvBwd)])
+SIGNATURES['tgmx_tconv_backward'] = (c_int32, [ctypes.POINTER(TconvBwd), _P])
 SIGNATURES['tgmx_tgn_step'] = (c_int32, [ctypes.POINTER(TgnStep), _P])
 SIGNATURES['tgmx_segment_sort_workspace_bytes'] = (c_size_t, [c_int64])
 SIGNATURES['tgmx_segment_sort'] = (c_int32, [_P, c_int64, c_int32, _P, _P, _P, _P, c_size_t, _P, _P])

@@ -1402,7 +1402,8 @@ static bool launch_edge_grouping(const tgmx_tconv_fwd_t* a, hipStream_t st, cons
   return fused;
 }
 
-extern "C" int tgmx_tconv_forward(const tgmx_tconv_fwd_t* a, tgmx_stream_t stream) {
+// drop: the training form's dropout on the attention coefficients (tgmx_tconv_forward_train); NULL = off
+static int tconv_forward_impl(const tgmx_tconv_fwd_t* a, const tgmx_dropout_t* drop, tgmx_stream_t stream) {
   TGMX_REQUIRE(a, "tconv_forward: null argument block");
   const int64_t U = a->U, E = a->E;
   if (U == 0) return TGMX_OK;
@@ -1432,7 +1433,7 @@ extern "C" int tgmx_tconv_forward(const tgmx_tconv_fwd_t* a, tgmx_stream_t strea
     if ((rc = tgmx_internal_sgemm_nt_pair(proj, eproj, stream))) return rc;
     TconvArgs t{a->qkvs, a->qkvs + U * HC, a->qkvs + 2 * U * HC, a->eproj, a->order, a->src, a->seg_lo, a->seg_hi, out, U, a->H, a->C,
                 1.0f / sqrtf((float)a->C)};
-    t.drop = make_dropout(nullptr);
+    t.drop = make_dropout(drop);
     t.unsorted = 1;
     t.order_big = a->order_big;
     t.short_ok = tconv_short_ok(t);
@@ -1447,7 +1448,13 @@ extern "C" int tgmx_tconv_forward(const tgmx_tconv_fwd_t* a, tgmx_stream_t strea
   if ((rc = tgmx_sgemm_nt(a->edge_attr, Wd, a->W_edge, Wd, a->eproj, HC, E, HC, Wd, nullptr, 0, 1, 0, 0, 0, stream))) return rc;
   if ((rc = tgmx_segment_sort(a->tgt, E, (int32_t)U, a->order, a->seg_lo, a->seg_hi, a->sort_ws, a->sort_ws_bytes, a->status, stream))) return rc;
   return tgmx_tconv_attend(a->qkvs, a->qkvs + U * HC, a->qkvs + 2 * U * HC, a->eproj, a->order, a->src, a->seg_lo, a->seg_hi, U, a->H, a->C,
-                           1.0f / sqrtf((float)a->C), out, nullptr, stream);
+                           1.0f / sqrtf((float)a->C), out, drop, stream);
+}
+
+extern "C" int tgmx_tconv_forward(const tgmx_tconv_fwd_t* a, tgmx_stream_t stream) { return tconv_forward_impl(a, nullptr, stream); }
+
+extern "C" int tgmx_tconv_forward_train(const tgmx_tconv_fwd_t* a, const tgmx_dropout_t* drop, tgmx_stream_t stream) {
+  return tconv_forward_impl(a, drop, stream);
 }
 
 // the model side of one TGN batch: memory forward -> embedding -> update_state (commit of the rows just computed + the batch's store)

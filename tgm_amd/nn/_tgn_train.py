@@ -7,6 +7,7 @@ projections (and flow back through ``x``, the memory module's output).
 """
 from __future__ import annotations
 
+import os
 from typing import Optional
 
 import torch
@@ -14,6 +15,17 @@ from torch import Tensor
 
 from .. import _native
 from . import _ops
+
+
+def native_backward_selected() -> bool:
+    """``TGMX_TGN_BWD=native``: the one-call layer backward / the deterministic attention kernels for heads of up to 64 channels too
+    (wider heads always take them).  Read per call: the tests switch it."""
+    return os.environ.get('TGMX_TGN_BWD', '') == 'native'
+
+
+def train_supported(H: int, C: int) -> bool:
+    """The envelope of csrc/tconv_bwd.hip, asked of the library itself: C <= 256, H <= 8, H C <= 512."""
+    return bool(_native.load().tgmx_tconv_train_supported(H, C))
 
 
 def _colsum(X: Tensor, R: int, C: int) -> Tensor:
@@ -192,10 +204,106 @@ class TconvAttendFn(torch.autograd.Function):
         lib = _native.load()
         dout = dout.contiguous()
         dq = torch.empty_like(q)
-        dk, dv = torch.zeros_like(k), torch.zeros_like(v)
         de = torch.empty_like(eproj)
+        if ctx.C > 64 or native_backward_selected():
+            # the deterministic kernels (csrc/tconv_bwd.hip): every element written once, no zero-initialisation
+            U, E = q.shape[0], eproj.shape[0]
+            dk, dv = torch.empty_like(k), torch.empty_like(v)
+            ws = torch.empty(max(int(lib.tgmx_tconv_attend_backward_det_workspace_bytes(U, E, ctx.H)), 4), dtype=torch.uint8, device=q.device)
+            _native.check(lib.tgmx_tconv_attend_backward_det(q.data_ptr(), k.data_ptr(), v.data_ptr(), eproj.data_ptr(), order.data_ptr(), src.data_ptr(),
+                                                             seg_lo.data_ptr(), seg_hi.data_ptr(), U, E, ctx.H, ctx.C, float(ctx.C) ** -0.5,
+                                                             dout.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), de.data_ptr(),
+                                                             _native.dropout_desc(*ctx.drop), ws.data_ptr(), ws.numel(), _native.stream_ptr()),
+                          'tgmx_tconv_attend_backward_det')  # fmt: skip
+            return dq, dk, dv, de, dout, None, None, None, None, None, None, None
+        dk, dv = torch.zeros_like(k), torch.zeros_like(v)
         _native.check(lib.tgmx_tconv_attend_backward(q.data_ptr(), k.data_ptr(), v.data_ptr(), eproj.data_ptr(), order.data_ptr(), src.data_ptr(),
                                                      seg_lo.data_ptr(), seg_hi.data_ptr(), q.shape[0], ctx.H, ctx.C, float(ctx.C) ** -0.5,
                                                      dout.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), de.data_ptr(),
                                                      _native.dropout_desc(*ctx.drop), _native.stream_ptr()), 'tgmx_tconv_attend_backward')  # fmt: skip
         return dq, dk, dv, de, dout, None, None, None, None, None, None, None
+
+
+class TconvLayerFn(torch.autograd.Function):
+    """GraphAttentionEmbedding's layer as ONE node: z = TransformerConv(x, [Time2Vec(last_update[src] - t) | msg]).  The forward is the
+    inference call with the dropout descriptor passed through (``tgmx_tconv_forward_train``), the backward one native call
+    (``tgmx_tconv_backward``).  Everything the backward reads is kept here at forward time: the reference's training loop calls
+    ``memory.update_state`` before ``loss.backward()``."""
+
+    @staticmethod
+    def forward(ctx, x, tw, tb, wq, bq, wk, bk, wv, bv, we, ws_, bs, conv, lu: Tensor, edge_index: Tensor, t: Tensor, msg: Tensor, drop: tuple):
+        lib = _native.load()
+        dev, U, H, C = x.device, x.shape[0], conv.heads, conv.out_channels
+        HC, E, T, D = H * C, edge_index.shape[1], tb.numel(), msg.shape[1]
+        f32 = dict(dtype=torch.float32, device=dev)
+        x = _ops._f32c(x.detach(), 'x')
+        W4, b4 = conv._stacked_projections()
+        we = we.detach().contiguous()
+        twc, tbc = tw.detach().reshape(-1).contiguous(), tb.detach().contiguous()
+        src, tgt = edge_index[0].contiguous(), edge_index[1].contiguous()
+        qkvs = torch.empty((4, U, HC), **f32)
+        fl = torch.empty(E * (T + D + HC), **f32)  # edge_attr [E, T + D] | eproj [E, HC]
+        Ep, Up = E + (E & 1), U + (U & 1)
+        ints = torch.empty(2 * Ep + 3 * Up, dtype=torch.int64, device=dev)  # order | seg_lo | seg_hi | cursor | order_big
+        need = int(lib.tgmx_segment_sort_workspace_bytes(E))
+        wsd = getattr(conv, '_seg_ws', None)
+        if wsd is None or wsd[0].device != dev or wsd[0].numel() < need:
+            wsd = conv._seg_ws = (torch.empty(need, dtype=torch.uint8, device=dev), torch.zeros(1, dtype=torch.int32, device=dev))
+        cnt = getattr(conv, '_tgt_count', None)
+        if cnt is None or cnt.device != dev or cnt.numel() < U:
+            cnt = conv._tgt_count = torch.zeros(max(2 * U, 1 << 14), dtype=torch.int32, device=dev)
+        a = _native.TconvFwd()
+        a.x, a.U, a.in_ch, a.last_update_local = x.data_ptr(), U, x.shape[1], lu.data_ptr()
+        a.src, a.tgt, a.t, a.msg, a.E, a.D, a.T = src.data_ptr(), tgt.data_ptr(), t.data_ptr(), msg.data_ptr(), E, D, T
+        a.tw, a.tb, a.W4, a.b4, a.W_edge, a.H, a.C = twc.data_ptr(), tbc.data_ptr(), W4.data_ptr(), b4.data_ptr(), we.data_ptr(), H, C
+        a.edge_attr, a.qkvs, a.eproj = fl.data_ptr(), qkvs.data_ptr(), fl.data_ptr() + 4 * E * (T + D)
+        a.order, a.seg_lo, a.seg_hi = ints.data_ptr(), ints.data_ptr() + 8 * Ep, ints.data_ptr() + 8 * (Ep + Up)
+        a.sort_ws, a.sort_ws_bytes, a.status = wsd[0].data_ptr(), wsd[0].numel(), wsd[1].data_ptr()
+        a.tgt_count, a.cursor, a.order_big = cnt.data_ptr(), ints.data_ptr() + 8 * (Ep + 2 * Up), ints.data_ptr() + 8 * (Ep + 3 * Up)
+        _native.check(lib.tgmx_tconv_forward_train(a, _native.dropout_desc(*drop), _native.stream_ptr()), 'tgmx_tconv_forward_train')
+        ctx.kept = (x, qkvs, fl, src, tgt, t, lu, twc, tbc, W4, we)
+        ctx.dims = (U, E, H, C, T, D, tw.shape, drop)
+        return qkvs[3]
+
+    @staticmethod
+    def backward(ctx, g: Tensor):
+        x, qkvs, fl, src, tgt, t, lu, twc, tbc, W4, we = ctx.kept
+        U, E, H, C, T, D, tw_shape, drop = ctx.dims
+        lib = _native.load()
+        HC, in_ch, dev = H * C, x.shape[1], x.device
+        f32 = dict(dtype=torch.float32, device=dev)
+        need = ctx.needs_input_grad
+        g = g.contiguous()
+        a = _native.TconvBwd()
+        a.U, a.E, a.in_ch, a.H, a.C, a.D, a.T = U, E, in_ch, H, C, D, T
+        a.g, a.ldg, a.x, a.qkvs = g.data_ptr(), HC, x.data_ptr(), qkvs.data_ptr()
+        a.edge_attr, a.eproj = fl.data_ptr(), fl.data_ptr() + 4 * E * (T + D)
+        a.src, a.tgt, a.t, a.last_update_local, a.tw, a.tb = src.data_ptr(), tgt.data_ptr(), t.data_ptr(), lu.data_ptr(), twc.data_ptr(), tbc.data_ptr()
+        if drop[0]:
+            a.drop = _native.Dropout(float(drop[0]), drop[1] & 0xFFFFFFFFFFFFFFFF, drop[2] & 0xFFFFFFFFFFFFFFFF, 0)
+        d_x = d_W4 = d_b4 = d_We = d_time = W4T = WeT = None
+        if need[0]:
+            d_x = torch.empty((U, in_ch), **f32)
+            W4T = W4.reshape(4 * HC, in_ch).t().contiguous()
+            a.d_x, a.W4T = d_x.data_ptr(), W4T.data_ptr()
+        if any(need[i] for i in (3, 5, 7, 10)):
+            d_W4 = torch.empty((4, HC, in_ch), **f32)
+            a.d_W4 = d_W4.data_ptr()
+        if any(need[i] for i in (4, 6, 8, 11)):
+            d_b4 = torch.empty((4, HC), **f32)
+            a.d_b4 = d_b4.data_ptr()
+        if need[9]:
+            d_We = torch.empty((HC, T + D), **f32)
+            a.d_Wedge = d_We.data_ptr()
+        if need[1] or need[2]:
+            d_time = torch.empty(2 * T, **f32)
+            WeT = we[:, :T].t().contiguous()
+            a.d_time, a.WeT = d_time.data_ptr(), WeT.data_ptr()
+        ws = torch.empty(max(int(lib.tgmx_tconv_backward_workspace_bytes(a)), 4), dtype=torch.uint8, device=dev)
+        a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
+        _native.check(lib.tgmx_tconv_backward(a, _native.stream_ptr()), 'tgmx_tconv_backward')
+        pick = lambda want, buf, i: buf[i] if (want and buf is not None) else None
+        return (d_x, d_time[:T].reshape(tw_shape) if need[1] else None, d_time[T:] if need[2] else None,
+                pick(need[3], d_W4, 0), pick(need[4], d_b4, 0), pick(need[5], d_W4, 1), pick(need[6], d_b4, 1),
+                pick(need[7], d_W4, 2), pick(need[8], d_b4, 2), d_We, pick(need[10], d_W4, 3), pick(need[11], d_b4, 3),
+                None, None, None, None, None, None)

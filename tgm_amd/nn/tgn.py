@@ -615,10 +615,12 @@ class TransformerConv(TransientCaches, nn.Module):
 
 def _tconv_forward_train(self, x: Tensor, edge_index: Tensor, edge_attr: Tensor) -> Tensor:
     """TransformerConv forward with autograd (hand-written backward kernels, nn/_tgn_train.py)."""
-    from ._tgn_train import LinearFn, TconvAttendFn
+    from ._tgn_train import LinearFn, TconvAttendFn, train_supported
 
-    if self.out_channels > 64:
-        raise NotImplementedError('tgm_amd TransformerConv backward supports out_channels <= 64')
+    if self.out_channels > 64 and not train_supported(self.heads, self.out_channels):
+        raise NotImplementedError('tgm_amd TransformerConv backward supports out_channels <= 64, and wider heads inside the envelope '
+                                  f'out_channels <= 256, heads <= 8, heads * out_channels <= 512 (got heads = {self.heads}, '
+                                  f'out_channels = {self.out_channels})')
     x = x.float().contiguous() if (x.dtype != torch.float32 or not x.is_contiguous()) else x
     dev, U, H, C = x.device, x.shape[0], self.heads, self.out_channels
     q = LinearFn.apply(x, self.lin_query.weight, self.lin_query.bias)
@@ -653,8 +655,17 @@ class GraphAttentionEmbedding(nn.Module):
         D = msg.shape[1]
         edge_index = edge_index.to(torch.int64)
         if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in param_list(self))):
-            from ._tgn_train import EdgeAttrFn
+            from ._tgn_train import EdgeAttrFn, TconvLayerFn, native_backward_selected, train_supported
 
+            conv = self.conv
+            wide = conv.out_channels > 64
+            if E and not msg.requires_grad and (wide or native_backward_selected()) and train_supported(conv.heads, conv.out_channels):
+                # the layer as one autograd node: the saving forward, loss.backward() as one native call (csrc/tconv_bwd.hip)
+                conv._edge_ctx = None
+                return TconvLayerFn.apply(x, self.time_enc.w.weight, self.time_enc.w.bias, conv.lin_query.weight, conv.lin_query.bias,
+                                          conv.lin_key.weight, conv.lin_key.bias, conv.lin_value.weight, conv.lin_value.bias, conv.lin_edge.weight,
+                                          conv.lin_skip.weight, conv.lin_skip.bias, conv, last_update.to(torch.int64).contiguous(), edge_index,
+                                          t.to(torch.int64).contiguous(), msg, conv._dropout_site())  # fmt: skip
             edge_attr = EdgeAttrFn.apply(self.time_enc.w.weight, self.time_enc.w.bias, last_update.to(torch.int64).contiguous(),
                                          edge_index[0].contiguous(), t.to(torch.int64).contiguous(), msg)  # fmt: skip
             return self.conv(x, edge_index, edge_attr)
