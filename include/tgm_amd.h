@@ -1347,6 +1347,42 @@ typedef struct tgmx_dygformer_bwd {
 size_t tgmx_dygformer_backward_workspace_bytes(const tgmx_dygformer_bwd_t* args);
 int tgmx_dygformer_backward(const tgmx_dygformer_bwd_t* args, tgmx_stream_t stream);
 
+/* ---- attention past 128 tokens (csrc/mha_stream.hip): K and V streamed through LDS, nothing T x T resident or written ---- */
+
+/* 1 for 128 < T <= 4096 and 1 <= dh <= 128: the one function the host and the entry points below choose the attention launch by. */
+int tgmx_mha_stream_supported(int32_t T, int32_t dh);
+
+/* The function of tgmx_mha_small_train on long sequences: running maximum and sum per query row, one workgroup per (b, h, 64 query rows).
+ * lse [B, H, T] receives m + log l per query row (NULL: not stored -- inference).  drop: as tgmx_mha_small_train's, element
+ * ((b H + h) T + i) T + j, applied to the normalised probabilities (NULL or p = 0: off).  Outside tgmx_mha_stream_supported:
+ * TGMX_E_UNSUPPORTED, nothing written.  tgmx_mha_stream: the same with lse = drop = NULL. */
+int tgmx_mha_stream_train(const float* qkv, int64_t ldq, int64_t B, int32_t T, int32_t H, int32_t dh, float* out, int64_t ldo, float* lse,
+                          const tgmx_dropout_t* drop, tgmx_stream_t stream);
+int tgmx_mha_stream(const float* qkv, int64_t ldq, int64_t B, int32_t T, int32_t H, int32_t dh, float* out, int64_t ldo, tgmx_stream_t stream);
+
+/* Its backward: att the forward's output, datt the gradient at it, lse what the forward stored, delta [B, H, T] scratch -> dqkv laid out
+ * as tgmx_mha_small_backward's (columns [3 H dh, ldq) untouched).  Three launches: delta = rowsum(datt o att); a key-centred pass (dK, dV)
+ * and a query-centred pass (dQ), each recomputing P = exp(scale S - lse) block by block and regenerating the mask.  No float atomics,
+ * every element written once, equal bits run to run. */
+int tgmx_mha_stream_backward(const float* qkv, int64_t ldq, const float* att, const float* datt, int64_t ldo, const float* lse, int64_t B,
+                             int32_t T, int32_t H, int32_t dh, float* dqkv, float* delta, const tgmx_dropout_t* drop, tgmx_stream_t stream);
+
+/* tgmx_dygformer_layer_train / _forward_train / _layer_backward / _backward with the buffer the long route keeps: lse [B, H, T] per layer
+ * (the whole model: [num_layers, P, heads, T]).  The entry points without it forward here with NULL.  T <= 128: lse is not touched and the
+ * launches, and the bits, are those of the short route; 128 < T inside tgmx_mha_stream_supported: the streaming kernels (a forward with
+ * lse = NULL is inference-only; the saving forms and the backwards then return TGMX_E_UNSUPPORTED). */
+int tgmx_dygformer_layer_train_lse(const tgmx_dygformer_layer_t* layer, int64_t B, int32_t T, int32_t H, int32_t D, float eps, const float* x_in,
+                                   float* x_out, float* y, float* x1, float* att, int64_t ldx, float* qkv, int64_t ldq, float* h, int64_t ldh,
+                                   float* lse, const tgmx_dropout_t* drop, tgmx_stream_t stream);
+int tgmx_dygformer_forward_train_lse(const tgmx_dygformer_fwd_t* args, const tgmx_dygformer_save_t* save, float* lse, const tgmx_dropout_t* drop,
+                                     tgmx_stream_t stream);
+int tgmx_dygformer_layer_backward_lse(const tgmx_dygformer_layer_t* layer, const tgmx_dygformer_layer_tr_t* tr,
+                                      const tgmx_dygformer_layer_grad_t* d, int64_t B, int32_t T, int32_t H, int32_t D, float eps, const float* x,
+                                      const float* qkv, const float* att, const float* x1, int64_t ldx, int64_t ldq, int64_t ldh, const float* lse,
+                                      float* g, float* dx, const tgmx_dropout_t* drop, void* workspace, size_t workspace_bytes,
+                                      tgmx_stream_t stream);
+int tgmx_dygformer_backward_lse(const tgmx_dygformer_bwd_t* args, const float* lse, tgmx_stream_t stream);
+
 /* ---- TPNet (the reference's tgm/nn/encoder/tpnet.py): temporal walk matrices as random projections, pair features, inference ---- */
 
 /* The num_layer + 1 tables P[0 .. levels) of RandomProjectionModule, each [num_nodes, dim] float32, row-major, contiguous. */

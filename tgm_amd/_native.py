@@ -535,6 +535,22 @@ SIGNATURES['tgmx_dygformer_layer_backward'] = (
 )  # fmt: skip
 SIGNATURES['tgmx_dygformer_backward_workspace_bytes'] = (c_size_t, [ctypes.POINTER(DyGFormerBwd)])
 SIGNATURES['tgmx_dygformer_backward'] = (c_int32, [ctypes.POINTER(DyGFormerBwd), _P])
+# attention past MHA_SMALL_MAX_TOKENS (csrc/mha_stream.hip) and the entry points that carry its lse buffer
+SIGNATURES['tgmx_mha_stream_supported'] = (c_int32, [c_int32, c_int32])
+SIGNATURES['tgmx_mha_stream_train'] = (c_int32, [_P, c_int64, c_int64, c_int32, c_int32, c_int32, _P, c_int64, _P, _P, _P])
+SIGNATURES['tgmx_mha_stream'] = (c_int32, [_P, c_int64, c_int64, c_int32, c_int32, c_int32, _P, c_int64, _P])
+SIGNATURES['tgmx_mha_stream_backward'] = (c_int32, [_P, c_int64, _P, _P, c_int64, _P, c_int64, c_int32, c_int32, c_int32, _P, _P, _P, _P])
+SIGNATURES['tgmx_dygformer_layer_train_lse'] = (
+    c_int32,
+    [ctypes.POINTER(DyGFormerLayer), c_int64, c_int32, c_int32, c_int32, ctypes.c_float, _P, _P, _P, _P, _P, c_int64, _P, c_int64, _P, c_int64, _P, _P, _P],
+)
+SIGNATURES['tgmx_dygformer_forward_train_lse'] = (c_int32, [ctypes.POINTER(DyGFormerFwd), ctypes.POINTER(DyGFormerSave), _P, _P, _P])
+SIGNATURES['tgmx_dygformer_layer_backward_lse'] = (
+    c_int32,
+    [ctypes.POINTER(DyGFormerLayer), ctypes.POINTER(DyGFormerLayerTr), ctypes.POINTER(DyGFormerLayerGrad), c_int64, c_int32, c_int32, c_int32,
+     ctypes.c_float, _P, _P, _P, _P, c_int64, c_int64, c_int64, _P, _P, _P, _P, _P, c_size_t, _P],
+)  # fmt: skip
+SIGNATURES['tgmx_dygformer_backward_lse'] = (c_int32, [ctypes.POINTER(DyGFormerBwd), _P, _P])
 
 TPNET_MAX_LEVELS = 8  # TGMX_TPNET_MAX_LEVELS
 TPNET_PAIR_MAX_LEVELS = 4  # tgmx_tpnet_pair_features' envelope (tables per side)

@@ -332,9 +332,11 @@ extern "C" int tgmx_dygformer_tail(const float* x, int64_t ldx, int64_t P, int32
 
 // one transformer layer x_in -> x_out [R, ldx] (x_out may be x_in; y, x1, att [R, ldx], qkv [R, ldq], h [R, ldh] scratch).  drop: the
 // layer's four sites draw from stream + 0 .. 3; with dropout the three row sites are extra launches (tgmx_dropout in place, tgmx_add_cols)
-extern "C" int tgmx_dygformer_layer_train(const tgmx_dygformer_layer_t* ly, int64_t B, int32_t T, int32_t H, int32_t D, float eps,
-                                          const float* x_in, float* x_out, float* y, float* x1, float* att, int64_t ldx, float* qkv,
-                                          int64_t ldq, float* h, int64_t ldh, const tgmx_dropout_t* drop, tgmx_stream_t stream) {
+// T <= 128: tgmx_mha_small (which refuses what is outside its envelope); longer sequences inside tgmx_mha_stream_supported: the streaming
+// kernels of csrc/mha_stream.hip, which also write lse [B, H, T] when the caller keeps it for the backward (NULL: inference)
+extern "C" int tgmx_dygformer_layer_train_lse(const tgmx_dygformer_layer_t* ly, int64_t B, int32_t T, int32_t H, int32_t D, float eps,
+                                              const float* x_in, float* x_out, float* y, float* x1, float* att, int64_t ldx, float* qkv,
+                                              int64_t ldq, float* h, int64_t ldh, float* lse, const tgmx_dropout_t* drop, tgmx_stream_t stream) {
   TGMX_REQUIRE(ly && B >= 0 && T > 0 && H > 0 && D > 0 && D % H == 0 && ldx >= D && ldq >= 3ll * D && ldh >= 4ll * D && ldx % 4 == 0 && ldq % 4 == 0 &&
                    ldh % 4 == 0,
                "dygformer_layer: bad sizes B=%lld T=%d H=%d D=%d (leading dimensions: multiples of 4)", (long long)B, T, H, D);
@@ -346,7 +348,11 @@ extern "C" int tgmx_dygformer_layer_train(const tgmx_dygformer_layer_t* ly, int6
   int rc;
   if ((rc = tgmx_layernorm_rows(x_in, ldx, R, D, ly->ln0_g, ly->ln0_b, eps, y, ldx, stream))) return rc;
   if ((rc = tgmx_sgemm_nt_ep(y, ldx, ly->in_w, D, qkv, ldq, R, 3 * D, D, ly->in_b, 0, nullptr, 0, stream))) return rc;
-  if ((rc = tgmx_mha_small_train(qkv, ldq, B, T, H, D / H, att, ldx, &site[0], stream))) return rc;
+  if (T > kMhaMaxT && tgmx_mha_stream_supported(T, D / H)) {
+    if ((rc = tgmx_mha_stream_train(qkv, ldq, B, T, H, D / H, att, ldx, lse, &site[0], stream))) return rc;
+  } else if ((rc = tgmx_mha_small_train(qkv, ldq, B, T, H, D / H, att, ldx, &site[0], stream))) {
+    return rc;
+  }
   if (!dropping) {
     if ((rc = tgmx_sgemm_nt_ep(att, ldx, ly->out_w, D, x1, ldx, R, D, D, ly->out_b, 0, x_in, ldx, stream))) return rc;
   } else {
@@ -363,6 +369,12 @@ extern "C" int tgmx_dygformer_layer_train(const tgmx_dygformer_layer_t* ly, int6
   return tgmx_add_cols(x_out, ldx, x1, ldx, R, D, 1, stream);
 }
 
+extern "C" int tgmx_dygformer_layer_train(const tgmx_dygformer_layer_t* ly, int64_t B, int32_t T, int32_t H, int32_t D, float eps,
+                                          const float* x_in, float* x_out, float* y, float* x1, float* att, int64_t ldx, float* qkv,
+                                          int64_t ldq, float* h, int64_t ldh, const tgmx_dropout_t* drop, tgmx_stream_t stream) {
+  return tgmx_dygformer_layer_train_lse(ly, B, T, H, D, eps, x_in, x_out, y, x1, att, ldx, qkv, ldq, h, ldh, nullptr, drop, stream);
+}
+
 // one transformer layer on x [R, ldx] (in place; y, x1, att [R, ldx], qkv [R, ldq], h [R, ldh] scratch)
 extern "C" int tgmx_dygformer_layer(const tgmx_dygformer_layer_t* ly, int64_t B, int32_t T, int32_t H, int32_t D, float eps, float* x, float* y,
                                     float* x1, float* att, int64_t ldx, float* qkv, int64_t ldq, float* h, int64_t ldh, tgmx_stream_t stream) {
@@ -371,7 +383,8 @@ extern "C" int tgmx_dygformer_layer(const tgmx_dygformer_layer_t* ly, int64_t B,
 
 // save == NULL: inference (every layer in place on a->x, scratch reused).  Otherwise the saving form: counts written, layer l reads its
 // input from save->x + l R ldx and writes save->x + (l + 1) R ldx; qkv, att and x1 of layer l stay in save->{qkv, att, x1} + l R ld.
-static int dyg_forward(const tgmx_dygformer_fwd_t* a, const tgmx_dygformer_save_t* save, const tgmx_dropout_t* drop, tgmx_stream_t stream) {
+// lse (saving form past 128 tokens): [num_layers, P, heads, T], layer l's at l P heads T.
+static int dyg_forward(const tgmx_dygformer_fwd_t* a, const tgmx_dygformer_save_t* save, float* lse, const tgmx_dropout_t* drop, tgmx_stream_t stream) {
   TGMX_REQUIRE(a && a->num_layers >= 0 && a->num_layers <= TGMX_DYGFORMER_MAX_LAYERS, "dygformer_forward: bad argument block");
   TGMX_REQUIRE(a->patch > 0 && a->k >= 0 && (a->k + 1) % a->patch == 0 && a->C > 0 && a->heads > 0 && (4 * a->C) % a->heads == 0,
                "dygformer_forward: bad shape k=%d patch=%d C=%d heads=%d", a->k, a->patch, a->C, a->heads);
@@ -409,23 +422,31 @@ static int dyg_forward(const tgmx_dygformer_fwd_t* a, const tgmx_dygformer_save_
     const long long ox = (long long)l * R * a->ldx, oq = (long long)l * R * a->ldq;
     tgmx_dropout_t d{0.f, 0, 0, 0};
     if (dropping) d = tgmx_dropout_t{drop->p, drop->seed, drop->stream + 4ull * l, 0};
-    if ((rc = tgmx_dygformer_layer_train(&a->layers[l], P, 2 * Np, a->heads, D, a->eps, save->x + ox, save->x + ox + R * a->ldx, a->y, save->x1 + ox,
-                                         save->att + ox, a->ldx, save->qkv + oq, a->ldq, a->h, a->ldh, &d, stream)))
+    if ((rc = tgmx_dygformer_layer_train_lse(&a->layers[l], P, 2 * Np, a->heads, D, a->eps, save->x + ox, save->x + ox + R * a->ldx, a->y, save->x1 + ox,
+                                             save->att + ox, a->ldx, save->qkv + oq, a->ldq, a->h, a->ldh,
+                                             lse ? lse + (long long)l * P * a->heads * 2 * Np : nullptr, &d, stream)))
       return rc;
   }
   return tgmx_dygformer_tail(save->x + (long long)a->num_layers * R * a->ldx, a->ldx, P, Np, D, a->mean, a->ldx, a->out_w, a->out_b, a->E, a->out, stream);
 }
 
-extern "C" int tgmx_dygformer_forward(const tgmx_dygformer_fwd_t* a, tgmx_stream_t stream) { return dyg_forward(a, nullptr, nullptr, stream); }
+extern "C" int tgmx_dygformer_forward(const tgmx_dygformer_fwd_t* a, tgmx_stream_t stream) { return dyg_forward(a, nullptr, nullptr, nullptr, stream); }
+
+extern "C" int tgmx_dygformer_forward_train_lse(const tgmx_dygformer_fwd_t* a, const tgmx_dygformer_save_t* save, float* lse,
+                                                const tgmx_dropout_t* drop, tgmx_stream_t stream) {
+  TGMX_REQUIRE(save, "dygformer_forward_train: null save block");
+  TGMX_REQUIRE(!drop || (drop->p >= 0.f && drop->p < 1.f), "dygformer_forward_train: p must be in [0, 1)");
+  if (a && a->P > 0 && a->patch > 0 && a->heads > 0) {
+    const int T = 2 * ((a->k + 1) / a->patch), dh = 4 * a->C / a->heads;
+    if (!tgmx_mha_small_train_supported(T, dh) && !(lse && tgmx_mha_stream_supported(T, dh))) {
+      set_error("dygformer_forward_train: %d tokens x head dimension %d is outside the attention backward's envelope", T, dh);
+      return TGMX_E_UNSUPPORTED;
+    }
+  }
+  return dyg_forward(a, save, lse, drop, stream);
+}
 
 extern "C" int tgmx_dygformer_forward_train(const tgmx_dygformer_fwd_t* a, const tgmx_dygformer_save_t* save, const tgmx_dropout_t* drop,
                                             tgmx_stream_t stream) {
-  TGMX_REQUIRE(save, "dygformer_forward_train: null save block");
-  TGMX_REQUIRE(!drop || (drop->p >= 0.f && drop->p < 1.f), "dygformer_forward_train: p must be in [0, 1)");
-  if (a && a->P > 0 && a->patch > 0 && a->heads > 0 && !tgmx_mha_small_train_supported(2 * ((a->k + 1) / a->patch), 4 * a->C / a->heads)) {
-    set_error("dygformer_forward_train: %d tokens x head dimension %d is outside the attention backward's envelope", 2 * ((a->k + 1) / a->patch),
-              4 * a->C / a->heads);
-    return TGMX_E_UNSUPPORTED;
-  }
-  return dyg_forward(a, save, drop, stream);
+  return tgmx_dygformer_forward_train_lse(a, save, nullptr, drop, stream);
 }

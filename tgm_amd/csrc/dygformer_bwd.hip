@@ -351,8 +351,8 @@ extern "C" int tgmx_dygformer_cooccurrence_backward(const int32_t* counts, const
 // ---- one layer --------------------------------------------------------------------------------------------------------------------------------
 static int layer_backward_pass(const tgmx_dygformer_layer_t* ly, const tgmx_dygformer_layer_tr_t* tr, const tgmx_dygformer_layer_grad_t* d, int64_t B,
                                int T, int H, int D, float eps, const float* x, const float* qkv, const float* att, const float* x1, int64_t ldx,
-                               int64_t ldq, int64_t ldh, float* g, float* dx, const tgmx_dropout_t* drop, void* workspace, bool dry, size_t* need,
-                               tgmx_stream_t stream) {
+                               int64_t ldq, int64_t ldh, const float* lse, float* g, float* dx, const tgmx_dropout_t* drop, void* workspace, bool dry,
+                               size_t* need, tgmx_stream_t stream) {
   const int64_t R = B * T;
   const bool dropping = drop && drop->p > 0.f;
   WorkspaceCarver ws(dry ? nullptr : workspace);
@@ -417,7 +417,11 @@ static int layer_backward_pass(const tgmx_dygformer_layer_t* ly, const tgmx_dygf
   if (d->out_b && (rc = tgmx_colsum(g1, ldx, R, D, d->out_b, 0, cs_ws, stream))) return rc;
   if (!(d->ln0_g || d->ln0_b || d->in_w || d->in_b || dx)) return TGMX_OK;
   if ((rc = tgmx_sgemm_nt_ep(g1, ldx, tr->out_wT, D, datt, ldx, R, D, D, nullptr, 0, nullptr, 0, stream))) return rc;
-  if ((rc = tgmx_mha_small_backward(qkv, ldq, datt, ldx, B, T, H, D / H, dqkv, &site[0], stream))) return rc;
+  if (lse) {  // past 128 tokens: the streaming backward; its delta [B, H, T] sits in dgx, free until the second LayerNorm backward
+    if ((rc = tgmx_mha_stream_backward(qkv, ldq, att, datt, ldx, lse, B, T, H, D / H, dqkv, dgx, &site[0], stream))) return rc;
+  } else if ((rc = tgmx_mha_small_backward(qkv, ldq, datt, ldx, B, T, H, D / H, dqkv, &site[0], stream))) {
+    return rc;
+  }
   if (d->in_w) {
     if ((rc = tgmx_layernorm_rows(x, ldx, R, D, ly->ln0_g, ly->ln0_b, eps, y, ldx, stream))) return rc;
     if ((rc = tgmx_sgemm_tn(dqkv, ldq, y, ldx, d->in_w, D, R, 3 * D, D, 1, 0, 0, 0, 0, tn_ws, stream))) return rc;
@@ -445,19 +449,21 @@ extern "C" size_t tgmx_dygformer_layer_backward_workspace_bytes(int64_t B, int32
   if (B < 0 || T <= 0 || D <= 0 || ldx < D || ldq < 3ll * D || ldh < 4ll * D) return 0;
   size_t need = 0;
   const tgmx_dropout_t on{0.5f, 0, 0, 0};  // (the size with dropout: an upper bound)
-  layer_backward_pass(nullptr, nullptr, nullptr, B, T, 1, D, 0.f, nullptr, nullptr, nullptr, nullptr, ldx, ldq, ldh, nullptr, nullptr, &on, nullptr, true,
-                      &need, nullptr);
+  layer_backward_pass(nullptr, nullptr, nullptr, B, T, 1, D, 0.f, nullptr, nullptr, nullptr, nullptr, ldx, ldq, ldh, nullptr, nullptr, nullptr, &on, nullptr,
+                      true, &need, nullptr);
   return need;
 }
 
-extern "C" int tgmx_dygformer_layer_backward(const tgmx_dygformer_layer_t* ly, const tgmx_dygformer_layer_tr_t* tr,
-                                             const tgmx_dygformer_layer_grad_t* d, int64_t B, int32_t T, int32_t H, int32_t D, float eps,
-                                             const float* x, const float* qkv, const float* att, const float* x1, int64_t ldx, int64_t ldq,
-                                             int64_t ldh, float* g, float* dx, const tgmx_dropout_t* drop, void* workspace,
-                                             size_t workspace_bytes, tgmx_stream_t stream) {
+// lse [B, H, T]: what tgmx_dygformer_layer_train_lse kept past 128 tokens (the streaming attention backward reads it); NULL: T <= 128
+extern "C" int tgmx_dygformer_layer_backward_lse(const tgmx_dygformer_layer_t* ly, const tgmx_dygformer_layer_tr_t* tr,
+                                                 const tgmx_dygformer_layer_grad_t* d, int64_t B, int32_t T, int32_t H, int32_t D, float eps,
+                                                 const float* x, const float* qkv, const float* att, const float* x1, int64_t ldx, int64_t ldq,
+                                                 int64_t ldh, const float* lse, float* g, float* dx, const tgmx_dropout_t* drop, void* workspace,
+                                                 size_t workspace_bytes, tgmx_stream_t stream) {
   int rc;
   if ((rc = layer_check(ly, tr, d, B, T, H, D, ldx, ldq, ldh, drop))) return rc;
-  if (!tgmx_mha_small_train_supported(T, D / H)) {
+  const bool lng = lse && T > kMhaMaxT && tgmx_mha_stream_supported(T, D / H);
+  if (!lng && !tgmx_mha_small_train_supported(T, D / H)) {
     set_error("dygformer_layer_backward: T=%d tokens x head dimension %d is outside the attention backward's envelope", T, D / H);
     return TGMX_E_UNSUPPORTED;
   }
@@ -468,7 +474,16 @@ extern "C" int tgmx_dygformer_layer_backward(const tgmx_dygformer_layer_t* ly, c
   const size_t need = tgmx_dygformer_layer_backward_workspace_bytes(B, T, D, ldx, ldq, ldh);
   TGMX_REQUIRE(workspace && workspace_bytes >= need, "dygformer_layer_backward: workspace too small (%zu bytes, %zu needed)", workspace_bytes, need);
   size_t used = 0;
-  return layer_backward_pass(ly, tr, d, B, T, H, D, eps, x, qkv, att, x1, ldx, ldq, ldh, g, dx, drop, workspace, false, &used, stream);
+  return layer_backward_pass(ly, tr, d, B, T, H, D, eps, x, qkv, att, x1, ldx, ldq, ldh, lng ? lse : nullptr, g, dx, drop, workspace, false, &used, stream);
+}
+
+extern "C" int tgmx_dygformer_layer_backward(const tgmx_dygformer_layer_t* ly, const tgmx_dygformer_layer_tr_t* tr,
+                                             const tgmx_dygformer_layer_grad_t* d, int64_t B, int32_t T, int32_t H, int32_t D, float eps,
+                                             const float* x, const float* qkv, const float* att, const float* x1, int64_t ldx, int64_t ldq,
+                                             int64_t ldh, float* g, float* dx, const tgmx_dropout_t* drop, void* workspace,
+                                             size_t workspace_bytes, tgmx_stream_t stream) {
+  return tgmx_dygformer_layer_backward_lse(ly, tr, d, B, T, H, D, eps, x, qkv, att, x1, ldx, ldq, ldh, nullptr, g, dx, drop, workspace, workspace_bytes,
+                                           stream);
 }
 
 // ---- the whole backward as one call ---------------------------------------------------------------------------------------------------------
@@ -489,7 +504,7 @@ static int dyg_bwd_check(const tgmx_dygformer_bwd_t* a, const char* what) {
   return TGMX_OK;
 }
 
-static int dyg_backward_pass(const tgmx_dygformer_bwd_t* a, bool dry, size_t* need, tgmx_stream_t stream) {
+static int dyg_backward_pass(const tgmx_dygformer_bwd_t* a, const float* lse, bool dry, size_t* need, tgmx_stream_t stream) {
   const int64_t P = a->P;
   const int L = a->k + 1, Np = L / a->patch, C = a->C, D = 4 * C, E = a->E, nL = a->num_layers, T = 2 * Np;
   const int64_t R = 2 * P * Np, n = 2 * P * L, ldx = a->ldx;
@@ -544,9 +559,9 @@ static int dyg_backward_pass(const tgmx_dygformer_bwd_t* a, bool dry, size_t* ne
     const int64_t ox = (int64_t)l * R * ldx, oq = (int64_t)l * R * a->ldq;
     const bool down = l > lowest || want_proj;
     const tgmx_dropout_t d{a->drop_p, a->drop_seed, a->drop_stream + 4ull * l, 0};
-    if ((rc = tgmx_dygformer_layer_backward(&a->layers[l], &a->tr[l], &a->d_layers[l], P, T, a->heads, D, a->eps, a->save_x + ox, a->save_qkv + oq,
-                                            a->save_att + ox, a->save_x1 + ox, ldx, a->ldq, a->ldh, gz, down ? gz2 : nullptr, &d, ly_ws, ly_bytes,
-                                            stream)))
+    if ((rc = tgmx_dygformer_layer_backward_lse(&a->layers[l], &a->tr[l], &a->d_layers[l], P, T, a->heads, D, a->eps, a->save_x + ox, a->save_qkv + oq,
+                                                a->save_att + ox, a->save_x1 + ox, ldx, a->ldq, a->ldh, lse ? lse + (int64_t)l * P * a->heads * T : nullptr,
+                                                gz, down ? gz2 : nullptr, &d, ly_ws, ly_bytes, stream)))
       return rc;
     float* tmp = gz;
     gz = gz2;
@@ -586,16 +601,17 @@ static int dyg_backward_pass(const tgmx_dygformer_bwd_t* a, bool dry, size_t* ne
 extern "C" size_t tgmx_dygformer_backward_workspace_bytes(const tgmx_dygformer_bwd_t* a) {
   size_t need = 0;
   if (dyg_bwd_check(a, "dygformer_backward_workspace_bytes") != TGMX_OK) return 0;
-  return dyg_backward_pass(a, true, &need, nullptr) == TGMX_OK ? need : 0;
+  return dyg_backward_pass(a, nullptr, true, &need, nullptr) == TGMX_OK ? need : 0;
 }
 
-extern "C" int tgmx_dygformer_backward(const tgmx_dygformer_bwd_t* a, tgmx_stream_t stream) {
+// lse [num_layers, P, heads, T]: what tgmx_dygformer_forward_train_lse kept past 128 tokens; NULL: T <= 128
+extern "C" int tgmx_dygformer_backward_lse(const tgmx_dygformer_bwd_t* a, const float* lse, tgmx_stream_t stream) {
   int rc;
   if ((rc = dyg_bwd_check(a, "dygformer_backward"))) return rc;
   if (a->P == 0) return TGMX_OK;
-  if (!tgmx_mha_small_train_supported(2 * ((a->k + 1) / a->patch), 4 * a->C / a->heads)) {
-    set_error("dygformer_backward: %d tokens x head dimension %d is outside the attention backward's envelope", 2 * ((a->k + 1) / a->patch),
-              4 * a->C / a->heads);
+  const int T = 2 * ((a->k + 1) / a->patch), dh = 4 * a->C / a->heads;
+  if (!tgmx_mha_small_train_supported(T, dh) && !(lse && tgmx_mha_stream_supported(T, dh))) {
+    set_error("dygformer_backward: %d tokens x head dimension %d is outside the attention backward's envelope", T, dh);
     return TGMX_E_UNSUPPORTED;
   }
   TGMX_REQUIRE(a->g && a->mean && a->out_wT, "dygformer_backward: the upstream gradient or the forward's saved buffers are missing");
@@ -606,7 +622,9 @@ extern "C" int tgmx_dygformer_backward(const tgmx_dygformer_bwd_t* a, tgmx_strea
   TGMX_REQUIRE(!(a->d_co_w1 || a->d_co_b1 || a->d_co_w2 || a->d_co_b2) || (a->proj_wT[3] && a->counts && a->co_w1 && a->co_b1 && a->co_w2T),
                "dygformer_backward: the co-occurrence tail needs proj_wT[3], the counts and the encoder");
   size_t need = 0;
-  if ((rc = dyg_backward_pass(a, true, &need, nullptr))) return rc;
+  if ((rc = dyg_backward_pass(a, lse, true, &need, nullptr))) return rc;
   TGMX_REQUIRE(a->workspace && a->workspace_bytes >= need, "dygformer_backward: workspace too small (%zu bytes, %zu needed)", a->workspace_bytes, need);
-  return dyg_backward_pass(a, false, &need, stream);
+  return dyg_backward_pass(a, lse, false, &need, stream);
 }
+
+extern "C" int tgmx_dygformer_backward(const tgmx_dygformer_bwd_t* a, tgmx_stream_t stream) { return tgmx_dygformer_backward_lse(a, nullptr, stream); }

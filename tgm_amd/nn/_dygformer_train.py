@@ -34,6 +34,7 @@ token rows, D = 4 C, leading dimensions rounded up to 4 floats:
     x         4 (num_layers + 1) R D
     qkv       12 num_layers R D
     att | x1  8 num_layers R D
+    lse       4 num_layers R heads    (only past 128 tokens per pair: the streaming attention's m + log l per query row and head)
     mean      8 P D
 
 -- at the example's shape (bs 200: P = 200, L = 32, patch 1, R = n = 12 800, dN = 128, dE = 172, dT = 100, C = 50, D = 200, 2 layers) 23.1 MB
@@ -49,6 +50,11 @@ tensor), regenerated in the backward, never stored.
 The attention backward keeps Q, K, V, dO and two T x T tiles resident in LDS (140.5 KiB at T = 64, dh = 100: one workgroup per CU), so
 the training envelope is narrower than inference's: ``tgmx_mha_small_train_supported`` (T = 64 with dh = 128 and T = 128 with dh = 32
 are outside and compose).
+
+Past 128 tokens per pair (``TGMX_DYGFORMER_LONG=native``, :func:`long_supported`) the attention is ``tgmx_mha_stream_train`` /
+``tgmx_mha_stream_backward`` (``csrc/mha_stream.hip``): K and V streamed through LDS, the probabilities recomputed block by block from the
+saved ``lse`` rows -- 0.8 MB a layer at P = 200, T = 512, two heads, where composed attention keeps 419 MB of probabilities.  The calls
+are the ``_lse`` forms of the same entry points; everything else above is unchanged.
 """
 from __future__ import annotations
 
@@ -86,6 +92,21 @@ def train_supported(T: int, dh: int) -> bool:
     return bool(_native.load().tgmx_mha_small_train_supported(int(T), int(dh)))
 
 
+LONG_DEFAULT = 'native'  # chosen by tools/bench_dygformer_long.py against the composed path
+
+
+def long_mode() -> str:
+    """'native' or 'torch': ``TGMX_DYGFORMER_LONG``, the route of more than 128 tokens per pair; anything else is the default."""
+    m = os.environ.get('TGMX_DYGFORMER_LONG', '')
+    return m if m in ('native', 'torch') else LONG_DEFAULT
+
+
+def long_supported(T: int, D: int, H: int) -> bool:
+    """T tokens at head dimension D / H take the streaming attention kernels (``tgmx_mha_stream_supported``: the one function the host
+    and the C entry points choose by), forward and backward alike, and ``TGMX_DYGFORMER_LONG`` asks for them."""
+    return long_mode() == 'native' and D % H == 0 and bool(_native.load().tgmx_mha_stream_supported(int(T), int(D // H)))
+
+
 def _layer_params(t) -> tuple:
     """The twelve parameters of a ``TransformerEncoder`` in ``tgmx_dygformer_layer_t``'s order."""
     mha, ln, lin = t.multi_head_attention, t.norm_layers, t.linear_layers
@@ -117,24 +138,38 @@ def _common(module, *inputs: Tensor) -> bool:
     return any(p.requires_grad for p in params)
 
 
-def in_envelope(module, a: dict) -> bool:
-    """The native training path takes this ``DyGFormer`` call (the conditions of the module docstring of ``dygformer.py``)."""
+def _model_ok(module, a: dict, long: bool) -> bool:
     node_x, nbr_x = a['node_x'], a['nbr_x']
     if a['P'] <= 0 or node_x.requires_grad or nbr_x.requires_grad or not _common(module, node_x, nbr_x):
         return False
-    if type(module.time_encoder) is not Time2Vec or not module._native_ok(a['L']):
+    if type(module.time_encoder) is not Time2Vec or not (module._native_long_ok(a['L']) if long else module._native_ok(a['L'])):
         return False
     D = module.num_channels * module.channel_embedding_dim
-    if D % module.num_heads or not train_supported(2 * module.num_patches, D // module.num_heads):
+    if D % module.num_heads or not (long or train_supported(2 * module.num_patches, D // module.num_heads)):
         return False
     eps = {float(n.eps) for t in module.transformers for n in t.norm_layers}
     return len(eps) <= 1 and all(_layer_ok(t, module.dropout) for t in module.transformers)
+
+
+def in_envelope(module, a: dict) -> bool:
+    """The native training path takes this ``DyGFormer`` call (the conditions of the module docstring of ``dygformer.py``)."""
+    return _model_ok(module, a, False)
+
+
+def in_long_envelope(module, a: dict) -> bool:
+    """The same conditions past 128 tokens per pair: the streaming attention (``long_supported``) in place of ``train_supported``."""
+    return _model_ok(module, a, True)
 
 
 def layer_in_envelope(t, x: Tensor) -> bool:
     """The native training path takes this ``TransformerEncoder.forward`` call: as above, for one layer; ``x`` may ask for its gradient."""
     B, T, D = x.shape
     return B * T > 0 and _common(t, x) and _layer_ok(t, t.dropout_rate) and D % t.num_heads == 0 and train_supported(T, D // t.num_heads)
+
+
+def layer_in_long_envelope(t, x: Tensor) -> bool:
+    B, T, D = x.shape
+    return B * T > 0 and _common(t, x) and _layer_ok(t, t.dropout_rate) and long_supported(T, D, t.num_heads)
 
 
 def _site0(drop: Tuple[float, int, int], layer: int):
@@ -262,13 +297,20 @@ class DyGFormerFunction(torch.autograd.Function):
         blk.ldx, blk.ldq, blk.ldh = ldx, ldq, ldh
         blk.out = out.data_ptr()
         save = _native.DyGFormerSave(counts.data_ptr(), save_x.data_ptr(), save_qkv.data_ptr(), save_att.data_ptr(), save_x1.data_ptr())
-        check_supported(lib.tgmx_dygformer_forward_train(ctypes.byref(blk), ctypes.byref(save), _native.dropout_desc(*drop), _native.stream_ptr()),
-                        'tgmx_dygformer_forward_train')  # fmt: skip
+        T = 2 * module.num_patches
+        lse = torch.empty((nL, P, module.num_heads, T), dtype=torch.float32, device=dev) if T > _native.MHA_SMALL_MAX_TOKENS else None
+        if lse is None:
+            check_supported(lib.tgmx_dygformer_forward_train(ctypes.byref(blk), ctypes.byref(save), _native.dropout_desc(*drop), _native.stream_ptr()),
+                            'tgmx_dygformer_forward_train')  # fmt: skip
+        else:  # the long route: the attention's m + log l per query row is kept for the backward
+            check_supported(lib.tgmx_dygformer_forward_train_lse(ctypes.byref(blk), ctypes.byref(save), lse.data_ptr(), _native.dropout_desc(*drop),
+                                                                 _native.stream_ptr()), 'tgmx_dygformer_forward_train_lse')  # fmt: skip
         # the weights belong to THIS forward: a later parameter version rebuilds the module's cache, not what the call holds
         w = backward_weights(module, module.transformers, module)
         ctx.module = module
         ctx.s = SimpleNamespace(P=P, L=L, dims=d, drop=drop, ch=ch, counts=counts, mean=mean, save_x=save_x, save_qkv=save_qkv, save_att=save_att,
-                                save_x1=save_x1, w=w, eps=float(blk.eps), a={k: a[k] for k in ('src', 'dst', 't', 'nids', 'nbr_t', 'src_rows', 'dst_rows')})  # fmt: skip
+                                save_x1=save_x1, lse=lse, w=w, eps=float(blk.eps),
+                                a={k: a[k] for k in ('src', 'dst', 't', 'nids', 'nbr_t', 'src_rows', 'dst_rows')})  # fmt: skip
         return out[:P], out[P:]
 
     @staticmethod
@@ -321,7 +363,7 @@ class DyGFormerFunction(torch.autograd.Function):
             for name, p, gr, ptr in zip(_LAYER_FIELDS, ps_, grads, ptrs):
                 setattr(t.d_layers[l], name, ptr)
                 by_id[id(p)] = gr
-        _run(t, dev)
+        _run(t, dev, s.lse)
         return (None, None) + tuple(by_id.get(id(p)) if n else None for p, n in zip(params, ctx.needs_input_grad[2:]))
 
 
@@ -330,10 +372,10 @@ def apply(module, a: dict) -> Tuple[Tensor, Tensor]:
     return DyGFormerFunction.apply(module, a, *param_list(module))
 
 
-def _run(t, dev) -> None:
-    """The backward over the filled block ``t``: the one call, or its launches one by one."""
+def _run(t, dev, lse: Optional[Tensor] = None) -> None:
+    """The backward over the filled block ``t``: the one call, or its launches one by one.  ``lse``: what the long route's forward kept."""
     if mode() == 'py':
-        backward_per_launch(t, dev)
+        backward_per_launch(t, dev, lse)
         return
     lib = _native.load()
     need = int(lib.tgmx_dygformer_backward_workspace_bytes(ctypes.byref(t)))
@@ -341,7 +383,10 @@ def _run(t, dev) -> None:
         _native.check(-1, 'tgmx_dygformer_backward_workspace_bytes')
     ws = torch.empty(need, dtype=torch.uint8, device=dev)
     t.workspace, t.workspace_bytes = ws.data_ptr(), need
-    _native.check(lib.tgmx_dygformer_backward(ctypes.byref(t), _native.stream_ptr()), 'tgmx_dygformer_backward')
+    if lse is None:
+        _native.check(lib.tgmx_dygformer_backward(ctypes.byref(t), _native.stream_ptr()), 'tgmx_dygformer_backward')
+    else:
+        _native.check(lib.tgmx_dygformer_backward_lse(ctypes.byref(t), lse.data_ptr(), _native.stream_ptr()), 'tgmx_dygformer_backward_lse')
     t.workspace, t.workspace_bytes = None, 0
 
 
@@ -363,13 +408,15 @@ class LayerFunction(torch.autograd.Function):
         xout, y, x1, att, qkv, h = _grad_views([(R, ldx)] * 4 + [(R, ldq), (R, ldh)], dev)
         keep, f32 = weight_keeper()
         ly = _layer_block(t, f32)
-        check_supported(
-            lib.tgmx_dygformer_layer_train(ctypes.byref(ly), B, T, t.num_heads, D, float(t.norm_layers[0].eps), xin.data_ptr(), xout.data_ptr(), y.data_ptr(),
-                                           x1.data_ptr(), att.data_ptr(), ldx, qkv.data_ptr(), ldq, h.data_ptr(), ldh, _site0(drop, 0), st),
-            'tgmx_dygformer_layer_train',
-        )  # fmt: skip
+        lse = torch.empty((B, t.num_heads, T), dtype=torch.float32, device=dev) if T > _native.MHA_SMALL_MAX_TOKENS else None
+        head = (ctypes.byref(ly), B, T, t.num_heads, D, float(t.norm_layers[0].eps), xin.data_ptr(), xout.data_ptr(), y.data_ptr(), x1.data_ptr(),
+                att.data_ptr(), ldx, qkv.data_ptr(), ldq, h.data_ptr(), ldh)  # fmt: skip
+        if lse is None:
+            check_supported(lib.tgmx_dygformer_layer_train(*head, _site0(drop, 0), st), 'tgmx_dygformer_layer_train')
+        else:
+            check_supported(lib.tgmx_dygformer_layer_train_lse(*head, lse.data_ptr(), _site0(drop, 0), st), 'tgmx_dygformer_layer_train_lse')
         ctx.t, ctx.params = t, params
-        ctx.s = SimpleNamespace(B=B, T=T, D=D, drop=drop, x=xin, x1=x1, att=att, qkv=qkv, w=backward_weights(t, [t]))
+        ctx.s = SimpleNamespace(B=B, T=T, D=D, drop=drop, x=xin, x1=x1, att=att, qkv=qkv, lse=lse, w=backward_weights(t, [t]))
         return xout[:, :D].reshape(B, T, D)
 
     @staticmethod
@@ -396,9 +443,9 @@ class LayerFunction(torch.autograd.Function):
         args = (ly, tr, d, B, T, t.num_heads, D, float(t.norm_layers[0].eps), s.x.data_ptr(), s.qkv.data_ptr(), s.att.data_ptr(), s.x1.data_ptr(), ldx, ldq,
                 ldh, gz.data_ptr(), _native.ptr(dx), (s.drop[0], s.drop[1], s.drop[2]))  # fmt: skip
         if mode() == 'py':
-            _LayerRun(dev).layer(*args)
+            _LayerRun(dev).layer(*args, lse=_native.ptr(s.lse))
         else:
-            _layer_native(*args, dev)
+            _layer_native(*args, dev, s.lse)
         return (None, dx[:, :D].reshape(B, T, D) if want_dx else None) + tuple(grads[order[id(p)]] if n else None for p, n in zip(params, need_p))
 
 
@@ -407,15 +454,16 @@ def apply_layer(t, x: Tensor) -> Tensor:
     return LayerFunction.apply(t, x, *t.parameters())
 
 
-def _layer_native(ly, tr, d, B, T, H, D, eps, x, qkv, att, x1, ldx, ldq, ldh, g, dx, drop, dev) -> None:
+def _layer_native(ly, tr, d, B, T, H, D, eps, x, qkv, att, x1, ldx, ldq, ldh, g, dx, drop, dev, lse: Optional[Tensor] = None) -> None:
     lib = _native.load()
     need = int(lib.tgmx_dygformer_layer_backward_workspace_bytes(B, T, D, ldx, ldq, ldh))
     ws = torch.empty(max(1, need), dtype=torch.uint8, device=dev)
-    check_supported(
-        lib.tgmx_dygformer_layer_backward(ctypes.byref(ly), ctypes.byref(tr), ctypes.byref(d), B, T, H, D, eps, x, qkv, att, x1, ldx, ldq, ldh, g, dx,
-                                          _native.dropout_desc(*drop), ws.data_ptr(), need, _native.stream_ptr()),
-        'tgmx_dygformer_layer_backward',
-    )  # fmt: skip
+    head = (ctypes.byref(ly), ctypes.byref(tr), ctypes.byref(d), B, T, H, D, eps, x, qkv, att, x1, ldx, ldq, ldh)
+    tail = (g, dx, _native.dropout_desc(*drop), ws.data_ptr(), need, _native.stream_ptr())
+    if lse is None:
+        check_supported(lib.tgmx_dygformer_layer_backward(*head, *tail), 'tgmx_dygformer_layer_backward')
+    else:
+        check_supported(lib.tgmx_dygformer_layer_backward_lse(*head, lse.data_ptr(), *tail), 'tgmx_dygformer_layer_backward_lse')
 
 
 # ---- the launches of tgmx_dygformer_backward, one ctypes call each (TGMX_DYGFORMER_BWD=py) ----------------------------------------------------
@@ -440,8 +488,9 @@ class _LayerRun:
     def nt(self, A, lda, B, ldb, C, ldc, M, N, K, bias=None) -> None:
         _native.check(self.lib.tgmx_sgemm_nt_ep(A, lda, B, ldb, C, ldc, M, N, K, bias, 0, None, 0, self.st), 'tgmx_sgemm_nt_ep')
 
-    def layer(self, ly, tr, d, B, T, H, D, eps, x, qkv, att, x1, ldx, ldq, ldh, g, dx, drop) -> None:
-        """g [R, ldx] (pointer): the gradient at the layer's output, clobbered; dx (pointer or None): the gradient at its input."""
+    def layer(self, ly, tr, d, B, T, H, D, eps, x, qkv, att, x1, ldx, ldq, ldh, g, dx, drop, lse=None) -> None:
+        """g [R, ldx] (pointer): the gradient at the layer's output, clobbered; dx (pointer or None): the gradient at its input; lse
+        (pointer or None): what the long route's forward kept."""
         lib, st, R = self.lib, self.st, B * T
         site = [_native.dropout_desc(drop[0], drop[1], drop[2] + s) for s in range(4)]
         ln = lambda src, gam, bet, dst: _native.check(lib.tgmx_layernorm_rows(src, ldx, R, D, gam, bet, eps, dst, ldx, st), 'tgmx_layernorm_rows')
@@ -491,7 +540,10 @@ class _LayerRun:
             return
         datt, dqkv = self.buf(R * ldx), self.buf(R * ldq)
         self.nt(g1, ldx, tr.out_wT, D, datt, ldx, R, D, D)
-        check_supported(lib.tgmx_mha_small_backward(qkv, ldq, datt, ldx, B, T, H, D // H, dqkv, site[0], st), 'tgmx_mha_small_backward')
+        if lse is None:
+            check_supported(lib.tgmx_mha_small_backward(qkv, ldq, datt, ldx, B, T, H, D // H, dqkv, site[0], st), 'tgmx_mha_small_backward')
+        else:  # (the native call keeps delta in dgx)
+            check_supported(lib.tgmx_mha_stream_backward(qkv, ldq, att, datt, ldx, lse, B, T, H, D // H, dqkv, dgx, site[0], st), 'tgmx_mha_stream_backward')
         if d.in_w:
             ln(x, ly.ln0_g, ly.ln0_b, y)
             self.tn(dqkv, ldq, y, ldx, d.in_w, D, R, 3 * D, D)
@@ -511,7 +563,7 @@ class _LayerRun:
         _native.check(lib.tgmx_add_cols(dx, ldx, g, ldx, R, D, 1, st), 'tgmx_add_cols')
 
 
-def backward_per_launch(a, dev) -> None:
+def backward_per_launch(a, dev, lse: Optional[Tensor] = None) -> None:
     """What ``tgmx_dygformer_backward`` composes, in its order with its kernels; every buffer of the native call's workspace is a tensor here."""
     run = _LayerRun(dev)
     lib, st = run.lib, run.st
@@ -539,7 +591,8 @@ def backward_per_launch(a, dev) -> None:
         ox, oq = 4 * l * R * ldx, 4 * l * R * a.ldq
         down = l > lowest or want_proj
         run.layer(a.layers[l], a.tr[l], a.d_layers[l], P, T, a.heads, D, a.eps, a.save_x + ox, a.save_qkv + oq, a.save_att + ox, a.save_x1 + ox, ldx, a.ldq,
-                  a.ldh, gz, gz2 if down else None, (a.drop_p, a.drop_seed, a.drop_stream + 4 * l))  # fmt: skip
+                  a.ldh, gz, gz2 if down else None, (a.drop_p, a.drop_seed, a.drop_stream + 4 * l),
+                  lse=None if lse is None else lse[l].data_ptr())  # fmt: skip
         gz, gz2 = gz2, gz
     if not want_proj:
         return
@@ -579,4 +632,4 @@ def cooccurrence_backward(counts, dfeat, ldf, n, L, C, w1, b1, w2T, d_w1, d_b1, 
 
 
 __all__ = ['DEFAULT', 'DyGFormerFunction', 'LayerFunction', 'apply', 'apply_layer', 'backward_per_launch', 'backward_weights', 'cooccurrence_backward',
-           'in_envelope', 'layer_in_envelope', 'mode', 'train_supported']
+           'in_envelope', 'in_long_envelope', 'layer_in_envelope', 'layer_in_long_envelope', 'long_mode', 'long_supported', 'mode', 'train_supported']

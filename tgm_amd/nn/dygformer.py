@@ -36,6 +36,12 @@ train-mode dropout with gradients disabled.  ``NeighborCooccurrenceEncoder.forwa
 the native inference envelope (more than 128 tokens per pair, a head dimension above 128, more than 2048 slots per sequence, more than 8
 layers) also takes the composed path on the device, and so does a device that cannot give the attention kernels their LDS
 (``TGMX_E_UNSUPPORTED``).  CPU tensors raise ``NativeLibraryError``.
+
+More than 128 tokens per pair (up to 4096, head dimension <= 128) has a native route of its own, ``TGMX_DYGFORMER_LONG`` = ``native`` or
+``torch`` (the default: ``_dygformer_train.LONG_DEFAULT``): the same one-call forward and one-call backward with the
+attention on the streaming kernels of ``csrc/mha_stream.hip`` (``tgmx_mha_stream_train`` / ``tgmx_mha_stream_backward``; K and V pass
+through LDS in blocks, nothing T x T is written), under the same other conditions as the short route.  ``_native_ok``, ``_mha_in_envelope``
+and ``train_supported`` keep describing the short route; ``_native_long_ok``, ``long_supported`` and ``in_long_envelope`` stand beside them.
 """
 from __future__ import annotations
 
@@ -180,12 +186,13 @@ class TransformerEncoder(nn.Module):
         if inputs.dim() != 3 or inputs.shape[2] != self.attention_dim:
             raise ValueError(f'TransformerEncoder expects [B, T, {self.attention_dim}], got {list(inputs.shape)}')
         B, T, D = inputs.shape
-        if _train.layer_in_envelope(self, inputs):
+        if _train.layer_in_envelope(self, inputs) or _train.layer_in_long_envelope(self, inputs):
             try:
                 return _train.apply_layer(self, inputs)
             except Unsupported:  # the device cannot give the attention kernels their LDS: compose
                 return self._torch_forward(inputs)
-        if needs_torch(self, self.dropout_rate, inputs) or not _mha_in_envelope(T, D, self.num_heads) or B * T == 0:
+        in_envelope = _mha_in_envelope(T, D, self.num_heads) or _train.long_supported(T, D, self.num_heads)
+        if needs_torch(self, self.dropout_rate, inputs) or not in_envelope or B * T == 0:
             return self._torch_forward(inputs)
         self._check_native()
         ldx = up4(D)
@@ -253,16 +260,22 @@ class DyGFormer(TransientCaches, nn.Module):
         return (L <= _native.DYGFORMER_MAX_SEQ and self.num_layers <= _native.DYGFORMER_MAX_LAYERS and hasattr(self.time_encoder, 'w')
                 and _mha_in_envelope(2 * self.num_patches, D, self.num_heads))  # fmt: skip
 
+    def _native_long_ok(self, L: int) -> bool:
+        """``_native_ok`` for the long route: more than 128 tokens per pair on the streaming attention (``TGMX_DYGFORMER_LONG=native``)."""
+        D = self.num_channels * self.channel_embedding_dim
+        return (L <= _native.DYGFORMER_MAX_SEQ and self.num_layers <= _native.DYGFORMER_MAX_LAYERS and hasattr(self.time_encoder, 'w')
+                and _train.long_supported(2 * self.num_patches, D, self.num_heads))  # fmt: skip
+
     def _run(self, a: dict) -> Tuple[Tensor, Tensor]:
         grad_inputs = (a['node_x'], a['nbr_x'])
-        if _train.in_envelope(self, a):
+        if _train.in_envelope(self, a) or _train.in_long_envelope(self, a):
             for t in self.transformers:
                 t._check_native()
             try:
                 return _train.apply(self, a)
             except Unsupported:  # the device cannot give the attention kernels their LDS: compose
                 return self._torch_forward(a)
-        if needs_torch(self, self.dropout, *grad_inputs) or not self._native_ok(a['L']):
+        if needs_torch(self, self.dropout, *grad_inputs) or not (self._native_ok(a['L']) or self._native_long_ok(a['L'])):
             return self._torch_forward(a)
         for t in self.transformers:
             t._check_native()
