@@ -59,7 +59,7 @@ int tgmx_version(void);
  * 12 tgmx_tgn_step_t, ..., 22 tgmx_ctan_fwd_t, 24 tgmx_gclstm_fwd_t, 26 tgmx_roland_fwd_t, 27 tgmx_decoder_fwd_t, 35 tgmx_ctan_bwd_t, 36 tgmx_graphmixer_bwd_t, 37 tgmx_dygformer_bwd_t, 38 tgmx_tpnet_bwd_t (23 and 25 are reserved and answer 0: tests/test_ctan_cpu.py and
  * tests/test_gclstm_cpu.py pin them), 28 tgmx_an_batch_t, 29 tgmx_node_analytics_t, 30 tgmx_decoder_train_t, 32 tgmx_gclstm_bwd_t (31 is
  * reserved the same way: tests/test_decoder_train_cpu.py), 39 tgmx_gcn_conv_bwd_t, 40 tgmx_tgcn_csr_fwd_t, 41 tgmx_tgcn_csr_bwd_t,
- * 43 tgmx_tconv_bwd_t (42 is reserved the same way: tests/test_gcn_sparse_cpu.py) */
+ * 43 tgmx_tconv_bwd_t (42 is reserved the same way: tests/test_gcn_sparse_cpu.py), 44 tgmx_dos_t */
 size_t tgmx_abi_sizeof(int32_t which);
 const char* tgmx_last_error(void);
 
@@ -2336,6 +2336,35 @@ int tgmx_node_analytics_step(const tgmx_node_analytics_t* st, const tgmx_an_batc
 /* Every entry of the pair table `from` moves into `to` (to_cap slots, all empty).  state: two int64, counters + 4 of the state above:
  * {status: TGMX_AN_TABLE_FULL where a claim found no room; entries moved, accumulating}. */
 int tgmx_node_analytics_rehash(const void* from, int64_t from_cap, void* to, int64_t to_cap, int64_t* state, tgmx_stream_t stream);
+
+/* ---- DensityOfStateEstimatorHook (the reference's examples/analytics/dos.py): the spectral density of one batch's graph by stochastic
+ * Chebyshev moments, the graph resident in LDS for the whole recurrence (csrc/dos.hip) ----
+ *
+ * G: the simple undirected graph of the E endpoint pairs (duplicates and reversed duplicates are one edge, a self-loop is one diagonal 1),
+ * its nodes the ids that occur, n of them, sorted.  S = L_norm - I: every stored entry, the diagonal included, is -1 / sqrt(d_i d_j) with
+ * d = A.sum(1), evaluated in float32 as -1.f / sqrtf((float)d_i * (float)d_j) with IEEE sqrt and divide.  Z [n, nZ]: Z[i, j] = +1 if bit 31
+ * of counter_u32(seed, call, node_id[i] * nZ + j) is clear, else -1.  T_0 = Z, T_1 = S Z, T_m = 2 S T_{m-1} - T_{m-2} in float32;
+ * c_m = mean_j sum_i Z_ij (T_m)_ij accumulated in double (c_0 = n: not normalised), times the Jackson factor
+ * g_m = ((N - m + 1) cos(tau m) + sin(tau m) / tan(tau)) / (N + 1), N = nM, tau = pi / (N + 1); x = linspace(-1 + 1e-8, 1 - 1e-8, n_pts),
+ * theta = acos x, y = c_0 (theta - pi) / 2 + sum_{m >= 1} c_m sin(m theta) / m, cdf = -2 y / pi, dos = max(diff(cdf), 0), in double.
+ *
+ * The envelope (tgmx_dos_supported): 1 <= E <= 4096 (2 E sort keys and, at one probe column a workgroup, 2 E rows fit gfx950's 160 KB of
+ * LDS), 1 <= nZ <= 1024, 2 <= nM <= 64, 2 <= n_pts <= 65536; ids in [0, 2^31): an event with an endpoint outside sets TGMX_AN_BAD_ID in
+ * *status (accumulating) and is skipped.  tgmx_dos_probe_width(E): the probe columns a moments workgroup owns, the widest of {8, 4, 2, 1}
+ * whose LDS fits (0 outside 1 .. 4096).  src / dst are int64 where their *_is64 flag is set, else int32.  dos [n_pts - 1] float64.
+ * Three launches (build, moments over ceil(nZ / width) workgroups, finish), no float atomics, nothing read back: equal arguments give
+ * equal bits. */
+typedef struct tgmx_dos {
+  const void* src; const void* dst; int64_t E; int32_t src_is64, dst_is64;
+  int32_t nZ, nM, n_pts, reserved0_;
+  uint64_t seed, call;
+  double* dos; int64_t* status;
+  void* workspace; size_t workspace_bytes;
+} tgmx_dos_t;
+int32_t tgmx_dos_supported(int64_t E, int32_t nZ, int32_t nM, int32_t n_pts);
+int32_t tgmx_dos_probe_width(int64_t E);
+size_t tgmx_dos_workspace_bytes(int64_t E, int32_t nZ, int32_t nM, int32_t n_pts);
+int tgmx_dos_estimate(const tgmx_dos_t* args, tgmx_stream_t stream);
 
 /* ---- TGBNegativeEdgeSamplerHook and its thgl / tkgl kin (the reference's tgm/hooks/negatives/tgb_sampler.py): the evaluation set of a
  * split, constant for its life, as a table on the device; a batch of positives is answered without a loop on the host. ----

@@ -1041,6 +1041,24 @@ SIGNATURES['tgmx_seen_nodes_step'] = (c_int32, [_P, c_int64, _P, c_int32, _P, c_
 SIGNATURES['tgmx_node_analytics_step'] = (c_int32, [ctypes.POINTER(NodeAnalytics), ctypes.POINTER(AnBatch), c_int64, _P, _P])
 SIGNATURES['tgmx_node_analytics_rehash'] = (c_int32, [_P, c_int64, _P, c_int64, _P, _P])
 
+
+class Dos(ctypes.Structure):
+    """tgmx_dos_t (include/tgm_amd.h)."""
+
+    _fields_ = [
+        ('src', c_void_p), ('dst', c_void_p), ('E', c_int64), ('src_is64', c_int32), ('dst_is64', c_int32),
+        ('nZ', c_int32), ('nM', c_int32), ('n_pts', c_int32), ('reserved0_', c_int32),
+        ('seed', ctypes.c_uint64), ('call', ctypes.c_uint64),
+        ('dos', c_void_p), ('status', c_void_p),
+        ('workspace', c_void_p), ('workspace_bytes', c_size_t),
+    ]  # fmt: skip
+
+
+SIGNATURES['tgmx_dos_supported'] = (c_int32, [c_int64, c_int32, c_int32, c_int32])
+SIGNATURES['tgmx_dos_probe_width'] = (c_int32, [c_int64])
+SIGNATURES['tgmx_dos_workspace_bytes'] = (c_size_t, [c_int64, c_int32, c_int32, c_int32])
+SIGNATURES['tgmx_dos_estimate'] = (c_int32, [ctypes.POINTER(Dos), _P])
+
 _lib: Optional[ctypes.CDLL] = None
 
 

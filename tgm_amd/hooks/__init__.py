@@ -10,7 +10,7 @@ from .uniform import NeighborSamplerHook
 from .time_gap import TimeGapNeighborHook
 from .registry import hook, list_hooks
 from . import neighbors  # noqa: E402,F401  (the reference's import path: tgm.hooks.neighbors.recency)
-from .analytics import BatchAnalyticsHook, NodeAnalyticsHook
+from .analytics import BatchAnalyticsHook, DensityOfStateEstimatorHook, NodeAnalyticsHook
 from .device import DeviceTransferHook, PinMemoryHook
 from .node_tracks import EdgeEventsSeenNodesTrackHook
 from . import negatives, tgb_sampler  # noqa: E402
@@ -27,6 +27,7 @@ __all__ = [
     'BatchAnalyticsHook',
     'DGHook',
     'DeduplicationHook',
+    'DensityOfStateEstimatorHook',
     'DeviceTransferHook',
     'EdgeEventsSeenNodesTrackHook',
     'HistoricalNegativeEdgeSamplerHook',
