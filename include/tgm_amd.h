@@ -59,7 +59,7 @@ int tgmx_version(void);
  * 12 tgmx_tgn_step_t, ..., 22 tgmx_ctan_fwd_t, 24 tgmx_gclstm_fwd_t, 26 tgmx_roland_fwd_t, 27 tgmx_decoder_fwd_t, 35 tgmx_ctan_bwd_t, 36 tgmx_graphmixer_bwd_t, 37 tgmx_dygformer_bwd_t, 38 tgmx_tpnet_bwd_t (23 and 25 are reserved and answer 0: tests/test_ctan_cpu.py and
  * tests/test_gclstm_cpu.py pin them), 28 tgmx_an_batch_t, 29 tgmx_node_analytics_t, 30 tgmx_decoder_train_t, 32 tgmx_gclstm_bwd_t (31 is
  * reserved the same way: tests/test_decoder_train_cpu.py), 39 tgmx_gcn_conv_bwd_t, 40 tgmx_tgcn_csr_fwd_t, 41 tgmx_tgcn_csr_bwd_t,
- * 43 tgmx_tconv_bwd_t (42 is reserved the same way: tests/test_gcn_sparse_cpu.py), 44 tgmx_dos_t */
+ * 43 tgmx_tconv_bwd_t (42 is reserved the same way: tests/test_gcn_sparse_cpu.py), 44 tgmx_dos_t, 45 tgmx_dos_large_t */
 size_t tgmx_abi_sizeof(int32_t which);
 const char* tgmx_last_error(void);
 
@@ -2365,6 +2365,28 @@ int32_t tgmx_dos_supported(int64_t E, int32_t nZ, int32_t nM, int32_t n_pts);
 int32_t tgmx_dos_probe_width(int64_t E);
 size_t tgmx_dos_workspace_bytes(int64_t E, int32_t nZ, int32_t nM, int32_t n_pts);
 int tgmx_dos_estimate(const tgmx_dos_t* args, tgmx_stream_t stream);
+
+/* The same estimate -- the definition, the probes, the float32 evaluation of S and of the recurrence, the double sums and the finish are
+ * those above -- for 4096 < E <= 2^22 events (csrc/dos_large.hip): the graph as the CSR of S in HBM (one radix sort of the 2 E directed
+ * keys, equal neighbours dropped, rows longer than 64 entries cut into chunks), the moments in ONE launch without grid-wide
+ * synchronisation: a workgroup owns a slab of tgmx_dos_large_probe_width(E, nZ) probe columns for all rows and all moments, its two T
+ * blocks in LDS where the graph has at most tgmx_dos_large_lds_rows(E, nZ) nodes, else in its own region of the workspace (chosen on the
+ * device: the node count is never read back).  The other limits, the fields and *status are tgmx_dos_t's.  The workspace is O(E) for the
+ * graph plus the T regions of the workgroups launched (at most 1 GiB of them, one at least): never nZ * n, never n^2.  No float atomics;
+ * the order of every sum is fixed by the CSR and by (E, nZ): equal arguments give equal bits.  Outside the envelope: 0 from the four
+ * queries, TGMX_E_INVALID from the call. */
+typedef struct tgmx_dos_large {
+  const void* src; const void* dst; int64_t E; int32_t src_is64, dst_is64;
+  int32_t nZ, nM, n_pts, reserved0_;
+  uint64_t seed, call;
+  double* dos; int64_t* status;
+  void* workspace; size_t workspace_bytes;
+} tgmx_dos_large_t;
+int32_t tgmx_dos_large_supported(int64_t E, int32_t nZ, int32_t nM, int32_t n_pts);
+int32_t tgmx_dos_large_probe_width(int64_t E, int32_t nZ);
+int32_t tgmx_dos_large_lds_rows(int64_t E, int32_t nZ);
+size_t tgmx_dos_large_workspace_bytes(int64_t E, int32_t nZ, int32_t nM, int32_t n_pts);
+int tgmx_dos_large_estimate(const tgmx_dos_large_t* args, tgmx_stream_t stream);
 
 /* ---- TGBNegativeEdgeSamplerHook and its thgl / tkgl kin (the reference's tgm/hooks/negatives/tgb_sampler.py): the evaluation set of a
  * split, constant for its life, as a table on the device; a batch of positives is answered without a loop on the host. ----

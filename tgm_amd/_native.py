@@ -1059,6 +1059,19 @@ SIGNATURES['tgmx_dos_probe_width'] = (c_int32, [c_int64])
 SIGNATURES['tgmx_dos_workspace_bytes'] = (c_size_t, [c_int64, c_int32, c_int32, c_int32])
 SIGNATURES['tgmx_dos_estimate'] = (c_int32, [ctypes.POINTER(Dos), _P])
 
+
+class DosLarge(ctypes.Structure):
+    """tgmx_dos_large_t (include/tgm_amd.h): tgmx_dos_t's fields."""
+
+    _fields_ = Dos._fields_
+
+
+SIGNATURES['tgmx_dos_large_supported'] = (c_int32, [c_int64, c_int32, c_int32, c_int32])
+SIGNATURES['tgmx_dos_large_probe_width'] = (c_int32, [c_int64, c_int32])
+SIGNATURES['tgmx_dos_large_lds_rows'] = (c_int32, [c_int64, c_int32])
+SIGNATURES['tgmx_dos_large_workspace_bytes'] = (c_size_t, [c_int64, c_int32, c_int32, c_int32])
+SIGNATURES['tgmx_dos_large_estimate'] = (c_int32, [ctypes.POINTER(DosLarge), _P])
+
 _lib: Optional[ctypes.CDLL] = None
 
 

@@ -59,6 +59,7 @@ extern "C" size_t tgmx_abi_sizeof(int32_t which) {
     case 41: return sizeof(tgmx_tgcn_csr_bwd_t);
     case 43: return sizeof(tgmx_tconv_bwd_t);  // (42 stays 0 for the same reason)
     case 44: return sizeof(tgmx_dos_t);
+    case 45: return sizeof(tgmx_dos_large_t);
     default: return 0;
   }
 }

@@ -18,9 +18,9 @@
 // Equal inputs give equal bits.
 //
 // Matrix instructions do not fit: a row holds two entries on average, there is no dense tile to feed an MFMA with.
-#include <atomic>
-
-#include "common.h"
+//
+// Past 4096 events the same estimate runs over a CSR in HBM: dos_large.hip.  dos_shared.h holds what the two routes share.
+#include "dos_shared.h"
 
 namespace tgmx {
 
@@ -29,12 +29,9 @@ constexpr int kDosBuildThreads = 1024;
 constexpr int kDosBuildPer = 8;         // keys a build thread owns at most: pow2(2 kDosMaxE) / kDosBuildThreads
 constexpr int kDosThreads = 512;        // moments kernel: 8 waves
 constexpr int kDosWaves = kDosThreads / kWave;
-constexpr int kDosChunk = 64;           // a row longer than this is summed in chunks of this many entries
 // nnz <= 8192: at most 8192 / 65 = 126 rows are longer than kDosChunk, and their chunks number sum ceil(len / 64) <= 8192 / 64 + 126 = 254
 constexpr int kDosMaxChunks = 256;
 constexpr int kDosMaxSplit = 128;
-constexpr size_t kDosLdsBudget = 160 * 1024;  // gfx950's LDS per CU; one workgroup may take all of it
-constexpr int kDosFinishThreads = 1024;
 constexpr unsigned long long kDosPadKey = ~0ull;  // sorts behind every key of ids < 2^31
 
 // header words of the workspace
@@ -60,28 +57,7 @@ struct DosArgs {
   unsigned long long* status;
 };
 
-// Exclusive scan over the workgroup (a multiple of 64 threads, <= 1024) of two counts packed as a << 16 | b; every total stays below 2^14, so
-// the halves never carry into each other.  *total: the sum over all threads.
-__device__ __forceinline__ unsigned dos_block_scan(unsigned v, unsigned* s_wave, unsigned* total) {
-  const int lane = lane_id(), wave = threadIdx.x / kWave, waves = blockDim.x / kWave;
-  unsigned incl = v;
-#pragma unroll
-  for (int off = 1; off < kWave; off <<= 1) {
-    const unsigned o = __shfl_up(incl, off);
-    if (lane >= off) incl += o;
-  }
-  if (lane == kWave - 1) s_wave[wave] = incl;
-  __syncthreads();
-  unsigned before = 0, all = 0;
-  for (int w = 0; w < waves; ++w) {
-    const unsigned t = s_wave[w];
-    if (w < wave) before += t;
-    all += t;
-  }
-  __syncthreads();  // s_wave may be written again
-  *total = all;
-  return before + incl - v;
-}
+// (dos_block_scan here: two counts packed as a << 16 | b in an unsigned; every total stays below 2^14)
 
 // ---- (a) the batch's graph as the CSR of S ------------------------------------------------------------------------------------------------
 
@@ -238,9 +214,7 @@ inline int dos_probe_width(long long E) {
   return 0;
 }
 
-__device__ __forceinline__ float dos_sign(const DosArgs& a, int node, int col) {
-  return (counter_u32(a.seed, a.call, (unsigned long long)(unsigned)node * (unsigned long long)a.nZ + (unsigned long long)col) >> 31) ? -1.f : 1.f;
-}
+__device__ __forceinline__ float dos_sign(const DosArgs& a, int node, int col) { return dos_sign(a.seed, a.call, a.nZ, node, col); }
 
 template <int PV>
 __global__ __launch_bounds__(kDosThreads) void dos_moments_kernel(DosArgs a) {
@@ -332,41 +306,7 @@ __global__ __launch_bounds__(kDosThreads) void dos_moments_kernel(DosArgs a) {
   }
 }
 
-// ---- (c) mean, Jackson filter, Chebyshev integration, diff and clip -------------------------------------------------------------------
-
-__global__ __launch_bounds__(kDosFinishThreads) void dos_finish_kernel(DosArgs a) {
-  __shared__ double s_c[64];
-  const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
-  const int nM = a.nM, nZ = a.nZ, n_pts = a.n_pts;
-  const double pi = 3.14159265358979323846;
-  // c_m = the mean over the columns: lane l adds columns l, l + 64, ... in order, then an xor tree; times the Jackson factor
-  for (int m = wave; m < nM; m += kDosFinishThreads / kWave) {
-    double s = 0.0;
-    for (int j = lane; j < nZ; j += kWave) s += a.cmom[(size_t)m * nZ + j];
-#pragma unroll
-    for (int off = 1; off < kWave; off <<= 1) s += __shfl_xor(s, off);
-    if (lane == 0) {
-      const double N = (double)nM, tau = pi / (N + 1.0);
-      const double g = ((N - m + 1.0) * cos(tau * m) + sin(tau * m) / tan(tau)) / (N + 1.0);
-      s_c[m] = g * (s / (double)nZ);
-    }
-  }
-  __syncthreads();
-  // cdf at x_i of linspace(-1 + 1e-8, 1 - 1e-8, n_pts) (numpy's: start + i step, the last point the stop itself)
-  const double lo = -1.0 + 1e-8, hi = 1.0 - 1e-8, step = (hi - lo) / (double)(n_pts - 1);
-  for (int i = tid; i < n_pts; i += kDosFinishThreads) {
-    const double x = i == n_pts - 1 ? hi : lo + (double)i * step;
-    const double th = acos(x);
-    double y = s_c[0] * (th - pi) / 2.0;
-    for (int m = 1; m < nM; ++m) y += s_c[m] * sin((double)m * th) / (double)m;
-    a.cdf[i] = y * (-2.0 / pi);
-  }
-  __syncthreads();  // the workgroup's own stores to cdf are visible to it
-  for (int i = tid; i < n_pts - 1; i += kDosFinishThreads) {
-    const double d = a.cdf[i + 1] - a.cdf[i];
-    a.dos[i] = d > 0.0 ? d : 0.0;
-  }
-}
+// ---- (c) mean, Jackson filter, Chebyshev integration, diff and clip: dos_finish_kernel (dos_shared.h) ------------------------------------
 
 static int dos_pow2(long long v) {
   int p = 2;
@@ -374,23 +314,6 @@ static int dos_pow2(long long v) {
   return p;
 }
 static size_t dos_align(size_t b) { return (b + 255) & ~(size_t)255; }
-
-// > 64 KB of dynamic LDS is a per-device opt-in of the function (as tgat.hip's chain kernel), made once for `bytes`: the most the function
-// ever asks for (its static LDS counts against the 160 KB too)
-template <typename K>
-static bool dos_reserve_lds(K kernel, std::atomic<bool>* flags, size_t bytes) {
-  constexpr int kMaxDevices = 64;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) dev = -1;
-  if (dev >= 0 && flags[dev].load(std::memory_order_acquire)) return true;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) {
-    (void)hipGetLastError();
-    set_error("dos_estimate: cannot reserve %zu bytes of LDS", bytes);
-    return false;
-  }
-  if (dev >= 0) flags[dev].store(true, std::memory_order_release);
-  return true;
-}
 
 }  // namespace tgmx
 
@@ -467,7 +390,7 @@ extern "C" int tgmx_dos_estimate(const tgmx_dos_t* args, tgmx_stream_t stream) {
 #undef TGMX_DOS_MOMENTS
   TGMX_CHECK_LAUNCH("dos_estimate(moments)");
 
-  hipLaunchKernelGGL(dos_finish_kernel, dim3(1), dim3(kDosFinishThreads), 0, st, a);
+  hipLaunchKernelGGL(dos_finish_kernel<DosArgs>, dim3(1), dim3(kDosFinishThreads), 0, st, a);
   TGMX_CHECK_LAUNCH("dos_estimate(finish)");
   return TGMX_OK;
 }

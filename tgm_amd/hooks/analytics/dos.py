@@ -19,18 +19,22 @@ clear, else ``-1`` (``probe_signs``), with ``seed`` the hook's ``seed=`` or ``to
 (1 for the first batch).  Keyed on the global node id, the estimate does not depend on how nodes are numbered locally.  Parity with the
 reference is therefore parity of the definition given Z, not of its random stream.
 
-On a ROCm device a batch is one ``tgmx_dos_estimate`` call (csrc/dos.hip: the batch's graph sorted, deduplicated and kept in LDS, the
-recurrence in float32 with float64 sums, three launches).  With ``sync=True`` ``batch.dos`` is a float64 numpy array as the reference's, the
-call's one read; with ``sync=False`` (extension, BatchAnalyticsHook's convention) a float64 device tensor, nothing read back.  Outside the
-kernel's envelope (more than 4096 events, more than 1024 probes, more than 64 moments, more than 65536 points) the device path is
-``_estimate_composed``: the same definition from stock torch ops in float32.  Host tensors run it over numpy in float64.  An empty batch
-gives zeros of length ``n_pts - 1`` (our choice: the reference raises on networkx's null graph).  An event with an endpoint outside
-[0, 2^31) is skipped, on every path; ``check()`` raises if a batch carried one.
+On a ROCm device a batch of up to 4096 events is one ``tgmx_dos_estimate`` call (csrc/dos.hip: the batch's graph sorted, deduplicated and
+kept in LDS, the recurrence in float32 with float64 sums, three launches).  A snapshot of 4097 to 2^22 events -- a day or a week of a stream
+-- is one ``tgmx_dos_large_estimate`` call (csrc/dos_large.hip: the graph as a CSR in HBM, the same recurrence and sums, a workgroup per slab
+of probe columns); ``TGMX_DOS_LARGE=torch`` sends that range to the composed path instead (``native`` is the default).  With ``sync=True``
+``batch.dos`` is a float64 numpy array as the reference's, the call's one read; with ``sync=False`` (extension, BatchAnalyticsHook's
+convention) a float64 device tensor, nothing read back.  Outside both envelopes (more than 2^22 events, more than 1024 probes, more than 64
+moments, more than 65536 points) the device path is ``_estimate_composed``: the same definition from stock torch ops in float32 over a dense
+[n, n] operator.  Host tensors run it over numpy in float64.  An empty batch gives zeros of length ``n_pts - 1`` (our choice: the reference
+raises on networkx's null graph).  An event with an endpoint outside [0, 2^31) is skipped, on every path; ``check()`` raises if a batch
+carried one.  ``last_path`` names the route of the last call: 'lds', 'csr', 'composed', 'host' or 'empty'.
 """
 from __future__ import annotations
 
 import ctypes
 import math
+import os
 from typing import Optional, Tuple
 
 import numpy as np
@@ -44,6 +48,7 @@ from ..registry import hook
 from .batch_analytics import _native_vector, require_on
 
 MAX_EVENTS, MAX_PROBES, MAX_MOMENTS, MAX_POINTS = 4096, 1024, 64, 65536  # tgmx_dos_supported
+MAX_EVENTS_LARGE = 1 << 22  # tgmx_dos_large_supported
 
 
 def supported(E: int, nZ: int, nM: int, n_pts: int) -> bool:
@@ -51,6 +56,18 @@ def supported(E: int, nZ: int, nM: int, n_pts: int) -> bool:
     width fits LDS (``tgmx_dos_probe_width(E) > 0``), true for every E up to ``MAX_EVENTS`` as the kernel is built; tests/test_dos_cpu.py
     holds the two together."""
     return 1 <= E <= MAX_EVENTS and 1 <= nZ <= MAX_PROBES and 2 <= nM <= MAX_MOMENTS and 2 <= n_pts <= MAX_POINTS
+
+
+def large_supported(E: int, nZ: int, nM: int, n_pts: int) -> bool:
+    """The CSR route's envelope (``tgmx_dos_large_supported``, mirrored; tests/test_dos_large_cpu.py holds the two together)."""
+    return MAX_EVENTS < E <= MAX_EVENTS_LARGE and 1 <= nZ <= MAX_PROBES and 2 <= nM <= MAX_MOMENTS and 2 <= n_pts <= MAX_POINTS
+
+
+def _large_route() -> str:
+    route = os.environ.get('TGMX_DOS_LARGE', 'native')
+    if route not in ('native', 'torch'):
+        raise ValueError(f"TGMX_DOS_LARGE must be 'native' or 'torch' (got {route!r})")
+    return route
 
 
 def probe_signs(seed: int, call: int, node_ids, nZ: int) -> np.ndarray:
@@ -122,6 +139,7 @@ class DensityOfStateEstimatorHook(StatelessHook):
         self._ws: Optional[torch.Tensor] = None
         self._status: Optional[torch.Tensor] = None
         self._bad_host = False
+        self.last_path: Optional[str] = None  # 'lds' | 'csr' | 'composed' | 'host' | 'empty'
         self.__post_init__()
 
     def __call__(self, dg: DGraph, batch: DGBatch) -> DGBatch:
@@ -133,37 +151,42 @@ class DensityOfStateEstimatorHook(StatelessHook):
         self.calls += 1
         E = 0 if src is None else int(src.numel())
         device = src.device if src is not None else torch.device('cpu')
+        shape = (E, self._probing_vectors, max(self._moments, 2), self._n_pts)
         if E == 0:
-            out = torch.zeros(self._n_pts - 1, dtype=torch.float64, device=device)
+            self.last_path, out = 'empty', torch.zeros(self._n_pts - 1, dtype=torch.float64, device=device)
         elif device.type != 'cuda':
-            out = torch.from_numpy(self._estimate_host(src, dst))
-        elif supported(E, self._probing_vectors, max(self._moments, 2), self._n_pts):
-            out = self._estimate_device(src, dst)
+            self.last_path, out = 'host', torch.from_numpy(self._estimate_host(src, dst))
+        elif supported(*shape):
+            self.last_path, out = 'lds', self._estimate_device(src, dst, large=False)
+        elif large_supported(*shape) and _large_route() == 'native':
+            self.last_path, out = 'csr', self._estimate_device(src, dst, large=True)
         else:
-            out = self._estimate_composed(src, dst)
+            self.last_path, out = 'composed', self._estimate_composed(src, dst)
         self.add_batch_attribute(batch, 'dos', out.cpu().numpy() if self.sync else out)  # sync: the one read of the batch
         return batch
 
-    def _estimate_device(self, src: torch.Tensor, dst: torch.Tensor) -> torch.Tensor:
+    def _estimate_device(self, src: torch.Tensor, dst: torch.Tensor, large: bool) -> torch.Tensor:
+        """One C call, nothing read back: ``tgmx_dos_estimate`` (the graph in LDS) or ``tgmx_dos_large_estimate`` (the graph as a CSR)."""
         device = src.device
         require_on(device, 'DensityOfStateEstimatorHook', edge_src=src, edge_dst=dst)
         src, dst = _native_vector(src, 'edge_src'), _native_vector(dst, 'edge_dst')
         lib = _native.load()
-        a = _native.Dos()
+        a = _native.DosLarge() if large else _native.Dos()
+        workspace_bytes, estimate = (lib.tgmx_dos_large_workspace_bytes, lib.tgmx_dos_large_estimate) if large else (lib.tgmx_dos_workspace_bytes, lib.tgmx_dos_estimate)
         a.src, a.dst, a.E = src.data_ptr(), dst.data_ptr(), src.numel()
         a.src_is64, a.dst_is64 = int(src.dtype == torch.int64), int(dst.dtype == torch.int64)
         a.nZ, a.nM, a.n_pts = self._probing_vectors, max(self._moments, 2), self._n_pts
         a.seed, a.call = self._rng_seed, self.calls
-        nbytes = int(lib.tgmx_dos_workspace_bytes(a.E, a.nZ, a.nM, a.n_pts))
+        nbytes = int(workspace_bytes(a.E, a.nZ, a.nM, a.n_pts))
         if self._ws is None or self._ws.numel() < nbytes or self._ws.device != device:
             self._ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
         if self._status is None or self._status.device != device:
             self._status = torch.zeros(1, dtype=torch.int64, device=device)
         out = torch.empty(self._n_pts - 1, dtype=torch.float64, device=device)
         a.dos, a.status, a.workspace, a.workspace_bytes = out.data_ptr(), self._status.data_ptr(), self._ws.data_ptr(), self._ws.numel()
-        rc = lib.tgmx_dos_estimate(ctypes.byref(a), _native.stream_ptr(device.index))
+        rc = estimate(ctypes.byref(a), _native.stream_ptr(device.index))
         if rc:
-            _native.check(rc, 'tgmx_dos_estimate')
+            _native.check(rc, 'tgmx_dos_large_estimate' if large else 'tgmx_dos_estimate')
         return out
 
     def _valid(self, s, d):

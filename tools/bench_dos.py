@@ -1,8 +1,11 @@
 #!/usr/bin/env python
-"""DensityOfStateEstimatorHook per batch, in microseconds, on two shapes:
+"""DensityOfStateEstimatorHook per batch, in microseconds, on two batch shapes and three snapshot shapes:
 
   wiki      the example's setting (examples/analytics/dos.py): the wiki-shaped stream, bs = 200, 20 moments, 100 probes, 1001 points
   comment   the comment-shaped stream (1 000 000 nodes), bs = 4096, its first --comment-edges events, the same estimator
+  wiki_day  a snapshot: the first 5 200 events of the wiki-shaped stream (9 227 ids) as ONE batch (csrc/dos_large.hip past 4096 events)
+  snap64k   a snapshot: 65 536 uniform events over 100 000 ids
+  snap1m    a snapshot: the first 1 000 000 events of the comment-shaped stream (1 000 000 ids)
 
 Measured in the same process:
 
@@ -13,8 +16,9 @@ Measured in the same process:
 
 A timed window is K consecutive batches between two device synchronisations, on a host clock; each figure is the median of --windows
 windows with the spread beside it, and native and composed windows alternate so that a pair shares the machine's state.  Before anything is
-reported the two ways are compared on one batch.  Appends one JSON line per shape to --out.
-    python tools/bench_dos.py [--out FILE] [--shapes wiki,comment]"""
+reported the two ways are compared on one batch.  Where the composed path cannot allocate its dense operator the line says so instead of
+giving a time.  Appends one JSON line per shape to --out (the snapshot shapes: profiles/r39_bench_dos_large.jsonl).
+    python tools/bench_dos.py [--out FILE] [--shapes wiki,comment,wiki_day,snap64k,snap1m]"""
 import argparse
 import json
 import os
@@ -52,9 +56,16 @@ def spread(v):
     return {'median': round(statistics.median(v), 1), 'min': round(min(v), 1), 'max': round(max(v), 1), 'windows': len(v)}
 
 
+def stream(shape: str, edges: int):
+    if shape == 'snap64k':
+        gen = torch.Generator().manual_seed(SEED)
+        return tuple(torch.randint(0, 100_000, (edges,), generator=gen, dtype=torch.int32).to(dev) for _ in range(2))
+    s = make_stream({'wiki_day': 'wiki', 'snap1m': 'comment'}.get(shape, shape), num_edges=edges, edge_dim=0)
+    return s.src.to(dev), s.dst.to(dev)
+
+
 def run(shape: str, bs: int, edges: int, K: int) -> dict:
-    s = make_stream(shape, num_edges=edges, edge_dim=0)
-    src, dst = s.src.to(dev), s.dst.to(dev)
+    src, dst = stream(shape, edges)
     per_pass = edges // bs
 
     def batch(i, to=None):
@@ -79,9 +90,16 @@ def run(shape: str, bs: int, edges: int, K: int) -> dict:
         'native_sync': (lambda h: lambda b: h(None, b))(new()),
         'composed': composed_step(),
     }
-    for step in steps.values():
-        for i in range(5):
-            step(batch(i))
+    cannot = None
+    for name, step in list(steps.items()):
+        try:
+            for i in range(5):
+                step(batch(i))
+        except torch.OutOfMemoryError as e:  # the composed path's dense [n, n] operator
+            assert name == 'composed'
+            cannot = 'cannot allocate: ' + str(e).split('.')[0]
+            del steps[name]
+            torch.cuda.empty_cache()
     # windows of the three ways interleaved: window w of each runs over the same K batches
     out = {k: [] for k in steps}
     t_end = time.perf_counter() + args.step_seconds
@@ -111,11 +129,16 @@ def run(shape: str, bs: int, edges: int, K: int) -> dict:
     b = batch(3)
     a, c = new(sync=False), new(sync=False)
     native = a(None, types.SimpleNamespace(**vars(b))).dos.cpu().numpy()
+    head = {
+        'bench': 'dos_hook', 'shape': shape, 'device': torch.cuda.get_device_name(0) if dev.type == 'cuda' else 'cpu (rehearsal)', 'bs': bs,
+        'moments': MOMENTS, 'probes': PROBES, 'n_pts': POINTS, 'batches_per_window': K, 'native_path': a.last_path,
+    }  # fmt: skip
+    if cannot:
+        return {**head, 'composed': cannot, 'per_kernel_us': 'not measured', 'us_per_batch': result}
     c._rng_seed, c.calls = SEED, 1
     composed = c._estimate_composed(b.edge_src, b.edge_dst).cpu().numpy()
     return {
-        'bench': 'dos_hook', 'shape': shape, 'device': torch.cuda.get_device_name(0) if dev.type == 'cuda' else 'cpu (rehearsal)', 'bs': bs,
-        'moments': MOMENTS, 'probes': PROBES, 'n_pts': POINTS, 'batches_per_window': K,
+        **head,
         'native_vs_composed_max_diff_of_max': float(np.abs(native - composed).max() / composed.max()),
         'native_faster_in_every_window_pair': bool(all(n < c for n, c in zip(out['native_sync'], out['composed'])) and all(n < c for n, c in zip(out['native_nosync'], out['composed']))),
         'speedup_nosync': round(result['composed']['median'] / result['native_nosync']['median'], 1),
@@ -125,7 +148,8 @@ def run(shape: str, bs: int, edges: int, K: int) -> dict:
     }  # fmt: skip
 
 
-SHAPES = {'wiki': (200, 157_474, 50), 'comment': (4096, args.comment_edges, 20)}
+SHAPES = {'wiki': (200, 157_474, 50), 'comment': (4096, args.comment_edges, 20),
+          'wiki_day': (5200, 5200, 5), 'snap64k': (65536, 65536, 2), 'snap1m': (1_000_000, 1_000_000, 1)}  # fmt: skip
 for name in args.shapes.split(','):
     bs, edges, K = SHAPES[name]
     line = json.dumps(run(name, bs, edges, K))
