@@ -111,12 +111,23 @@ int tgmx_recency_lookup_csr(const int64_t* indptr, const tgmx_adj_t* adj,
  * order, left aligned, padded with (-1, 0, 0.0) -- bit-exact with the reference.  More than k: a uniformly random
  * k-permutation without replacement (virtual Fisher-Yates), a deterministic function of (rng_seed, rng_stream, node) so
  * that every occurrence of a node in one call gets the same row, as in the reference.  The reference draws with
- * Python's Mersenne Twister (random.sample), so parity there is distributional.  k <= 64. */
+ * Python's Mersenne Twister (random.sample), so parity there is distributional.  k <= 64 here (one wave per seed, the
+ * shuffle as a serial chain inside the wave); 64 < k <= 2048: tgmx_uniform_lookup_wide below. */
 int tgmx_uniform_lookup_csr(const int64_t* indptr, const tgmx_adj_t* adj, const float* edge_x, int32_t D,
                             const int32_t* seeds, int64_t S, int32_t k, int64_t ev_hi, int32_t num_nodes,
                             int32_t allow_pad, uint64_t rng_seed, uint64_t rng_stream,
                             int32_t* out_nid, int64_t* out_ts, float* out_x, int32_t* status,
                             tgmx_stream_t stream);
+
+/* The same lookup, arguments and draw for 64 < k <= 2048 (any other k: TGMX_E_INVALID): one workgroup per seed, all k
+ * picks computed at once, grouped by an LDS sort and resolved by pointer jumping instead of the serial chain
+ * (csrc/uniform_wide.hip).  Where both apply the definition is one: the row of (rng_seed, rng_stream, node) is what the
+ * serial shuffle gives, slot for slot. */
+int tgmx_uniform_lookup_wide(const int64_t* indptr, const tgmx_adj_t* adj, const float* edge_x, int32_t D,
+                             const int32_t* seeds, int64_t S, int32_t k, int64_t ev_hi, int32_t num_nodes,
+                             int32_t allow_pad, uint64_t rng_seed, uint64_t rng_stream,
+                             int32_t* out_nid, int64_t* out_ts, float* out_x, int32_t* status,
+                             tgmx_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * Streaming mode: per-node rings of B records, the exact state machine of the

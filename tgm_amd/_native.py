@@ -398,6 +398,7 @@ ACCOUNTING_PARTIALS = 1024
 SIGNATURES['tgmx_lookup_accounting'] = (c_int32, [_P, c_int64, _P, _P, c_int64, _P, _P])
 SIGNATURES['tgmx_uniform_lookup_csr'] = (c_int32, [_P, _P, _P, c_int32, _P, c_int64, c_int32, c_int64, c_int32, c_int32, ctypes.c_uint64, ctypes.c_uint64,
                                                    _P, _P, _P, _P, _P])
+SIGNATURES['tgmx_uniform_lookup_wide'] = SIGNATURES['tgmx_uniform_lookup_csr']  # 64 < k <= 2048, same arguments
 SIGNATURES['tgmx_ring_update_scratch_bytes'] = (c_size_t, [c_int64, c_int32])
 SIGNATURES['tgmx_defer_create'] = (c_void_p, [c_int32, c_int32])
 SIGNATURES['tgmx_defer_destroy'] = (None, [_P])

@@ -37,16 +37,10 @@
 #include <rocprim/iterator/counting_iterator.hpp>
 #include <rocprim/iterator/transform_iterator.hpp>
 
+#include "adj_rec.h"
 #include "common.h"
 
 namespace tgmx {
-
-struct __align__(16) Rec {
-  int nbr;
-  int eid;
-  long long ts;
-};
-static_assert(sizeof(Rec) == sizeof(tgmx_adj_t), "record layout");
 
 // hop-0 seeds given as groups (recency.py:173-237 concatenates them with torch.cat): the lookup wave of seed s
 // reads its (node, time) from the group that covers s and publishes the concatenation as a side effect
@@ -221,36 +215,7 @@ __device__ __forceinline__ float2 zero_vec<float2>() { return make_float2(0.f, 0
 template <>
 __device__ __forceinline__ float zero_vec<float>() { return 0.f; }
 
-// Number of records in [a, z) whose eid < bound, given that those records form
-// a prefix (true for batch-boundary bounds).  64 probes/round.
-__device__ __forceinline__ long long wave_prefix_count(const Rec* recs, long long a, long long z,
-                                                       long long bound, int lane) {
-  long long lo = a, hi = z;
-  while (hi - lo > kWave) {
-    const long long len = hi - lo;
-    const long long stride = (len + kWave - 1) / kWave;
-    long long idx = lo + (long long)(lane + 1) * stride - 1;
-    if (idx > hi - 1) idx = hi - 1;
-    const bool less = (long long)recs[idx].eid < bound;
-    const int c = __popcll(__ballot(less));
-    long long nlo = lo, nhi = hi;
-    if (c > 0) {
-      long long p = lo + (long long)c * stride - 1;
-      if (p > hi - 1) p = hi - 1;
-      nlo = p + 1;
-    }
-    if (c < kWave) {
-      long long p = lo + (long long)(c + 1) * stride - 1;
-      if (p > hi - 1) p = hi - 1;
-      nhi = p;  // recs[p] is >= bound: the answer is <= p
-    }
-    lo = nlo;
-    hi = nhi < nlo ? nlo : nhi;
-  }
-  const long long idx = lo + lane;
-  const bool less = idx < hi && (long long)recs[idx].eid < bound;
-  return lo + __popcll(__ballot(less)) - a;
-}
+// (Rec and wave_prefix_count, the 64-ary search for a node's visible prefix: adj_rec.h)
 
 // ---------------------------------------------------------------------------
 // Streaming rings: batched append -- a faithful restatement of
@@ -3205,26 +3170,7 @@ using namespace tgmx;
 
 namespace tgmx {
 
-struct UniformArgs {
-  const int64_t* indptr;
-  const Rec* recs;
-  const float* edge_x;
-  const int32_t* seeds;
-  int32_t* out_nid;
-  int64_t* out_ts;
-  float* out_x;
-  int32_t* status;
-  long long S, ev_hi;
-  unsigned long long rng_seed, rng_stream;
-  int D, k, N, allow_pad;
-};
-
-__device__ __forceinline__ unsigned long long splitmix64(unsigned long long x) {
-  x += 0x9E3779B97F4A7C15ull;
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-  return x ^ (x >> 31);
-}
+// (UniformArgs and splitmix64: adj_rec.h, shared with the kernel for 64 < k <= 2048 in uniform_wide.hip)
 
 // One wave per seed.  c = #candidates (prefix of the node's (eid, role)-ordered entries below ev_hi).
 // c <= k: lane j takes candidate j.  c > k: k steps of a virtual Fisher-Yates shuffle of [0, c) -- the array is the

@@ -4,7 +4,10 @@ Reference: ``tgm/hooks/neighbors/uniform.py:16-142`` over ``DGStorageArrayBacken
 (``tgm/core/_storage/backends/array_backend.py:108-171``), which walks every edge before the batch in a Python loop
 per hop (quadratic per epoch, its own comment says so).  Here the candidates of a node are a prefix of its entries
 in a static per-node index ordered by ``(eid, role)`` (``tgmx_csr_build(num_batches=-1)``), found by a 64-ary wave
-search, and the draw is a virtual Fisher-Yates shuffle inside the kernel (``tgmx_uniform_lookup_csr``).
+search, and the draw is a virtual Fisher-Yates shuffle inside the kernel: ``tgmx_uniform_lookup_csr`` up to 64 neighbors per
+hop (one wave per seed, the shuffle as a serial chain), ``tgmx_uniform_lookup_wide`` from 65 to 2048 (a workgroup per seed, all
+picks at once, grouped by an LDS sort and resolved by pointer jumping).  Both compute the same draw, and each hop takes the entry
+point its own ``k`` asks for.
 
 Parity: rows with at most k candidates are bit-exact with the reference (all neighbors, event order, left aligned);
 rows that are sampled are uniformly random k-subsets like the reference's ``random.sample``, but drawn from a
@@ -27,13 +30,15 @@ from .base import SeedableHook, StatelessHook
 from .recency import RecencyNeighborHook
 from .registry import hook
 
+WAVE_NBRS = 64  # k up to here: tgmx_uniform_lookup_csr; past it, up to MAX_NBRS: tgmx_uniform_lookup_wide
+MAX_NBRS = 2048
 
 @hook
 class NeighborSamplerHook(StatelessHook, SeedableHook):
     """Load neighbors from the DGraph with uniform sampling.
 
     Args:
-        num_nbrs: neighbors to sample at each hop.
+        num_nbrs: neighbors to sample at each hop (at most 2048 per hop; more raises ``NotImplementedError``).
         seed_nodes_keys / seed_times_keys: batch attributes naming hop-0 seeds / query times.
         directed: only aggregate src->dst interactions.
         id: suffix for the hook name and every produced attribute.
@@ -55,8 +60,8 @@ class NeighborSamplerHook(StatelessHook, SeedableHook):
                 f'len(seed_nodes_keys) ({len(seed_nodes_keys)}) != len(seed_times_keys) ({len(seed_times_keys)})\n'
                 f'seed_nodes_keys={seed_nodes_keys}, seed_times_keys={seed_times_keys}'
             )
-        if max(num_nbrs) > 64:
-            raise NotImplementedError('tgm_amd NeighborSamplerHook supports at most 64 neighbors per hop')
+        if max(num_nbrs) > MAX_NBRS:
+            raise NotImplementedError(f'tgm_amd NeighborSamplerHook supports at most {MAX_NBRS} neighbors per hop')
         self._num_nbrs = list(num_nbrs)
         self._directed = bool(directed)
         self._seed_nodes_keys = list(seed_nodes_keys)
@@ -143,13 +148,15 @@ class NeighborSamplerHook(StatelessHook, SeedableHook):
                     nid = torch.empty((S, k), dtype=torch.int32, device=device)
                     nts = torch.empty((S, k), dtype=torch.int64, device=device)
                     nx = torch.empty((S, k, D), dtype=torch.float32, device=device)
+                    # each hop by its own k: one wave per seed up to 64, a workgroup per seed (csrc/uniform_wide.hip) past that -- one draw
+                    entry = 'tgmx_uniform_lookup_csr' if k <= WAVE_NBRS else 'tgmx_uniform_lookup_wide'
                     _native.check(
-                        lib.tgmx_uniform_lookup_csr(
+                        getattr(lib, entry)(
                             csr.indptr.data_ptr(), csr.adj.data_ptr(), _native.ptr(edge_x), D, cur_n.data_ptr(), S, k, ev_hi,
                             self._num_nodes, 1 if hop else 0, self._rng_seed, (self._calls << 8) | hop, nid.data_ptr(), nts.data_ptr(),
                             nx.data_ptr(), self._status.data_ptr(), stream,
                         ),
-                        'tgmx_uniform_lookup_csr',
+                        entry,
                     )  # fmt: skip
                     out_seed_n.append(cur_n)
                     out_seed_t.append(cur_t)
